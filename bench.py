@@ -60,6 +60,7 @@ HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8.0 TB/s spec
 BYTES_PER_LINK_UPDATE = 212      # 128 B read + 84 B written per link-update, full-record mode
 NODE_KERNEL_BYTES = 164          # of which sending/receiving/solve/cumulative update (node_kernel): 116 B read + 48 B written
 LINK_KERNEL_BYTES = 48           # density / speed / travel-time update (link_kernel): 12 B read + 36 B written
+DUMP_BYTES = 48 << 20            # --dump-outputs writes at most this many bytes of arrays (a replica sample beyond it)
 
 
 def replica_demand(T, key, base=5.0, peak=10.0):
@@ -455,6 +456,26 @@ def bench_rl(args):
     print(json.dumps(measure_rl(args.network, args.replicas, args.steps, args.warmup, args.history, args.randomize)), flush=True)
 
 
+def dump_outputs(e, t, directory, offset=0):
+    """--dump-outputs: what the timed region's LAST step (network_loading(t)) wrote, as a caller reads it back (pedn_read): one
+    DIR/<field>.npy per history field, [replicas, columns] in the field's own dtype (f64 / f32), row t -- row t - 1 for
+    sending_flow / receiving_flow, the entries step t writes for those (include/pedn.h).  When all replicas would exceed
+    DUMP_BYTES, a fixed sample of them (seeded, sorted) is written; DIR/replicas.npy holds their global replica ids (float64)."""
+    from pednstream_amd.network import LINK_FIELDS
+
+    R = e.n_replicas
+    cols = {fid: e.n_all if fid < 4 else e.n_links for fid, _ in LINK_FIELDS.values()}
+    per_replica = sum(cols[fid] * np.dtype(dt).itemsize for fid, dt in LINK_FIELDS.values()) + 8
+    n = min(R, DUMP_BYTES // per_replica)
+    pick = np.arange(R) if n == R else np.sort(np.random.default_rng(0).choice(R, n, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, (fid, dt) in LINK_FIELDS.items():
+        row = t - 1 if name in ("sending_flow", "receiving_flow") else t
+        a = e.read_block(fid, row, row + 1)[0]                 # [columns, R]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a[:, pick].T.astype(dt, copy=False)))
+    np.save(os.path.join(directory, "replicas.npy"), (offset + pick).astype(np.float64))
+
+
 def spawn_ranks(args, argv):
     """`python bench.py --gpus N` (N > 1) outside a launcher: start the N ranks as a CHILD process (torch.distributed.run, one
     rank per GPU, rendezvous on 127.0.0.1) before this process has touched the GPU, and hand its exit code back."""
@@ -546,6 +567,8 @@ def measure(args, network, dist, rank, local_rank, world, demand_scale=1.0):
     rc, _ = e.error_flags()
     if rc != 0:
         raise SystemExit(f"model error flags set: {rc}")
+    if args.dump_outputs:
+        dump_outputs(e, state["t"] - 1, args.dump_outputs, offset)
 
     # per-launch durations (the dispatches' own start / stop timestamps) under the SAME launch plan as the timed region, continuing
     # the same simulation.  chains = 2: run() launched the two halves of the replicas as two chains on two streams; a launch then
@@ -780,7 +803,11 @@ def main():
                     "(BASELINE config #4: --total-replicas 4096; its weak-scaling shape is --replicas 512)")
     ap.add_argument("--history", default="full", choices=["full", "recent"], help="full: the reference's footprint (the headline mode); "
                     "recent: rings for everything the recurrence does not look far back into (include/pedn.h PEDN_HIST_RECENT)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them computed "
+                    "(every history field's row of that step, a fixed sample of the replicas, <= 48 MB) as DIR/<field>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.rl or args.gpus != 1):
+        raise SystemExit("--dump-outputs is supported for the link-update workload on one GPU (--gpus 1, no --rl)")
     if args.rl:
         return bench_rl(args)
 
@@ -847,7 +874,7 @@ def main():
 
         def variant(network, replicas=1024, steps=None, warmup=None, demand_scale=1.0, cpu_seconds=0.0):
             a2 = copy.copy(args)
-            a2.replicas, a2.no_extra = replicas, True
+            a2.replicas, a2.no_extra, a2.dump_outputs = replicas, True, None
             a2.steps, a2.warmup = steps or args.steps, warmup or args.warmup
             ex, net2, origins2 = measure(a2, network, None, 0, local_rank, 1, demand_scale=demand_scale)
             try:

@@ -1,11 +1,13 @@
 """bench.py without a GPU: the command line the driver uses parses, the synthetic demand is a function of the replica id only
 (it keys results to the GLOBAL replica id, whatever the rank count), and a WORLD_SIZE that disagrees with --gpus is refused
 before anything is imported."""
+import json
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -14,7 +16,8 @@ BENCH = os.path.join(ROOT, "bench.py")
 def test_help_lists_the_contract_flags():
     out = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--replicas", "--total-replicas", "--network", "--rl", "--randomize", "--history"):
+    for flag in ("--gpus", "--steps", "--warmup", "--replicas", "--total-replicas", "--network", "--rl", "--randomize", "--history",
+                 "--dump-outputs"):
         assert flag in out.stdout, flag
 
 
@@ -93,3 +96,96 @@ def test_compact_line_is_small_and_carries_the_contract_fields():
     assert all(len(json.dumps(v)) < 900 for v in d["extra"].values())
     # no prose anywhere
     assert "xxxx" not in line.replace(d["extra"]["broken"]["error"], "")
+
+
+def test_dump_outputs_is_refused_where_it_is_not_supported(tmp_path):
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    for extra in (["--gpus", "2"], ["--rl"]):
+        out = subprocess.run([sys.executable, BENCH, "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "d")] + extra,
+                             capture_output=True, text=True, env=env, timeout=120)
+        assert out.returncode != 0 and "--dump-outputs" in out.stderr, extra
+    assert not (tmp_path / "d").exists()
+
+
+class _FakeEngine:
+    """read_block of a known pattern: value = field * 1e6 + row * 1e3 + column + replica / 1e4."""
+
+    def __init__(self, n_links, n_vlinks, n_replicas):
+        self.n_links, self.n_all, self.n_replicas = n_links, n_links + n_vlinks, n_replicas
+
+    def read_block(self, field, t0, t1):
+        cols = self.n_all if field < 4 else self.n_links
+        t, c, r = np.meshgrid(np.arange(t0, t1), np.arange(cols), np.arange(self.n_replicas), indexing="ij")
+        return (field * 1e6 + t * 1e3 + c + r / 1e4).astype(np.float64 if field < 7 else np.float32)
+
+
+@pytest.mark.parametrize("n_links, n_replicas", [(24, 64), (938, 1024)])
+def test_dump_outputs_writes_the_last_step_within_the_budget(tmp_path, n_links, n_replicas):
+    sys.path.insert(0, ROOT)
+    import bench
+    from pednstream_amd.network import LINK_FIELDS
+
+    e, t = _FakeEngine(n_links, 9, n_replicas), 25
+    bench.dump_outputs(e, t, str(tmp_path / "a"), offset=100)
+    bench.dump_outputs(e, t, str(tmp_path / "b"), offset=100)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted([f + ".npy" for f in LINK_FIELDS] + ["replicas.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 10 ** 6
+    reps = np.load(tmp_path / "a" / "replicas.npy")
+    assert reps.dtype == np.float64 and np.all(np.diff(reps) > 0) and 100 <= reps[0] and reps[-1] < 100 + n_replicas
+    if n_replicas == 64:
+        assert np.array_equal(reps, 100 + np.arange(64))           # everything fits: every replica
+    else:
+        assert len(reps) < n_replicas                             # a sample
+    for name, (fid, dt) in LINK_FIELDS.items():
+        a = np.load(tmp_path / "a" / (name + ".npy"))
+        assert a.dtype == dt and np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy")))   # the same sample every run
+        row = t - 1 if name in ("sending_flow", "receiving_flow") else t
+        cols = e.n_all if fid < 4 else n_links
+        want = e.read_block(fid, row, row + 1)[0][:, (reps - 100).astype(int)].T
+        assert a.shape == (len(reps), cols) and np.array_equal(a, want), name
+
+
+@pytest.mark.gpu
+def test_dump_outputs_repeat_and_match_the_oracle(tmp_path):
+    """Two runs of the same command dump the same arrays bit for bit, and those are the CPU oracle's rows of the last timed step
+    for the same replicas (same Philox keys, same per-replica demand)."""
+    import oracle_driver as od
+    from golden_util import DATA
+    from pednstream_amd import NetworkEnvGenerator
+    from pednstream_amd.flatten import flatten_network
+    from pednstream_amd.network import LINK_FIELDS
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    steps, warmup, R = 7, 4, 64
+    dirs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--network", "nine_intersections", "--replicas", str(R), "--steps", str(steps),
+                              "--warmup", str(warmup), "--no-extra", "--no-cpu-baseline", "--no-live-traffic", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        dirs.append(d)
+    for name in list(LINK_FIELDS) + ["replicas"]:
+        assert np.array_equal(np.load(dirs[0] / (name + ".npy")), np.load(dirs[1] / (name + ".npy"))), name
+
+    net = NetworkEnvGenerator(DATA).create_network("nine_intersections", verbose=False, n_replicas=R, rng_seed=0)
+    model, T = flatten_network(net), net.simulation_steps
+    t = warmup + steps                          # the clock starts at 1: the last timed step is network_loading(warmup + steps)
+    reps = np.load(dirs[0] / "replicas.npy").astype(int)
+    assert np.array_equal(reps, np.arange(R))
+    for i in (0, R - 1):
+        o = od.Oracle(model, seed=0, replica=i)
+        for nid in net.origin_nodes:
+            o.set_demand(net.nodes[nid].index, bench.replica_demand(T, i))
+        o.run(1, t + 1)
+        for name in LINK_FIELDS:
+            row = t - 1 if name in ("sending_flow", "receiving_flow") else t
+            assert np.array_equal(np.load(dirs[0] / (name + ".npy"))[i], o.field(name)[:, row]), (name, i)
+        o.close()
