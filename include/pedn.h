@@ -261,7 +261,8 @@ int pedn_set_streams(pedn_sim* sim, int32_t n);
  * the runtime may map two streams onto one hardware queue, which would serialise the chains), info[3] = duration in microseconds of
  * the probe's two concurrent 300 us kernels on the pair kept (~300: they overlap, ~600: they do not); n = entries of info (>= 4);
  * with n >= 5: info[4] = how nodes were packed into the node kernel's workgroups: 0 by degree, 1 by the static load estimate, 2 by
- * the measured cost pedn_model_desc.node_cost. */
+ * the measured cost pedn_model_desc.node_cost; with n >= 6: info[5] = 1 when those one-launch steps skip the loads of corridors that were
+ * empty in all 64 replicas of a group at the step before (quiet corridors, PEDN_QUIET=0|1; results are the same either way). */
 int pedn_plan_info(pedn_sim* sim, int32_t* info, int32_t n);
 
 /* reset all histories and dynamic state to t = 0 (widths, turning fractions and demand are kept) */

@@ -56,6 +56,12 @@ struct pedn_sim {
   int clock_t0 = 0;   // step the clock was set to by pedn_rl_clock_begin
   int valid_hi = 0x7fffffff;   // lazy reset: history rows above this index are neither written nor cleared (DevView.valid_hi)
   int link_pending = -1;  // owner-wave plan: step whose link update has not been performed yet, -1 none
+  // Quiet corridors (DevView.quiet): node_kernel<LU> launches store the words (PEDN_QUIET=0|1, default wherever link_owner is chosen);
+  // quiet_valid = the step whose words every replica group has, from a node_kernel<LU> launch on each chain with no change of a history
+  // row since -- the next LU launch may use them; -1 none.  Cleared by everything that could break that (no_quiet).
+  int quiet = 0;
+  int quiet_valid = -1;
+  uint32_t* d_quiet = nullptr;
   int fuse_obs = 1;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
   // (The link update as a launch of its own runs one replica per lane -- link_kernel_1r: 42-47 VGPRs, 8 waves per SIMD; melbourne x 1024
   // 12.3-12.6 against 12.7-13.1 us with two replicas per lane, profiles/r03_link_kernel_variants.txt; inside link_turn_kernel, whose
@@ -118,6 +124,9 @@ struct pedn_sim {
   size_t rl_pin_bytes = 0;
   std::string err;
 };
+
+// the quiet words of the last step may not be used by the next launch (pedn_sim.quiet_valid)
+static inline void no_quiet(pedn_sim* s) { s->quiet_valid = -1; }
 
 static int fail(pedn_sim* s, int code, const std::string& msg) {
   g_last_error = msg;
@@ -305,6 +314,7 @@ static int reset_state_lazy(pedn_sim* s) {
 // has not run, a zero-copy consumer).
 static int catch_up(pedn_sim* s, int upto) {
   if (s->valid_hi >= upto) return PEDN_OK;
+  no_quiet(s);
   upto = std::min(upto, s->v.T1 - 1);
   DevView view = s->v;
   int rc = PEDN_OK;
@@ -881,6 +891,12 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
         base += d * d;  // <= 64 tiles because sum(d) <= 8
       }
     }
+    {  // the mirror of a physical slot: the slot whose incoming link is its outgoing link (every physical link is the incoming link of one slot)
+      std::vector<int32_t> pos_of(L, -1);
+      for (size_t i = 0; i < rec.size(); ++i)
+        if (rec[i].node >= 0 && rec[i].lin < L) pos_of[rec[i].lin] = (int32_t)i;
+      for (SlotRec& R : rec) R.mirror = R.node >= 0 && R.lin < L && R.lout < L ? pos_of[R.lout] : -1;
+    }
     s->n_blocks = (int)bins.size();
     for (int n = 0; n < N; ++n) s->max_degree = std::max(s->max_degree, deg(n));
     if (const char* f = getenv("PEDN_NODE_MD")) if (atoi(f) == 8) s->max_degree = 8;  // diagnostic: the general instantiation
@@ -952,6 +968,9 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
       (void)hipGetLastError();
     }
     if (s->inline_tf) s->link_owner = 1;
+    // quiet corridors: the owner-wave launches skip the loads of corridors that are empty in all 64 replicas of a group (node_step)
+    s->quiet = s->link_owner && m->node_model != PEDN_NODE_OPTIMAL;
+    if (const char* f = getenv("PEDN_QUIET")) s->quiet = atoi(f) != 0;
     // 0 = by batch: two chains where the step is not a pure chain of latencies any more -- from 4096 envs, and from 1024 with per-env
     // scenarios (45_intersections: 2048 envs plain 24.8-25.2 -> 24.7-25.7 us per env step, randomised 27.5-27.9 -> 25.6-26.0;
     // 4096 envs 40.6 -> 35.9; profiles/r04_rl_chains.txt); PEDN_RL_CHAINS=1|2 forces
@@ -972,6 +991,12 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     s->h_slot_rec = rec;
     TRY(upload(s, rec.data(), rec.size(), &v.slot_rec));
     s->d_slot_rec = const_cast<SlotRec*>(v.slot_rec);
+    v.quiet_npos = (int32_t)rec.size();
+    if (s->quiet) {   // [2][slot positions][RS / 64][own | inbox]: melbourne x 1024 ~ 0.3 MB
+      const size_t nq = (size_t)2 * rec.size() * (size_t)(v.RS / 64) * 2;
+      TRY(dalloc(s, nq, &s->d_quiet));
+      HIP_TRY(s, hipMemset(s->d_quiet, 0, nq * sizeof(uint32_t)));
+    }
   }
   // ---- dynamic state
   {
@@ -1070,6 +1095,7 @@ int pedn_reset(pedn_sim* s) {
   s->tp_ready = -1;
   s->last_t = -1;
   s->link_pending = -1;   // discarded: the state it would complete is being cleared
+  no_quiet(s);
   return reset_state(s);
 }
 
@@ -1080,6 +1106,7 @@ int pedn_reset_lazy(pedn_sim* s) {
   s->tp_ready = -1;
   s->last_t = -1;
   s->link_pending = -1;
+  no_quiet(s);
   return reset_state_lazy(s);
 }
 
@@ -1414,6 +1441,7 @@ static inline bool last_chain(const pedn_sim* s, int half) { return half < 0 || 
 // Owner-wave plan: the link update of the last step launched is still to be done (link_pending); do it now.
 static void flush_links(pedn_sim* s, int half, hipEvent_t* ev) {
   if (s->link_pending < 0) return;
+  no_quiet(s);
   hipStream_t stream;
   const DevView v = view_of(s, half, &stream);
   launch_link_update(s, v, stream, s->link_pending, ev, 4);
@@ -1439,6 +1467,7 @@ static inline void join_forked(pedn_sim* s) {
 }
 static inline void pending_links_first(pedn_sim* s) {
   s->touched = 1;
+  no_quiet(s);   // whatever comes next may change a history row or break the chain of node_kernel<LU> launches
   join_forked(s);
   if (s->link_pending >= 0) flush_links(s, -1, nullptr);
 }
@@ -1492,6 +1521,11 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   if (flush_now) flush_links(s, half, nullptr);
   DevView vn = v;                 // node_kernel's view: with the action rows when it applies the gater actions itself
   vn.rl_actions = fold_actions;
+  // quiet corridors: every node_kernel<LU> launch (not the single-launch plan's <LU, TF>) stores the words of step t; it uses those of
+  // t - 1 when the launch of t - 1 was one of them and nothing has touched the history since (quiet_valid)
+  const bool quiet = lu && !inl && s->quiet;
+  vn.quiet = quiet ? s->d_quiet : nullptr;
+  vn.quiet_use = quiet && s->quiet_valid == t - 1;
   const unsigned rgroups = (unsigned)(v.subRS / 64);
   // the turning fractions of t + 1 ride in the launch behind node_kernel(t) -- except behind the last step of the horizon, where
   // pair_pod / turn_tab have no row T + 1 to read (they hold T + 1 rows, 0..T) and nothing would consume the result
@@ -1516,7 +1550,10 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   // link update: one replica per lane as a launch of its own and with per-replica parameters, two inside link_turn_kernel (link_body)
   const bool one_r = v.pr || (!fused && !obs_fused);
   const unsigned nlb = lazy ? 0u : link_blocks(v, one_r);   // lazy: no link-update workgroups in this step's second launch
-  if (last_chain(s, half)) s->link_pending = lazy ? t : -1;
+  if (last_chain(s, half)) {
+    s->link_pending = lazy ? t : -1;
+    s->quiet_valid = quiet ? t : -1;
+  }
   s->second_launch = 1;
   if (fused || obs_fused) {
     const unsigned ntb = fused ? (unsigned)((v.n_trow + 3) / 4) * rgroups : 0u;
@@ -1677,6 +1714,7 @@ int pedn_plan_info(pedn_sim* s, int32_t* info, int32_t n) {
   info[2] = s->stream_probe_attempts;
   info[3] = (int32_t)(s->stream_probe_ms * 1000.0f + 0.5f);
   if (n >= 5) info[4] = s->packed_by;   // bins of node_kernel packed by 0 degree, 1 the static load estimate, 2 measured node cost
+  if (n >= 6) info[5] = s->quiet && info[1];   // the owner-wave launches keep and use the quiet-corridor words (PEDN_QUIET)
   return PEDN_OK;
 }
 
@@ -2319,6 +2357,7 @@ int pedn_rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t 
 static int clock_end(pedn_sim* s) {
   if (!s->clocked) return PEDN_OK;
   s->clocked = false;
+  no_quiet(s);
   // the clocked steps may sit on a caller's stream (or in a graph replayed on one): everything on the device first
   HIP_TRY(s, hipDeviceSynchronize());
   int32_t h[4] = {0, 0, 0, 0};

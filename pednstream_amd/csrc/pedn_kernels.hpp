@@ -755,6 +755,17 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
   const SlotRec& W = v.slot_rec[(size_t)by * 8 + wave];  // wave-uniform: scalar loads
   const int node = W.node, slot = W.slot, base = W.base, m = W.m;
   const bool active = node >= 0;
+  // quiet corridors (QU; DevView.quiet): the two words of step t - 1 for this slot -- addressed without the record, so they are
+  // loaded in the record's burst.  Both set: in every replica of the group, inflow / outflow [t-1] of both directions, cumulative_inflow /
+  // cumulative_outflow [t-1] of both directions, num_pedestrians[t-2] of both directions and sending_flow[t-2] of the incoming link are
+  // +0.0, and no separator or zero shock-wave look-back is involved.
+  constexpr bool QU = LU && !TF && !CLK;
+  const size_t qgroup = (size_t)(RS >> 6), qslot = (size_t)by * 8 + wave, qrg = (size_t)(r0 >> 6);
+  bool quiet = false;
+  if (QU && v.quiet != nullptr && v.quiet_use) {
+    const uint2 qw = *reinterpret_cast<const uint2*>(v.quiet + ((((size_t)(tp & 1) * (size_t)v.quiet_npos + qslot) * qgroup + qrg) << 1));
+    quiet = qw.x == (uint32_t)t && qw.y == (uint32_t)t;   // (launch t - 1 stores t)
+  }
   PH(1, lane + node);
   if (CLK) {
     // a clocked launch replayed beyond the horizon: uniform over the grid.  (node >= -1 always: the term only makes the guard depend on
@@ -764,6 +775,7 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     if (bx == 0 && by == 0 && threadIdx.x == 0) v.clock[1] = t;   // the step of the launch behind this one (see node_clock)
   }
   uint32_t fl = 0;
+  bool qz = false;   // QU: this lane's share of the quiet word of step t (virtual pairs: never quiet)
   double s_i = 0.0, r_i = 0.0, qo = 0.0, qi = 0.0, co_prev = 0.0, ci_prev = 0.0;
   int lin = 0, lout = 0, kind = 0;
   double tfr[MD - 1];
@@ -807,7 +819,9 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     double lu_ia = 0.0, lu_oa = 0.0, lu_ib = 0.0, lu_ob = 0.0, lu_npa = 0.0, lu_npb = 0.0;
     float lu_pa = 0.0f, lu_pb = 0.0f, lu_rs = 0.0f, lu_old = 0.0f;
     const bool lu_win = tp >= v.W;
+    uint32_t qfl = 0;   // QU: the replica's error flags as the launches before this one left them (a 4 KB array: cache hits)
     auto load_batch = [&]() {
+      if (QU) qfl = v.flags[r];
       Pin = lane_params<PR>(v, W.Pin, lin, r);
       Pout = lane_params<PR>(v, W.Pout, lout, r);
       early = tp < Pin.fft;  // link.py:267-269: sending flow is 0 until the first pedestrians can arrive
@@ -815,31 +829,46 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
       tm1 = wrap_idx(tp - 1, v.T1, flw);
       fl |= flw;
       t_sw = tp + 1 - Pout.tau_sw > 0 ? tp + 1 - Pout.tau_sw : 0;
-      if (!LU) {
-        x.n_in = rowp(v.f32[G_N], R32(G_N, tp), lin, L, RS, r0)[lane];
-        x.n_out = rowp(v.f32[G_N], R32(G_N, tp), lout, L, RS, r0)[lane];
-        // density[t'] of a plain link is num_pedestrians[t'] / float32(length * width) (link.py:136): recomputed from n_in with the
-        // link update's own division instead of being read back; a separator's density depends on its width at that time
-        x.k_in = Pin.sep ? rowp(v.f32[G_K], R32(G_K, tp), lin, L, RS, r0)[lane] : 0.0f;
-        x.att_in = rowp(v.f32[G_ATT], R32(G_ATT, tp), lin, L, RS, r0)[lane];
-      } else {
-        // inputs of the link update of step t' for the corridor (lin, lout): all of them written by the launches before this one
-        lu_ia = rowp(v.f64[F_IN], R64(F_IN, tp), lin, Lall, RS, r0)[lane];
-        lu_oa = rowp(v.f64[F_OUT], R64(F_OUT, tp), lin, Lall, RS, r0)[lane];
-        lu_ib = rowp(v.f64[F_IN], R64(F_IN, tp), lout, Lall, RS, r0)[lane];
-        lu_ob = rowp(v.f64[F_OUT], R64(F_OUT, tp), lout, Lall, RS, r0)[lane];
-        lu_pa = rowp(v.f32[G_N], R32(G_N, tp - 1), lin, L, RS, r0)[lane];
-        lu_pb = rowp(v.f32[G_N], R32(G_N, tp - 1), lout, L, RS, r0)[lane];
+      if (QU && quiet) {
+        // a quiet corridor: only what the zero state does not determine.  The inputs of the link update, cumulative_outflow[t'] of the
+        // incoming link, cumulative_inflow[t'] of the outgoing one, the shock-wave look-back (its row t_sw <= t' -- the producer saw
+        // tau_sw >= 1 in every lane -- and the cumulative counts of a replica without a negative flow never decrease: see the quiet
+        // word) and sending_flow[t'-1] are +0.0; the code below runs unchanged on them.  (receiving_flow, the running sum and the travel
+        // times are not zero on an empty corridor.)
         lu_rs = v.rsum[(size_t)lin * RS + r];
         lu_old = lu_win ? rowp(v.f32[G_TT], R32(G_TT, tp - v.W), lin, L, RS, r0)[lane] : 0.0f;
-        if (Pin.sep) lu_npa = v.sepnp[(size_t)lin * RS + r];
-        if (Pout.sep) lu_npb = v.sepnp[(size_t)lout * RS + r];
+        x.co_in = 0.0;
+        x.s_prev = 0.0;
+        x.co_sw = 0.0;
+        x.ci_out = 0.0;
+        x.r_prev = rowp(v.f64[F_R], R64(F_R, tm1), lout, L, RS, r0)[lane];
+      } else {
+        if (!LU) {
+          x.n_in = rowp(v.f32[G_N], R32(G_N, tp), lin, L, RS, r0)[lane];
+          x.n_out = rowp(v.f32[G_N], R32(G_N, tp), lout, L, RS, r0)[lane];
+          // density[t'] of a plain link is num_pedestrians[t'] / float32(length * width) (link.py:136): recomputed from n_in with the
+          // link update's own division instead of being read back; a separator's density depends on its width at that time
+          x.k_in = Pin.sep ? rowp(v.f32[G_K], R32(G_K, tp), lin, L, RS, r0)[lane] : 0.0f;
+          x.att_in = rowp(v.f32[G_ATT], R32(G_ATT, tp), lin, L, RS, r0)[lane];
+        } else {
+          // inputs of the link update of step t' for the corridor (lin, lout): all of them written by the launches before this one
+          lu_ia = rowp(v.f64[F_IN], R64(F_IN, tp), lin, Lall, RS, r0)[lane];
+          lu_oa = rowp(v.f64[F_OUT], R64(F_OUT, tp), lin, Lall, RS, r0)[lane];
+          lu_ib = rowp(v.f64[F_IN], R64(F_IN, tp), lout, Lall, RS, r0)[lane];
+          lu_ob = rowp(v.f64[F_OUT], R64(F_OUT, tp), lout, Lall, RS, r0)[lane];
+          lu_pa = rowp(v.f32[G_N], R32(G_N, tp - 1), lin, L, RS, r0)[lane];
+          lu_pb = rowp(v.f32[G_N], R32(G_N, tp - 1), lout, L, RS, r0)[lane];
+          lu_rs = v.rsum[(size_t)lin * RS + r];
+          lu_old = lu_win ? rowp(v.f32[G_TT], R32(G_TT, tp - v.W), lin, L, RS, r0)[lane] : 0.0f;
+          if (Pin.sep) lu_npa = v.sepnp[(size_t)lin * RS + r];
+          if (Pout.sep) lu_npb = v.sepnp[(size_t)lout * RS + r];
+        }
+        x.co_in = rowp(v.f64[F_CO], R64(F_CO, tp), lin, Lall, RS, r0)[lane];
+        x.s_prev = rowp(v.f64[F_S], R64(F_S, tm1), lin, L, RS, r0)[lane];
+        x.co_sw = rowp(v.f64[F_CO], R64(F_CO, t_sw), lout, Lall, RS, r0)[lane];
+        x.ci_out = rowp(v.f64[F_CI], R64(F_CI, tp), lout, Lall, RS, r0)[lane];
+        x.r_prev = rowp(v.f64[F_R], R64(F_R, tm1), lout, L, RS, r0)[lane];
       }
-      x.co_in = rowp(v.f64[F_CO], R64(F_CO, tp), lin, Lall, RS, r0)[lane];
-      x.s_prev = rowp(v.f64[F_S], R64(F_S, tm1), lin, L, RS, r0)[lane];
-      x.co_sw = rowp(v.f64[F_CO], R64(F_CO, t_sw), lout, Lall, RS, r0)[lane];
-      x.ci_out = rowp(v.f64[F_CI], R64(F_CI, tp), lout, Lall, RS, r0)[lane];
-      x.r_prev = rowp(v.f64[F_R], R64(F_R, tm1), lout, L, RS, r0)[lane];
       const double fu = v.front_u[lin], bu = v.back_u[lout];
       x.front_in = fu == fu ? fu : v.front[(size_t)lin * RS + r];
       x.back_out = bu == bu ? bu : v.back[(size_t)lout * RS + r];
@@ -919,6 +948,13 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
         const double go = Pout.sep ? x.sepw_out : lu_gate;
         if (go != Pout.width || v.hist) rowp(v.f64[F_GATE], R64(F_GATE, tp), lout, L, RS, r0)[lane] = go;
         x.n_in = na; x.n_out = nb; x.k_in = ka; x.att_in = so.att;
+        // quiet word of this step, part 1 (part 2 below the node's flows): num_pedestrians[t'] of the incoming link, the shock-wave
+        // look-back of at least one step that the next launch's quiet batch assumes, never a separator on either side, and no negative
+        // flow in this replica so far this episode.  A cumulative count falls only by a negative flow (a one-to-one node adds
+        // min(s, r) unclamped), and every negative flow raises PEDN_F_NEG_FLOW / PEDN_F_NEG_SENDING in the replica's sticky flags
+        // (cleared by the resets only): without them, +0.0 at row t means +0.0 at every earlier look-back row of the corridor
+        if (QU) qz = !Pin.sep && !Pout.sep && Pout.tau_sw >= 1 && __float_as_int(na) == 0 &&
+                     (qfl & (PEDN_F_NEG_FLOW | PEDN_F_NEG_SENDING)) == 0;
       }
       if (!LU && !Pin.sep) x.k_in = x.n_in / Pin.area32;
       co_prev = x.co_in;   // cumulative_outflow[t-1] of the incoming link, reused by update_links below
@@ -929,7 +965,9 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
       int idx_s = tp + 1 - __float2int_rn(x.att_in / (float)v.dt);  // link.py:260,274
       if (idx_s < 0) idx_s = 0;
       if (idx_s > tp + 1) idx_s = tp + 1;   // a zero / negative / garbage avg_travel_time must not take the load past the rows written so far
-      double ci_look = v.f64[F_CI][at(R64(F_CI, idx_s), lin, Lall, RS, r)];
+      // (a quiet corridor: +0.0 at every row <= t' -- a look-back of 0 steps, idx_s = t' + 1, is loaded as by the full batch)
+      double ci_look = 0.0;
+      if (!(QU && quiet) || idx_s > tp) ci_look = v.f64[F_CI][at(R64(F_CI, idx_s), lin, Lall, RS, r)];
       // (lazy reset: a zero look-back -- the PEDN_F_SAME_STEP case -- reads the row of THIS step, which an ordinary reset left at 0)
       ci_look = idx_s > vhi ? 0.0 : ci_look;
       const double rp = recv_reverse_peds(v, Pout, lout, tp, r, x, fl);
@@ -1029,11 +1067,25 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     // Node.update_links (node.py:146-162; link.py:19-25)
     double* const p_out = rowp(v.f64[F_OUT], R64(F_OUT, t), lin, Lall, RS, r0) + lane;
     double* const p_in = rowp(v.f64[F_IN], R64(F_IN, t), lout, Lall, RS, r0) + lane;
-    rowp(v.f64[F_CO], R64(F_CO, t), lin, Lall, RS, r0)[lane] = co_prev + qo;
-    rowp(v.f64[F_CI], R64(F_CI, t), lout, Lall, RS, r0)[lane] = ci_prev + qi;
+    const double co_t = co_prev + qo, ci_t = ci_prev + qi;
+    rowp(v.f64[F_CO], R64(F_CO, t), lin, Lall, RS, r0)[lane] = co_t;
+    rowp(v.f64[F_CI], R64(F_CI, t), lout, Lall, RS, r0)[lane] = ci_t;
     if (fl) atomicOr(&v.flags[r], fl);
     *p_out = qo;
     *p_in = qi;
+    if (QU && v.quiet != nullptr) {
+      // quiet word of step t, part 2: sending_flow[t'] and outflow / cumulative_outflow [t] of the incoming link, inflow /
+      // cumulative_inflow [t] of the outgoing one are +0.0 in every lane, and this step raised no negative flow either.  Into this
+      // slot's own word and the mirror's inbox: launch t + 1 of each end reads both
+      qz = qz && (fl & (PEDN_F_NEG_FLOW | PEDN_F_NEG_SENDING)) == 0 && __double_as_longlong(s_i) == 0 && __double_as_longlong(qo) == 0 &&
+           __double_as_longlong(qi) == 0 && __double_as_longlong(co_t) == 0 && __double_as_longlong(ci_t) == 0;
+      const uint32_t word = __all(qz) ? (uint32_t)t + 1u : 0u;
+      if (lane == 0) {
+        uint32_t* const qw = v.quiet + (size_t)(t & 1) * (size_t)v.quiet_npos * qgroup * 2;
+        qw[(qslot * qgroup + qrg) * 2] = word;
+        if (W.mirror >= 0) qw[((size_t)W.mirror * qgroup + qrg) * 2 + 1] = word;
+      }
+    }
   }
 #ifdef PEDN_PHASE_PROFILE
   PH(9, qo + qi);

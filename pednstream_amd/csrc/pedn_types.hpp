@@ -39,7 +39,9 @@ struct SlotRec {  // one wave of node_kernel: a (node, slot) with everything sta
   // act: action slot of the batched RL step that sets this slot's gate (back gate of lout = front gate of lin), -1 none
   // lp: index of the node among those that solve the node LP (assign_flows_type 'optimal'), on the node's slot 0, else -1
   // trow: the slot's row record in trow_words when the row's turning fractions are computed on the device (dyn == 1), else -1
-  int32_t node, slot, base, m, kind, dyn, lin, lout, turn0, demand_row, act, lp, trow, pad1;
+  // mirror: position (block * 8 + wave) of the slot at the corridor's other end -- the one whose incoming link is this slot's
+  // outgoing link -- for the quiet-corridor words (DevView.quiet); -1 for a virtual pair
+  int32_t node, slot, base, m, kind, dyn, lin, lout, turn0, demand_row, act, lp, trow, mirror;
   LinkP Pin, Pout;  // parameters of the incoming / outgoing link of the slot (unused for a virtual pair)
 };
 
@@ -127,4 +129,11 @@ struct DevView {
   double* lp_ws;
   int32_t* lp_basis;
   size_t lp_stride, lp_bstride;
+  // Quiet corridors (owner-wave plan, node_kernel<LU>; PEDN_QUIET): words [2][quiet_npos][RS / 64][2] -- [step & 1][slot position
+  // (block * 8 + wave)][replica group][own | inbox].  Launch t stores t + 1 into its own word and into its mirror's inbox word when,
+  // in all 64 replicas, everything it wrote for its end of the corridor is +0.0, else 0 (see node_step).  quiet_use: the host vouches
+  // that launch t - 1 on this chain was such a launch and nothing has changed a history row since (launch_step); nullptr: neither
+  // loaded nor stored.
+  uint32_t* quiet;
+  int32_t quiet_use, quiet_npos;
 };
