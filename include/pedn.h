@@ -262,7 +262,12 @@ int pedn_set_streams(pedn_sim* sim, int32_t n);
  * the probe's two concurrent 300 us kernels on the pair kept (~300: they overlap, ~600: they do not); n = entries of info (>= 4);
  * with n >= 5: info[4] = how nodes were packed into the node kernel's workgroups: 0 by degree, 1 by the static load estimate, 2 by
  * the measured cost pedn_model_desc.node_cost; with n >= 6: info[5] = 1 when those one-launch steps skip the loads of corridors that were
- * empty in all 64 replicas of a group at the step before (quiet corridors, PEDN_QUIET=0|1; results are the same either way). */
+ * empty in all 64 replicas of a group at the step before (quiet corridors, PEDN_QUIET=0|1; results are the same either way); with
+ * n >= 7: info[6] = 1 when the node kernels skip the stores of +0.0 into rows of inflow / outflow / cumulative_inflow /
+ * cumulative_outflow / num_pedestrians / density that have held +0.0 since the last pedn_reset (zero elision, PEDN_ZERO_ELIDE=0|1,
+ * full-record mode only; results are the same either way; pedn_device_ptr on one of those fields, and the clocked steps, turn it
+ * off until the next pedn_reset); with n >= 8: info[7] = node-kernel launches that could skip such stores since the last reset of
+ * either kind. */
 int pedn_plan_info(pedn_sim* sim, int32_t* info, int32_t n);
 
 /* reset all histories and dynamic state to t = 0 (widths, turning fractions and demand are kept) */

@@ -62,6 +62,15 @@ struct pedn_sim {
   int quiet = 0;
   int quiet_valid = -1;
   uint32_t* d_quiet = nullptr;
+  // Zero elision (DevView.zg64 / zg32; PEDN_ZERO_ELIDE=0|1, default on): zhw64 = the highest row of inflow / outflow / cumulative_inflow /
+  // cumulative_outflow, zhw32 = of num_pedestrians / density, that may hold anything but +0.0 -- -1 after a full reset (which leaves every
+  // row at +0.0), kept by the lazy reset (the old episode's rows stay), INT_MAX when something the host does not follow may write them
+  // (a zero-copy pointer, the clocked steps) until the next full reset.  A launch that writes row x of a group gets the gate iff
+  // x > the group's mark; the mark is raised to x once the step is enqueued (both chains of a step decide from the marks before it).
+  // Only zeros are ever written below the marks' back (clear_rows, catch_up), so they need not raise them.
+  int zero_elide = 1;
+  int zhw64 = 0x7fffffff, zhw32 = 0x7fffffff;
+  int zgated = 0;   // node-kernel launches with a gate open since the last reset of either kind (pedn_plan_info info[7])
   int fuse_obs = 1;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
   // (The link update as a launch of its own runs one replica per lane -- link_kernel_1r: 42-47 VGPRs, 8 waves per SIMD; melbourne x 1024
   // 12.3-12.6 against 12.7-13.1 us with two replicas per lane, profiles/r03_link_kernel_variants.txt; inside link_turn_kernel, whose
@@ -127,6 +136,10 @@ struct pedn_sim {
 
 // the quiet words of the last step may not be used by the next launch (pedn_sim.quiet_valid)
 static inline void no_quiet(pedn_sim* s) { s->quiet_valid = -1; }
+
+// zero elision: may a launch that writes row `row` of a group whose mark is `hw` skip its +0.0 stores (pedn_sim.zhw64 / zhw32)?
+// (recent-history mode: ring rows are reused, never)
+static inline int32_t zero_gate(const pedn_sim* s, int hw, int row) { return s->zero_elide && !s->v.hist && row > hw ? 1 : 0; }
 
 static int fail(pedn_sim* s, int code, const std::string& msg) {
   g_last_error = msg;
@@ -294,6 +307,8 @@ static int reset_state(pedn_sim* s) {
   DevView& v = s->v;
   HIP_TRY(s, hipMemsetAsync(v.flags, 0, (size_t)v.RS * sizeof(uint32_t), s->stream));
   s->valid_hi = v.valid_hi = 0x7fffffff;
+  s->zhw64 = s->zhw32 = -1;   // every row of the six fields is +0.0 once clear_rows has run
+  s->zgated = 0;
   return clear_rows(s, 0, v.T1, 1);
 }
 
@@ -307,6 +322,7 @@ static int reset_state_lazy(pedn_sim* s) {
   int rc;
   if ((rc = clear_rows(s, 0, 1, 1)) || (rc = clear_rows(s, 1, std::min(v.W, v.T1), 2)) || (rc = clear_rows(s, 1, v.T1, 4))) return rc;
   s->valid_hi = v.valid_hi = 0;
+  s->zgated = 0;   // (the zero-elision marks stay: the rows above row 0 still hold the old episode's values)
   return PEDN_OK;
 }
 
@@ -971,6 +987,8 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     // quiet corridors: the owner-wave launches skip the loads of corridors that are empty in all 64 replicas of a group (node_step)
     s->quiet = s->link_owner && m->node_model != PEDN_NODE_OPTIMAL;
     if (const char* f = getenv("PEDN_QUIET")) s->quiet = atoi(f) != 0;
+    // zero elision: the node kernels skip +0.0 stores into rows that hold +0.0 since the last full reset (zero_gate)
+    if (const char* f = getenv("PEDN_ZERO_ELIDE")) s->zero_elide = atoi(f) != 0;
     // 0 = by batch: two chains where the step is not a pure chain of latencies any more -- from 4096 envs, and from 1024 with per-env
     // scenarios (45_intersections: 2048 envs plain 24.8-25.2 -> 24.7-25.7 us per env step, randomised 27.5-27.9 -> 25.6-26.0;
     // 4096 envs 40.6 -> 35.9; profiles/r04_rl_chains.txt); PEDN_RL_CHAINS=1|2 forces
@@ -1445,7 +1463,10 @@ static void flush_links(pedn_sim* s, int half, hipEvent_t* ev) {
   hipStream_t stream;
   const DevView v = view_of(s, half, &stream);
   launch_link_update(s, v, stream, s->link_pending, ev, 4);
-  if (last_chain(s, half)) s->link_pending = -1;
+  if (last_chain(s, half)) {
+    s->zhw32 = std::max(s->zhw32, s->link_pending);   // (zero elision) num_pedestrians / density of that row written
+    s->link_pending = -1;
+  }
 }
 
 // One step = node_kernel(t), then ONE launch with the link update of t and -- where they apply -- the turn probabilities of
@@ -1508,6 +1529,9 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   }
   hipStream_t stream;
   DevView v = view_of(s, half, &stream);
+  // zero elision: the marks as they were before this step (a flush below raises zhw32 first, but then this node kernel is not the
+  // LU one and writes no row of num_pedestrians / density); both chains of a step decide alike, the marks are raised by the last one
+  const int zhw64 = s->zhw64, zhw32 = s->zhw32;
   lazy = lazy && !s->node_lp && v.n_pairs_corr > 0;
   // a pending link update is flushed when this is not the step it waits for, or when this step starts with the stand-alone turning
   // fractions (they read num_pedestrians[t - 1] as stored)
@@ -1526,6 +1550,11 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   const bool quiet = lu && !inl && s->quiet;
   vn.quiet = quiet ? s->d_quiet : nullptr;
   vn.quiet_use = quiet && s->quiet_valid == t - 1;
+  // zero elision: node_kernel(t) writes row t of the flows and cumulative counts, node_kernel<LU>(t) also row t - 1 of num_pedestrians /
+  // density (the link update behind an ordinary node kernel writes row t of those, ungated)
+  vn.zg64 = zero_gate(s, zhw64, t);
+  vn.zg32 = lu ? zero_gate(s, zhw32, t - 1) : 0;
+  if (vn.zg64 || vn.zg32) ++s->zgated;
   const unsigned rgroups = (unsigned)(v.subRS / 64);
   // the turning fractions of t + 1 ride in the launch behind node_kernel(t) -- except behind the last step of the horizon, where
   // pair_pod / turn_tab have no row T + 1 to read (they hold T + 1 rows, 0..T) and nothing would consume the result
@@ -1553,6 +1582,9 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   if (last_chain(s, half)) {
     s->link_pending = lazy ? t : -1;
     s->quiet_valid = quiet ? t : -1;
+    s->zhw64 = std::max(s->zhw64, t);
+    if (lu) s->zhw32 = std::max(s->zhw32, t - 1);
+    if (nlb > 0) s->zhw32 = std::max(s->zhw32, t);   // the link update of t below
   }
   s->second_launch = 1;
   if (fused || obs_fused) {
@@ -1715,6 +1747,8 @@ int pedn_plan_info(pedn_sim* s, int32_t* info, int32_t n) {
   info[3] = (int32_t)(s->stream_probe_ms * 1000.0f + 0.5f);
   if (n >= 5) info[4] = s->packed_by;   // bins of node_kernel packed by 0 degree, 1 the static load estimate, 2 measured node cost
   if (n >= 6) info[5] = s->quiet && info[1];   // the owner-wave launches keep and use the quiet-corridor words (PEDN_QUIET)
+  if (n >= 7) info[6] = s->zero_elide && !s->v.hist;   // the node kernels may skip +0.0 stores into clean rows (PEDN_ZERO_ELIDE)
+  if (n >= 8) info[7] = s->zgated;   // ... and this many node-kernel launches had a gate open since the last reset
   return PEDN_OK;
 }
 
@@ -1923,6 +1957,9 @@ int pedn_flush(pedn_sim* s) {
 void* pedn_device_ptr(pedn_sim* s, int32_t field, int64_t* columns, int64_t* replica_stride) {
   if (!s || field < 0 || field >= PEDN_N_FIELDS) return nullptr;
   if ((s->link_pending >= 0 || s->forked || s->clocked || s->valid_hi != 0x7fffffff) && pedn_flush(s) != PEDN_OK) return nullptr;
+  // zero elision: a zero-copy consumer may write any row of the field -- no gate on its group until the next full reset
+  if (field <= F_CO) s->zhw64 = 0x7fffffff;
+  if (field == 7 + G_N || field == 7 + G_K) s->zhw32 = 0x7fffffff;
   if (columns) *columns = field < 4 ? s->v.Lall : s->v.L;
   if (replica_stride) *replica_stride = s->v.RS;
   return field < 7 ? (void*)s->v.f64[field] : (void*)s->v.f32[field - 7];
@@ -2392,6 +2429,7 @@ int pedn_rl_clock_begin(pedn_sim* s, int32_t t) {
   HIP_TRY(s, hipGetLastError());
   s->clocked = true;
   s->clock_t0 = t;
+  s->zhw64 = s->zhw32 = 0x7fffffff;   // zero elision: the host does not see which rows the clocked steps write (until the next full reset)
   return PEDN_OK;
 }
 

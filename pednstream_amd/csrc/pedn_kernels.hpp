@@ -760,6 +760,8 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
   // cumulative_outflow [t-1] of both directions, num_pedestrians[t-2] of both directions and sending_flow[t-2] of the incoming link are
   // +0.0, and no separator or zero shock-wave look-back is involved.
   constexpr bool QU = LU && !TF && !CLK;
+  // zero elision (DevView.zg64 / zg32): not in the clocked step, whose step index the host does not see, nor in recent-history mode
+  constexpr bool ZE = !CLK && !HIST;
   const size_t qgroup = (size_t)(RS >> 6), qslot = (size_t)by * 8 + wave, qrg = (size_t)(r0 >> 6);
   bool quiet = false;
   if (QU && v.quiet != nullptr && v.quiet_use) {
@@ -936,9 +938,13 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
         float ka = na / Pin.area32, kb = nb / Pout.area32;
         if (Pin.sep) ka = lu_npa != 0.0 ? (float)((double)na / (Pin.length * x.sepw_in)) : na / (float)(Pin.length * x.sepw_in);
         if (Pout.sep) kb = lu_npb != 0.0 ? (float)((double)nb / (Pout.length * x.sepw_out)) : nb / (float)(Pout.length * x.sepw_out);
+        // zero elision (ZE, DevView.zg32): row t' of both fields holds +0.0 already -- one vote per pair, a -0.0 is still stored.
+        // (Stored ahead of the speed: with the vote behind it, 8 vector spills)
+        if (!(ZE && v.zg32 && __all((__float_as_int(na) | __float_as_int(ka)) == 0))) {
+          rowp(v.f32[G_N], R32(G_N, tp), lin, L, RS, r0)[lane] = na;
+          rowp(v.f32[G_K], R32(G_K, tp), lin, L, RS, r0)[lane] = ka;
+        }
         const SpeedOut so = speed_calc(v, Pin, lin, tp, r, ka, kb, lu_rs, lu_old, nz);
-        rowp(v.f32[G_N], R32(G_N, tp), lin, L, RS, r0)[lane] = na;
-        rowp(v.f32[G_K], R32(G_K, tp), lin, L, RS, r0)[lane] = ka;
         rowp(v.f32[G_V], R32(G_V, tp), lin, L, RS, r0)[lane] = so.spd;
         rowp(v.f32[G_TT], R32(G_TT, tp), lin, L, RS, r0)[lane] = so.tt;
         rowp(v.f32[G_LF], R32(G_LF, tp), lin, L, RS, r0)[lane] = so.lf;
@@ -1068,11 +1074,18 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     double* const p_out = rowp(v.f64[F_OUT], R64(F_OUT, t), lin, Lall, RS, r0) + lane;
     double* const p_in = rowp(v.f64[F_IN], R64(F_IN, t), lout, Lall, RS, r0) + lane;
     const double co_t = co_prev + qo, ci_t = ci_prev + qi;
-    rowp(v.f64[F_CO], R64(F_CO, t), lin, Lall, RS, r0)[lane] = co_t;
-    rowp(v.f64[F_CI], R64(F_CI, t), lout, Lall, RS, r0)[lane] = ci_t;
+    // zero elision (ZE, DevView.zg64): row t of the four fields holds +0.0 already, so a pair of rows whose values are +0.0 in all 64
+    // lanes is not stored -- decided per wave (a 512-byte row segment is written whole or not at all), by the bits (-0.0 is stored)
+    // (each vote right at its pair of stores: node_kernel lives on its last vector register, see node_kernel_waves)
     if (fl) atomicOr(&v.flags[r], fl);
-    *p_out = qo;
-    *p_in = qi;
+    if (!(ZE && v.zg64 && __all((__double_as_longlong(qo) | __double_as_longlong(co_t)) == 0))) {
+      rowp(v.f64[F_CO], R64(F_CO, t), lin, Lall, RS, r0)[lane] = co_t;
+      *p_out = qo;
+    }
+    if (!(ZE && v.zg64 && __all((__double_as_longlong(qi) | __double_as_longlong(ci_t)) == 0))) {
+      rowp(v.f64[F_CI], R64(F_CI, t), lout, Lall, RS, r0)[lane] = ci_t;
+      *p_in = qi;
+    }
     if (QU && v.quiet != nullptr) {
       // quiet word of step t, part 2: sending_flow[t'] and outflow / cumulative_outflow [t] of the incoming link, inflow /
       // cumulative_inflow [t] of the outgoing one are +0.0 in every lane, and this step raised no negative flow either.  Into this

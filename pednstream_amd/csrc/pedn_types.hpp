@@ -136,4 +136,9 @@ struct DevView {
   // loaded nor stored.
   uint32_t* quiet;
   int32_t quiet_use, quiet_npos;
+  // Zero elision (full-record mode; PEDN_ZERO_ELIDE): the host vouches that the row this launch writes of inflow / outflow /
+  // cumulative_inflow / cumulative_outflow (zg64: row t) and of num_pedestrians / density (zg32: row t - 1, node_kernel<LU>) holds +0.0
+  // -- not written since the last full reset but by zeros (pedn_sim.zhw64 / zhw32).  A wave then skips a pair of stores whose values
+  // are +0.0 in all 64 lanes (node_step).  0 in the engine's own view: set only in the copy a step launch carries.
+  int32_t zg64, zg32;
 };
