@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- link-updates/s of the network_loading hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one network_loading(t) over the whole replica batch of one GPU.  Workload at N = 1: the Melbourne network
@@ -15,9 +15,14 @@ value = links x replicas(all ranks) x K / wall-seconds (max over ranks) of the t
 HBM before the region starts.  The region: barrier + synchronize | clock starts | K steps | synchronize | clock stops | barrier;
 every rank times its own K steps to completion and the job's time is the MAX over ranks.
 
+A PLAIN run (the command above) does what its headline figure needs and nothing else: set-up, warm-up, the timed region,
+--dump-outputs if given, and the result line.  Everything else it can measure is behind --full (off by default); --no-live-traffic,
+--no-cpu-baseline and --no-extra trim a --full run.
+
 OUTPUT.  The LAST line of stdout is ONE compact JSON object (< 4 KB: numbers and short identifiers only -- compact_line(); the driver
-keeps an 8 KB tail of stdout and parses its last line); everything measured, with the prose that says how each figure was formed, is
-written to bench_full.json beside this script.  Both carry
+keeps an 8 KB tail of stdout and parses its last line).  A plain run's line carries the headline fields (metric, value, unit,
+ms_per_step, device_ms_per_step, higher_is_better, dtype, ...) and the config.  A --full run adds the blocks below to the line and
+writes everything measured, with the prose that says how each figure was formed, to bench_full.json beside this script:
   launch_plan  how pedn_run stepped (pedn_plan_info): chains of launches, whether the link update of step t is performed by the slot
                waves of step t + 1's node kernel (ONE launch per step), how the nodes were packed into workgroups
   roofline     dominant kernel (node_kernel).  `basis_kind` names the basis of `achieved` / `frac`: "moved" = memory-side bytes per
@@ -217,7 +222,7 @@ def live_traffic(workloads, history):
                 print(f"bench.py: PMC budget spent, no live passes for {network} x {replicas}", file=sys.stderr)
                 break
             cmd = [sys.executable, os.path.abspath(__file__), "--network", network, "--replicas", str(replicas), "--history", history,
-                   "--steps", "48", "--warmup", "20", "--no-cpu-baseline", "--no-extra"]
+                   "--steps", "48", "--warmup", "20", "--full", "--no-cpu-baseline", "--no-extra"]
             f, w = counters("FETCH_SIZE", f"pf_{network}_{replicas}", cmd), counters("WRITE_SIZE", f"pw_{network}_{replicas}", cmd)
             out = {"fetch_factor": fetch_factor, "write_factor": write_factor}
             for k in f:
@@ -491,7 +496,8 @@ def spawn_ranks(args, argv):
 
 
 def measure(args, network, dist, rank, local_rank, world, demand_scale=1.0):
-    """Warm-up, the timed region, per-kernel durations; returns (fields of the JSON line, net, engine-side context).
+    """Warm-up, the timed region and, with --full, per-kernel durations and the roofline; returns (fields of the JSON line, net,
+    engine-side context).
     demand_scale: the origin demand of every replica times this (12: the congested regime of the goldens melbourne_heavy_*)."""
     from pednstream_amd import NetworkEnvGenerator
     from pednstream_amd.ensemble import shard
@@ -569,6 +575,19 @@ def measure(args, network, dist, rank, local_rank, world, demand_scale=1.0):
         raise SystemExit(f"model error flags set: {rc}")
     if args.dump_outputs:
         dump_outputs(e, state["t"] - 1, args.dump_outputs, offset)
+    out = {
+        "metric": "link-updates/sec (links x replicas x steps/sec)", "value": L * R * world * args.steps / wall, "unit": "link-updates/s",
+        "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong" if args.total_replicas else "weak", "vs_baseline": None, "dtype": "f64+f32", "data": "synthetic",
+        "config": {"workload": f"{network} network ({L} links, {len(net.nodes)} nodes, T={T}) x {R} replicas per GPU, "
+                               f"{'full-record' if args.history == 'full' else 'recent-history'} mode, per-replica Poisson demand and Philox keys",
+                   "network": network, "history": "full-record" if args.history == "full" else "recent",
+                   "replicas_per_gpu": R, "replicas_total": R * world, "links": L,
+                   "parallelism": f"replica-sharded x{world}, no step-path collective"},
+        "device_ms_per_step": dev_ms / args.steps,
+    }
+    if not args.full:
+        return out, net, origins
 
     # per-launch durations (the dispatches' own start / stop timestamps) under the SAME launch plan as the timed region, continuing
     # the same simulation.  chains = 2: run() launched the two halves of the replicas as two chains on two streams; a launch then
@@ -625,7 +644,6 @@ def measure(args, network, dist, rank, local_rank, world, demand_scale=1.0):
                     "unit": "link-updates/s", "ms_per_step": wall2 / args.steps * 1e3, "device_ms_per_step": dev2 / args.steps,
                     "whole_step_frac_wall": BYTES_PER_LINK_UPDATE * L * R / (wall2 / args.steps) / 1e9 / HBM_PEAK_GBS}
 
-    total_lu = L * R * world * args.steps
     node_bytes = node_kernel_bytes * L * R // chains          # one launch covers R / chains replicas
     step_bytes = BYTES_PER_LINK_UPDATE * L * R
     # time the machine spends on one step of all replicas: one chain -> the sum of its launches (gaps excluded); two chains ->
@@ -659,16 +677,7 @@ def measure(args, network, dist, rank, local_rank, world, demand_scale=1.0):
     working_set = None if traffic is None or traffic2 is None else (traffic + traffic2) * chains
     mdl = e.model
     n_dyn_turns = int(np.diff(mdl["node_turn_ptr"])[np.asarray(mdl["node_dyn"]) > 0].sum())     # +8 B each per replica
-    out = {
-        "metric": "link-updates/sec (links x replicas x steps/sec)", "value": total_lu / wall, "unit": "link-updates/s",
-        "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong" if args.total_replicas else "weak", "vs_baseline": None, "dtype": "f64+f32", "data": "synthetic",
-        "config": {"workload": f"{network} network ({L} links, {len(net.nodes)} nodes, T={T}) x {R} replicas per GPU, "
-                               f"{'full-record' if args.history == 'full' else 'recent-history'} mode, per-replica Poisson demand and Philox keys",
-                   "network": network, "history": "full-record" if args.history == "full" else "recent",
-                   "replicas_per_gpu": R, "replicas_total": R * world, "links": L,
-                   "parallelism": f"replica-sharded x{world}, no step-path collective"},
-        "device_ms_per_step": dev_ms / args.steps,
+    out.update({
         "roofline": {"bound": "hbm",
                      "kernel": ("node_kernel<LU>: sending / receiving flows, node model, cumulative counts AND the link update of the previous step "
                                 "(one launch per step)" if owner else "node_kernel: sending / receiving flows, node model, cumulative counts"),
@@ -710,7 +719,7 @@ def measure(args, network, dist, rank, local_rank, world, demand_scale=1.0):
                      "whole_step_bytes_per_link_update": BYTES_PER_LINK_UPDATE,
                      "dynamic_turns": n_dyn_turns,
                      "whole_step_frac_incl_dynamic_turns": (step_bytes + 8 * n_dyn_turns * R) / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-    }
+    })
     if one_chain is not None:
         out["roofline"]["one_chain"] = one_chain
     if alt_plan is not None:
@@ -729,25 +738,27 @@ def _pick(d, keys):
     return {k: _sig(d[k]) for k in keys if isinstance(d, dict) and k in d and not isinstance(d[k], (dict, list))}
 
 
-def compact_line(out):
+def compact_line(out, full_file=None):
     """The line the driver parses: the LAST line of stdout, < 4 KB, numbers and short identifiers only.  Everything measured (every
-    extra with its own roofline block, the prose that says how each figure was formed) is written to bench_full.json beside this script."""
-    rf, cb = out["roofline"], out.get("cpu_baseline")
+    extra with its own roofline block, the prose that says how each figure was formed) is written to `full_file` (--full:
+    bench_full.json beside this script); a plain run's `out` has no roofline and the line only the headline fields and the config."""
+    rf, cb = out.get("roofline"), out.get("cpu_baseline")
     cfg = out["config"]
     line = {k: _sig(out[k]) for k in ("metric", "value", "unit", "n_gpus", "ranks_seen", "steps", "warmup", "ms_per_step", "device_ms_per_step",
                                       "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in out}
     line["config"] = {"workload": f"{cfg['network']} x {cfg['replicas_per_gpu']} replicas per GPU, {cfg['history']} histories",
                       "replicas_per_gpu": cfg["replicas_per_gpu"], "replicas_total": cfg["replicas_total"], "links": cfg["links"],
                       "parallelism": f"replicas x{out['n_gpus']}"}
-    r = _pick(rf, ("bound", "kernel_name", "achieved", "peak", "unit", "frac", "basis_kind", "traffic", "frac_algorithmic", "frac_counter",
-                   "frac_executed", "traffic_bytes_per_link_update", "algorithmic_bytes_per_link_update", "algorithmic_bytes_per_launch",
-                   "fits_infinity_cache", "concurrent_chains", "avg_launch_ms", "whole_step_frac", "whole_step_frac_counter"))
-    r["kernel"] = r.pop("kernel_name")
-    pl = rf.get("launch_plan") or {}
-    r["launch_plan"] = {k: pl[k] for k in ("chains", "link_update_by_next_node_kernel", "single_launch_step") if k in pl}
-    if "one_chain" in rf:
-        r["one_chain"] = _pick(rf["one_chain"], ("avg_launch_ms", "frac"))
-    line["roofline"] = r
+    if rf is not None:
+        r = _pick(rf, ("bound", "kernel_name", "achieved", "peak", "unit", "frac", "basis_kind", "traffic", "frac_algorithmic", "frac_counter",
+                       "frac_executed", "traffic_bytes_per_link_update", "algorithmic_bytes_per_link_update", "algorithmic_bytes_per_launch",
+                       "fits_infinity_cache", "concurrent_chains", "avg_launch_ms", "whole_step_frac", "whole_step_frac_counter"))
+        r["kernel"] = r.pop("kernel_name")
+        pl = rf.get("launch_plan") or {}
+        r["launch_plan"] = {k: pl[k] for k in ("chains", "link_update_by_next_node_kernel", "single_launch_step") if k in pl}
+        if "one_chain" in rf:
+            r["one_chain"] = _pick(rf["one_chain"], ("avg_launch_ms", "frac"))
+        line["roofline"] = r
     if cb is not None:
         c = _pick(cb, ("value", "unit", "cores", "kind", "sample_short", "cpu_model", "one_thread", "all_cores"))
         c["sample"] = c.pop("sample_short")
@@ -778,7 +789,8 @@ def compact_line(out):
                 if "roofline" in v:
                     e2[name].update(_pick(v["roofline"], ("whole_step_frac", "whole_step_frac_counter")))
         line["extra"] = e2
-    line["full"] = "bench_full.json"
+    if full_file:
+        line["full"] = full_file
     return line
 
 
@@ -789,9 +801,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--network", default="melbourne")
     ap.add_argument("--replicas", type=int, default=1024, help="replicas per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not run the rocprofv3 --pmc child passes; roofline.traffic then comes from profiles/")
-    ap.add_argument("--no-extra", action="store_true", help="skip the delft x 1024 (BASELINE config #3) measurement that rides along at N = 1")
+    ap.add_argument("--full", action="store_true", help="measure more than the headline figure: per-kernel durations and the roofline, at N = 1 "
+                    "also the rocprofv3 --pmc child passes, the CPU baseline and the extra configurations; everything goes to bench_full.json")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-live-traffic", action="store_true", help="with --full: do not run the rocprofv3 --pmc child passes; roofline.traffic "
+                    "then comes from profiles/")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the counter passes, the launch-plan diagnostics and the extra "
+                    "configurations that ride along at N = 1")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the "
                     "multi-rank path on one GPU)")
     ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank uses GPU 0")
@@ -816,7 +832,7 @@ def main():
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}")
         if args.gpus > 1:             # nothing has touched the GPU yet: the ranks run in a child, this process only relays its exit code
             raise SystemExit(spawn_ranks(args, sys.argv[1:]))
-        if args.gpus == 1 and not args.no_extra and not args.rl and not args.no_live_traffic:
+        if args.gpus == 1 and args.full and not args.no_extra and not args.rl and not args.no_live_traffic:
             headline = args.network == "melbourne" and args.replicas == 1024 and not args.total_replicas
             live_traffic([(args.network, args.total_replicas or args.replicas)] + ([("delft", 1024), ("melbourne", 4096)] if headline else []), args.history)
     rank = int(os.environ.get("RANK", "0"))
@@ -854,13 +870,13 @@ def main():
         rf["executed_basis"] = ("whole step: 212 B per link-update minus the bytes of paths this workload does not take (bench.py: executed_bytes; "
                                 "tallied by the oracle over the replicas cpu_baseline ran, whole episodes) over the step's device time")
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(flatten_network(net), net, origins, args.network)
             add_executed(out, out["cpu_baseline"])
     net.close()
     headline = args.network == "melbourne" and args.replicas == 1024 and not args.total_replicas
-    if rank == 0 and world == 1 and not args.no_extra and headline:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and headline:
         import copy
         keep = ("value", "unit", "ms_per_step", "device_ms_per_step", "steps", "warmup", "config", "roofline")
         out["extra"] = {}
@@ -926,15 +942,18 @@ def main():
 
         extra("config5_rl_45int_x2048", config5)
     if rank == 0:
-        # everything measured goes to a file beside the script; the LAST line of stdout is the compact headline object (< 4 KB)
-        try:
-            with open(os.path.join(ROOT, "bench_full.json"), "w") as f:
-                json.dump(out, f)
-        except OSError as exc:
-            print(f"bench.py: bench_full.json not written ({exc})", file=sys.stderr)
-        line = json.dumps(compact_line(out), separators=(",", ":"))
+        # --full: everything measured goes to a file beside the script; the LAST line of stdout is the compact headline object (< 4 KB)
+        full_file = None
+        if args.full:
+            full_file = "bench_full.json"
+            try:
+                with open(os.path.join(ROOT, full_file), "w") as f:
+                    json.dump(out, f)
+            except OSError as exc:
+                print(f"bench.py: bench_full.json not written ({exc})", file=sys.stderr)
+        line = json.dumps(compact_line(out, full_file), separators=(",", ":"))
         if len(line) >= 4096:                       # never let detail cost the line: drop the extras before anything else
-            slim = compact_line(out)
+            slim = compact_line(out, full_file)
             slim.pop("extra", None)
             line = json.dumps(slim, separators=(",", ":"))
         print(line, flush=True)

@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -17,7 +18,7 @@ def test_help_lists_the_contract_flags():
     out = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--replicas", "--total-replicas", "--network", "--rl", "--randomize", "--history",
-                 "--dump-outputs"):
+                 "--dump-outputs", "--full"):
         assert flag in out.stdout, flag
 
 
@@ -96,6 +97,22 @@ def test_compact_line_is_small_and_carries_the_contract_fields():
     assert all(len(json.dumps(v)) < 900 for v in d["extra"].values())
     # no prose anywhere
     assert "xxxx" not in line.replace(d["extra"]["broken"]["error"], "")
+
+
+def test_plain_line_carries_the_headline_only():
+    """A plain run (no --full) measures no roofline, CPU baseline or extras: its line is the headline fields and the config, the same
+    values a --full run prints for them, and names no bench_full.json."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    full = _full_object()
+    plain = {k: v for k, v in full.items() if k not in ("roofline", "cpu_baseline", "extra")}
+    line, full_line = bench.compact_line(plain), bench.compact_line(full, "bench_full.json")
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "ranks_seen", "steps", "warmup", "ms_per_step", "device_ms_per_step",
+                         "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"}
+    assert full_line["full"] == "bench_full.json" and "roofline" in full_line and "cpu_baseline" in full_line and "extra" in full_line
+    for k in line:
+        assert line[k] == full_line[k], k
 
 
 def test_dump_outputs_is_refused_where_it_is_not_supported(tmp_path):
@@ -189,3 +206,27 @@ def test_dump_outputs_repeat_and_match_the_oracle(tmp_path):
             row = t - 1 if name in ("sending_flow", "receiving_flow") else t
             assert np.array_equal(np.load(dirs[0] / (name + ".npy"))[i], o.field(name)[:, row]), (name, i)
         o.close()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full prints the headline line alone (no roofline, CPU baseline or extras, no
+    bench_full.json written) and spends little time outside its steps, set-up included."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    full = os.path.join(ROOT, "bench_full.json")
+    before = os.stat(full).st_mtime_ns if os.path.exists(full) else None
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                         capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "link-updates/sec (links x replicas x steps/sec)" and d["unit"] == "link-updates/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f64+f32" and d["steps"] == steps and d["warmup"] == warmup
+    assert abs(d["value"] - 938 * 1024 * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-3 * d["value"]
+    assert not {"roofline", "cpu_baseline", "extra", "full"} & set(d), sorted(d)
+    assert (os.stat(full).st_mtime_ns if os.path.exists(full) else None) == before
+    assert wall - (steps + warmup) * d["ms_per_step"] * 1e-3 < 30, wall

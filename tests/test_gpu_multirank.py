@@ -104,7 +104,7 @@ def test_bench_under_the_launcher_runs_the_rccl_branch_once():
 
     pytest.importorskip("torch")
     bench = os.path.join(ROOT, "bench.py")
-    short = ["--gpus", "1", "--steps", "60", "--warmup", "20", "--no-extra", "--no-cpu-baseline"]
+    short = ["--gpus", "1", "--steps", "60", "--warmup", "20", "--full", "--no-extra", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
@@ -145,7 +145,7 @@ def test_bench_two_ranks_rehearsal_prints_one_compact_line():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     for extra, per_gpu, scaling in ((["--replicas", "256"], 256, "weak"), (["--total-replicas", "512"], 256, "strong")):
-        out = subprocess.run([sys.executable, bench, "--gpus", "2", "--share-device", "--steps", "40", "--warmup", "10", "--no-cpu-baseline"] + extra,
+        out = subprocess.run([sys.executable, bench, "--gpus", "2", "--share-device", "--steps", "40", "--warmup", "10", "--full", "--no-cpu-baseline"] + extra,
                              capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

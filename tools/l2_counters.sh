@@ -11,7 +11,7 @@ P=$O/profiles_out
 mkdir -p $P
 cd /tmp
 export TMPDIR=/tmp
-B="python3 $R/bench.py --network $NET --steps 48 --warmup 20 --no-cpu-baseline --no-extra --no-live-traffic"
+B="python3 $R/bench.py --network $NET --steps 48 --warmup 20 --full --no-cpu-baseline --no-extra --no-live-traffic"
 DIRS=""
 i=0
 for pair in "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_LEVEL_sum" \

@@ -21,15 +21,15 @@ profile() {  # $1 = suffix ("" or "_delft"), rest = bench arguments
   # whole-batch launches instead of the default plan's half-batch ones
   export PEDN_STREAM_PROBE=0
   rm -rf $O/kt$SUF $O/pf$SUF $O/pw$SUF $O/sq1$SUF $O/sq2$SUF $O/sq3$SUF $O/sq4$SUF
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt$SUF -- python3 $R/bench.py "$@" --no-cpu-baseline --no-extra > $O/kt$SUF.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt$SUF -- python3 $R/bench.py "$@" --full --no-cpu-baseline --no-extra > $O/kt$SUF.log 2>&1
   echo "kernel trace$SUF done"
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pf$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --no-cpu-baseline --no-extra > $O/pf$SUF.log 2>&1
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pw$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --no-cpu-baseline --no-extra > $O/pw$SUF.log 2>&1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pf$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --full --no-cpu-baseline --no-extra > $O/pf$SUF.log 2>&1
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pw$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --full --no-cpu-baseline --no-extra > $O/pw$SUF.log 2>&1
   echo "FETCH/WRITE$SUF done"
-  rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/sq1$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --no-cpu-baseline --no-extra > $O/sq1$SUF.log 2>&1 || echo "SQ pass 1 failed (see sq1$SUF.log)"
-  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS --kernel-trace --output-format csv -d $O/sq2$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --no-cpu-baseline --no-extra > $O/sq2$SUF.log 2>&1 || echo "SQ pass 2 failed (see sq2$SUF.log)"
-  rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d $O/sq3$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --no-cpu-baseline --no-extra > $O/sq3$SUF.log 2>&1 || echo "SQ pass 3 failed (see sq3$SUF.log)"
-  rocprofv3 --pmc SQ_WAVES SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/sq4$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --no-cpu-baseline --no-extra > $O/sq4$SUF.log 2>&1 || echo "SQ pass 4 failed (see sq4$SUF.log)"
+  rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/sq1$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --full --no-cpu-baseline --no-extra > $O/sq1$SUF.log 2>&1 || echo "SQ pass 1 failed (see sq1$SUF.log)"
+  rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS --kernel-trace --output-format csv -d $O/sq2$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --full --no-cpu-baseline --no-extra > $O/sq2$SUF.log 2>&1 || echo "SQ pass 2 failed (see sq2$SUF.log)"
+  rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace --output-format csv -d $O/sq3$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --full --no-cpu-baseline --no-extra > $O/sq3$SUF.log 2>&1 || echo "SQ pass 3 failed (see sq3$SUF.log)"
+  rocprofv3 --pmc SQ_WAVES SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace --output-format csv -d $O/sq4$SUF -- python3 $R/bench.py "$@" --steps 48 --warmup 20 --full --no-cpu-baseline --no-extra > $O/sq4$SUF.log 2>&1 || echo "SQ pass 4 failed (see sq4$SUF.log)"
   unset PEDN_STREAM_PROBE
   (cd $R && python3 tools/summarize_busy.py $O/sq3$SUF $O/sq4$SUF > $P/$TAG${SUF}_unit_busy.json) || true
   echo "SQ$SUF done"
@@ -46,7 +46,7 @@ if [ "$PART" = all ] || [ "$PART" = trace ]; then
   # the same command with ONE chain of launches (PEDN_STREAMS=1): every launch covers the whole batch and runs alone -- the per-launch
   # figure a reader can check by hand (bytes of the whole batch / mean launch duration)
   rm -rf $O/kt1
-  PEDN_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python3 $R/bench.py --network melbourne --no-cpu-baseline --no-extra --no-live-traffic > $O/kt1.log 2>&1
+  PEDN_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python3 $R/bench.py --network melbourne --full --no-cpu-baseline --no-extra --no-live-traffic > $O/kt1.log 2>&1
   cp $O/kt1/*/*_kernel_stats.csv $P/${TAG}_one_chain_kernel_stats.csv
   profile _delft --network delft
   # config #5: per-kernel durations of the batched RL step, plain and after reset(options={'randomize': True})
@@ -80,17 +80,17 @@ if [ "$PART" = rl ]; then      # only the RL kernel statistics of the trace part
 fi
 cd $R
 if [ "$PART" = all ] || [ "$PART" = bench ]; then
-  # the default command: its LAST stdout line is the compact object the driver parses, everything measured goes to bench_full.json
-  python3 bench.py > $P/${TAG}_bench_n1_line.json 2> $O/bench.err
+  # the full measurement: its LAST stdout line is the compact object, everything measured goes to bench_full.json
+  python3 bench.py --full > $P/${TAG}_bench_n1_line.json 2> $O/bench.err
   cp bench_full.json $P/${TAG}_bench_n1.json
   python3 bench.py --steps 20 --warmup 5 > $P/${TAG}_bench_driver_command_line.json 2>> $O/bench.err        # the driver's own command
-  python3 bench.py --network delft > $P/${TAG}_delft_bench_n1_line.json 2>> $O/bench.err
+  python3 bench.py --full --network delft > $P/${TAG}_delft_bench_n1_line.json 2>> $O/bench.err
   cp bench_full.json $P/${TAG}_delft_bench_n1.json
   python3 bench.py --rl --network 45_intersections --replicas 2048 > $P/${TAG}_bench_rl_config5.json 2>> $O/bench.err
   python3 bench.py --rl --network 45_intersections --replicas 2048 --history recent >> $P/${TAG}_bench_rl_config5.json 2>> $O/bench.err
   python3 bench.py --rl --randomize --network 45_intersections --replicas 2048 >> $P/${TAG}_bench_rl_config5.json 2>> $O/bench.err
-  for r in 2048 3072 4096; do python3 bench.py --replicas $r --no-cpu-baseline --no-extra --steps 200 --warmup 50; done > $P/${TAG}_replica_scaling.jsonl 2>> $O/bench.err
-  { python3 bench.py --network nine_intersections --replicas 256 --no-cpu-baseline --no-extra; python3 bench.py --network 45_intersections --replicas 2048 --no-cpu-baseline --no-extra; } > $P/${TAG}_small_configs.jsonl 2>> $O/bench.err
+  for r in 2048 3072 4096; do python3 bench.py --replicas $r --full --no-cpu-baseline --no-extra --steps 200 --warmup 50; done > $P/${TAG}_replica_scaling.jsonl 2>> $O/bench.err
+  { python3 bench.py --network nine_intersections --replicas 256 --full --no-cpu-baseline --no-extra; python3 bench.py --network 45_intersections --replicas 2048 --full --no-cpu-baseline --no-extra; } > $P/${TAG}_small_configs.jsonl 2>> $O/bench.err
 fi
 if [ "$PART" = all ] || [ "$PART" = extras ]; then
   make -s -C pednstream_amd/csrc phase-profile 2>> $O/bench.err || true      # the instrumented build must match the engine's ABI

@@ -1,8 +1,8 @@
 """Overlap of the launches of the two chains, from a rocprofv3 --kernel-trace of a two-chain run (least perturbed view):
 
     cd /tmp && export TMPDIR=/tmp PEDN_STREAMS=2
-    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt2 -- python3 $REPO/bench.py --steps 120 --warmup 40 --no-cpu-baseline --no-extra --no-live-traffic
-    python3 $REPO/tools/trace_overlap.py /tmp/kt2
+    rocprofv3 --kernel-trace --output-format csv -d kt2 -- python3 $REPO/bench.py --steps 120 --warmup 40 --full --no-cpu-baseline --no-extra --no-live-traffic
+    python3 $REPO/tools/trace_overlap.py kt2
 
 Takes the last 200 step-kernel dispatches, prints a stretch of them (start / end in us, queue) and how much of the time 0 / 1 / 2
 of them were in flight."""
