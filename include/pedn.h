@@ -264,10 +264,11 @@ int pedn_set_streams(pedn_sim* sim, int32_t n);
  * the measured cost pedn_model_desc.node_cost; with n >= 6: info[5] = 1 when those one-launch steps skip the loads of corridors that were
  * empty in all 64 replicas of a group at the step before (quiet corridors, PEDN_QUIET=0|1; results are the same either way); with
  * n >= 7: info[6] = 1 when the node kernels skip the stores of +0.0 into rows of inflow / outflow / cumulative_inflow /
- * cumulative_outflow / num_pedestrians / density that have held +0.0 since the last pedn_reset (zero elision, PEDN_ZERO_ELIDE=0|1,
+ * cumulative_outflow / num_pedestrians / density / link_flow that have held +0.0 since the last pedn_reset (zero elision, PEDN_ZERO_ELIDE=0|1,
  * full-record mode only; results are the same either way; pedn_device_ptr on one of those fields, and the clocked steps, turn it
  * off until the next pedn_reset); with n >= 8: info[7] = node-kernel launches that could skip such stores since the last reset of
- * either kind. */
+ * either kind; with n >= 9: info[8] = 1 when the quiet-corridor launches of info[5] also skip the column pass / row sums of a node
+ * slot whose flows are +0.0 in all 64 replicas of a group (PEDN_QUIET_LEAN=0|1, default on; results are the same either way). */
 int pedn_plan_info(pedn_sim* sim, int32_t* info, int32_t n);
 
 /* reset all histories and dynamic state to t = 0 (widths, turning fractions and demand are kept) */

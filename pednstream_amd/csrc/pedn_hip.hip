@@ -61,10 +61,11 @@ struct pedn_sim {
   // row since -- the next LU launch may use them; -1 none.  Cleared by everything that could break that (no_quiet).
   int quiet = 0;
   int quiet_valid = -1;
+  int quiet_lean = 1;   // PEDN_QUIET_LEAN=0|1 (default on): those launches skip the node work that all-zero flows fix (DevView.quiet_lean)
   uint32_t* d_quiet = nullptr;
   // Zero elision (DevView.zg64 / zg32; PEDN_ZERO_ELIDE=0|1, default on): zhw64 = the highest row of inflow / outflow / cumulative_inflow /
-  // cumulative_outflow, zhw32 = of num_pedestrians / density, that may hold anything but +0.0 -- -1 after a full reset (which leaves every
-  // row at +0.0), kept by the lazy reset (the old episode's rows stay), INT_MAX when something the host does not follow may write them
+  // cumulative_outflow, zhw32 = of num_pedestrians / density / link_flow, that may hold anything but +0.0 -- -1 after a full reset (which
+  // leaves every row at +0.0), kept by the lazy reset (the old episode's rows stay), INT_MAX when something the host does not follow may write them
   // (a zero-copy pointer, the clocked steps) until the next full reset.  A launch that writes row x of a group gets the gate iff
   // x > the group's mark; the mark is raised to x once the step is enqueued (both chains of a step decide from the marks before it).
   // Only zeros are ever written below the marks' back (clear_rows, catch_up), so they need not raise them.
@@ -987,6 +988,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     // quiet corridors: the owner-wave launches skip the loads of corridors that are empty in all 64 replicas of a group (node_step)
     s->quiet = s->link_owner && m->node_model != PEDN_NODE_OPTIMAL;
     if (const char* f = getenv("PEDN_QUIET")) s->quiet = atoi(f) != 0;
+    if (const char* f = getenv("PEDN_QUIET_LEAN")) s->quiet_lean = atoi(f) != 0;
     // zero elision: the node kernels skip +0.0 stores into rows that hold +0.0 since the last full reset (zero_gate)
     if (const char* f = getenv("PEDN_ZERO_ELIDE")) s->zero_elide = atoi(f) != 0;
     // 0 = by batch: two chains where the step is not a pure chain of latencies any more -- from 4096 envs, and from 1024 with per-env
@@ -1550,6 +1552,7 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   const bool quiet = lu && !inl && s->quiet;
   vn.quiet = quiet ? s->d_quiet : nullptr;
   vn.quiet_use = quiet && s->quiet_valid == t - 1;
+  vn.quiet_lean = quiet && s->quiet_lean ? 1 : 0;
   // zero elision: node_kernel(t) writes row t of the flows and cumulative counts, node_kernel<LU>(t) also row t - 1 of num_pedestrians /
   // density (the link update behind an ordinary node kernel writes row t of those, ungated)
   vn.zg64 = zero_gate(s, zhw64, t);
@@ -1749,6 +1752,7 @@ int pedn_plan_info(pedn_sim* s, int32_t* info, int32_t n) {
   if (n >= 6) info[5] = s->quiet && info[1];   // the owner-wave launches keep and use the quiet-corridor words (PEDN_QUIET)
   if (n >= 7) info[6] = s->zero_elide && !s->v.hist;   // the node kernels may skip +0.0 stores into clean rows (PEDN_ZERO_ELIDE)
   if (n >= 8) info[7] = s->zgated;   // ... and this many node-kernel launches had a gate open since the last reset
+  if (n >= 9) info[8] = s->quiet_lean && s->quiet && info[1];   // the quiet-corridor launches take the lean path (PEDN_QUIET_LEAN)
   return PEDN_OK;
 }
 
@@ -1959,7 +1963,7 @@ void* pedn_device_ptr(pedn_sim* s, int32_t field, int64_t* columns, int64_t* rep
   if ((s->link_pending >= 0 || s->forked || s->clocked || s->valid_hi != 0x7fffffff) && pedn_flush(s) != PEDN_OK) return nullptr;
   // zero elision: a zero-copy consumer may write any row of the field -- no gate on its group until the next full reset
   if (field <= F_CO) s->zhw64 = 0x7fffffff;
-  if (field == 7 + G_N || field == 7 + G_K) s->zhw32 = 0x7fffffff;
+  if (field == 7 + G_N || field == 7 + G_K || field == 7 + G_LF) s->zhw32 = 0x7fffffff;
   if (columns) *columns = field < 4 ? s->v.Lall : s->v.L;
   if (replica_stride) *replica_stride = s->v.RS;
   return field < 7 ? (void*)s->v.f64[field] : (void*)s->v.f32[field - 7];
@@ -2572,23 +2576,28 @@ extern "C" int pedn_debug_lt_timeline(unsigned long long* out, int n_blocks, int
   if (n_blocks > PEDN_LT_BLOCKS) n_blocks = PEDN_LT_BLOCKS;
   return (int)hipMemcpy(out, dev, sizeof(unsigned long long) * (size_t)n_blocks * 4, hipMemcpyDeviceToHost);
 }
-// raw accumulators of the first n_waves waves of the grid: [wave][12] = 9 phase sums, -, count, lifetime (tools/pack_analysis.py)
+// raw accumulators of the first n_waves waves of the grid, quiet and non-quiet launches together: [wave][12] = 9 phase sums, -, count,
+// lifetime (tools/pack_analysis.py)
 extern "C" int pedn_debug_phase_waves(unsigned long long* out, int n_waves) {
   void* dev = nullptr;
   if (hipGetSymbolAddress(&dev, HIP_SYMBOL(g_phase)) != hipSuccess) return -1;
   if (n_waves > PEDN_PHASE_WAVES) n_waves = PEDN_PHASE_WAVES;
-  return (int)hipMemcpy(out, dev, sizeof(unsigned long long) * (size_t)n_waves * 12, hipMemcpyDeviceToHost);
+  std::vector<unsigned long long> h((size_t)n_waves * 24);
+  if (hipMemcpy(h.data(), dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  for (size_t w = 0; w < (size_t)n_waves; ++w)
+    for (int i = 0; i < 12; ++i) out[w * 12 + i] = h[w * 24 + i] + h[w * 24 + 12 + i];
+  return 0;
 }
 extern "C" int pedn_debug_phases(unsigned long long* out, int zero) {
-  const size_t n = (size_t)PEDN_PHASE_WAVES * 12;
+  const size_t n = (size_t)PEDN_PHASE_WAVES * 24;   // out[0..11]: non-quiet waves, out[12..23]: quiet ones (g_phase)
   void* dev = nullptr;
   if (hipGetSymbolAddress(&dev, HIP_SYMBOL(g_phase)) != hipSuccess) return -1;
   if (zero) return (int)hipMemset(dev, 0, n * sizeof(unsigned long long));
   std::vector<unsigned long long> h(n);
   if (hipMemcpy(h.data(), dev, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  for (int i = 0; i < 16; ++i) out[i] = 0;
+  for (int i = 0; i < 24; ++i) out[i] = 0;
   for (size_t w = 0; w < (size_t)PEDN_PHASE_WAVES; ++w)
-    for (int i = 0; i < 12; ++i) out[i] += h[w * 12 + i];
+    for (int i = 0; i < 24; ++i) out[i] += h[w * 24 + i];
   return 0;
 }
 #endif

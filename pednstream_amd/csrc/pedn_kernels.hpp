@@ -31,7 +31,8 @@ using namespace pedn;
 // s_memtime stamps at the phase boundaries, summed over all waves into g_phase.  Not part of the product build.
 #ifdef PEDN_PHASE_PROFILE
 #define PEDN_PHASE_WAVES (1 << 17)
-__device__ unsigned long long g_phase[PEDN_PHASE_WAVES * 12];  // [wave of the grid][phase]: plain stores, no contended atomics
+// [wave of the grid][non-quiet | quiet slot wave (node_kernel<LU>: both quiet words set)][phase]: plain stores, no contended atomics
+__device__ unsigned long long g_phase[PEDN_PHASE_WAVES * 24];
 #define PH(i, dep) do { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) : "v"(dep) : "memory"); ph[i] = _t; } while (0)
 __device__ unsigned long long g_tphase[4096 * 8];  // turn_frac_body: [row][stamp] of replica group 0
 #define TPH(i, dep) do { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) : "v"(dep) : "memory"); tph[i] = _t; } while (0)
@@ -763,6 +764,8 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
   // zero elision (DevView.zg64 / zg32): not in the clocked step, whose step index the host does not see, nor in recent-history mode
   constexpr bool ZE = !CLK && !HIST;
   const size_t qgroup = (size_t)(RS >> 6), qslot = (size_t)by * 8 + wave, qrg = (size_t)(r0 >> 6);
+  // lean quiet step (QL; DevView.quiet_lean): the column pass and the row sums of a slot whose products are all +0.0 (row0, below)
+  constexpr bool QL = QU && !LP;
   bool quiet = false;
   if (QU && v.quiet != nullptr && v.quiet_use) {
     const uint2 qw = *reinterpret_cast<const uint2*>(v.quiet + ((((size_t)(tp & 1) * (size_t)v.quiet_npos + qslot) * qgroup + qrg) << 1));
@@ -780,6 +783,9 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
   bool qz = false;   // QU: this lane's share of the quiet word of step t (virtual pairs: never quiet)
   double s_i = 0.0, r_i = 0.0, qo = 0.0, qi = 0.0, co_prev = 0.0, ci_prev = 0.0;
   int lin = 0, lout = 0, kind = 0;
+  // QL: every P[slot][j] * s_i of this wave's row is +0.0 in all 64 lanes (wave-uniform) -- then so is every g_slot,j that the column
+  // passes leave in the row (a = +0.0: b = r_j * (a / D_j) is +-0.0 or NaN, b < a is false, g = floor(a)), and the row sums are +0.0
+  bool row0 = false;
   double tfr[MD - 1];
 
   if (HELP && wave16 >= 8) {   // wave-uniform
@@ -947,7 +953,7 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
         const SpeedOut so = speed_calc(v, Pin, lin, tp, r, ka, kb, lu_rs, lu_old, nz);
         rowp(v.f32[G_V], R32(G_V, tp), lin, L, RS, r0)[lane] = so.spd;
         rowp(v.f32[G_TT], R32(G_TT, tp), lin, L, RS, r0)[lane] = so.tt;
-        rowp(v.f32[G_LF], R32(G_LF, tp), lin, L, RS, r0)[lane] = so.lf;
+        if (!(ZE && v.zg32 && __all(__float_as_int(so.lf) == 0))) rowp(v.f32[G_LF], R32(G_LF, tp), lin, L, RS, r0)[lane] = so.lf;
         if (lu_win) rowp(v.f32[G_ATT], R32(G_ATT, tp), lin, L, RS, r0)[lane] = so.att;
         v.rsum[(size_t)lin * RS + r] = so.rs;
         // recorded width of the OUTGOING link (link.py:188 / :451-452): its back gate as loaded above, before any action of this step
@@ -997,13 +1003,17 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     }
     if (kind == 1) {
       // P[i][j] * s_i  (node.py:285)
+      uint64_t zb = 0;
 #pragma unroll
       for (int jj = 0; jj < MD - 1; ++jj) {
         if (jj < m - 1) {
           const int j = jj < slot ? jj : jj + 1;
-          sPS[(size_t)(base + slot * m + j) * 64 + lane] = LP ? tfr[jj] : tfr[jj] * s_i;
+          const double ps = LP ? tfr[jj] : tfr[jj] * s_i;
+          sPS[(size_t)(base + slot * m + j) * 64 + lane] = ps;
+          zb |= (uint64_t)__double_as_longlong(ps);
         }
       }
+      row0 = QL && v.quiet_lean && __all(zb == 0);
     } else {
       sPS[(size_t)(base + slot) * 64 + lane] = s_i;
     }
@@ -1026,23 +1036,28 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     // column `slot`: D_j = sum_i P[i][j] s_i (i ascending), g_ij = floor(min(P s, r_j * (P s / D_j)))  (node.py:286-298)
     double D = 0.0;
     bool first = true;
+    uint64_t zb = 0;
 #pragma unroll
     for (int k = 0; k < MD; ++k) {
       if (k < m && k != slot) {
         double x = sPS[(size_t)(base + k * m + slot) * 64 + lane];
         D = first ? x : D + x;
         first = false;
+        zb |= (uint64_t)__double_as_longlong(x);
       }
     }
-    const double Ds = D != 0.0 ? D : 1e-5;
+    // QL: a column of +0.0 in all 64 lanes leaves every g = +0.0 (see row0) where it already stands, and qi = +0.0
+    if (!(QL && v.quiet_lean && __all(zb == 0))) {
+      const double Ds = D != 0.0 ? D : 1e-5;
 #pragma unroll
-    for (int k = 0; k < MD; ++k) {
-      if (k < m && k != slot) {
-        double a = sPS[(size_t)(base + k * m + slot) * 64 + lane];
-        double b = r_i * (a / Ds);
-        double g = floor(b < a ? b : a);
-        sPS[(size_t)(base + k * m + slot) * 64 + lane] = g;
-        qi += g;
+      for (int k = 0; k < MD; ++k) {
+        if (k < m && k != slot) {
+          double a = sPS[(size_t)(base + k * m + slot) * 64 + lane];
+          double b = r_i * (a / Ds);
+          double g = floor(b < a ? b : a);
+          sPS[(size_t)(base + k * m + slot) * 64 + lane] = g;
+          qi += g;
+        }
       }
     }
   }
@@ -1052,9 +1067,11 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
 
   if (active) {
     if (kind == 1) {
+      if (!row0) {
 #pragma unroll
-      for (int j = 0; j < MD; ++j)
-        if (j < m && j != slot) qo += sPS[(size_t)(base + slot * m + j) * 64 + lane];
+        for (int j = 0; j < MD; ++j)
+          if (j < m && j != slot) qo += sPS[(size_t)(base + slot * m + j) * 64 + lane];
+      }
       if (LP) {  // q = A_ub @ floor(x): the column sums were not formed by a column pass
 #pragma unroll
         for (int k = 0; k < MD; ++k)
@@ -1104,7 +1121,7 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
   PH(9, qo + qi);
   if (active && lane == 0) {
     for (int i = 1; i < 10; ++i) if (ph[i] == 0) ph[i] = ph[i - 1];
-    const size_t w = (((size_t)by * (size_t)(v.subRS / 64) + bx) * 8 + wave) % PEDN_PHASE_WAVES;
+    const size_t w = ((((size_t)by * (size_t)(v.subRS / 64) + bx) * 8 + wave) % PEDN_PHASE_WAVES) * 2 + (quiet ? 1 : 0);
     for (int i = 1; i < 10; ++i) g_phase[w * 12 + i] += ph[i] - ph[i - 1];
     g_phase[w * 12 + 10] += 1ull;
     g_phase[w * 12 + 11] += ph[9] - ph[0];

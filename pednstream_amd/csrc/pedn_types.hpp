@@ -140,5 +140,9 @@ struct DevView {
   // cumulative_inflow / cumulative_outflow (zg64: row t) and of num_pedestrians / density (zg32: row t - 1, node_kernel<LU>) holds +0.0
   // -- not written since the last full reset but by zeros (pedn_sim.zhw64 / zhw32).  A wave then skips a pair of stores whose values
   // are +0.0 in all 64 lanes (node_step).  0 in the engine's own view: set only in the copy a step launch carries.
+  // zg32 covers link_flow too: its quiet value ks * speed is +0.0 wherever num_pedestrians is.
   int32_t zg64, zg32;
+  // Lean quiet step (PEDN_QUIET_LEAN; set with DevView.quiet): a slot wave whose column / row of the node's products P * s holds +0.0 in
+  // all 64 lanes skips its column pass / row sums, whose results that fixes (node_step)
+  int32_t quiet_lean;
 };

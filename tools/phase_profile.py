@@ -43,14 +43,19 @@ def main():
         e.run(150, 250)
         e.synchronize()
         wall = (time.perf_counter() - t0) / 100
-        out = (ctypes.c_ulonglong * 16)()
+        out = (ctypes.c_ulonglong * 24)()
         lib.pedn_debug_phases(out, 0)
-        o = np.array(out[:], dtype=np.float64)
+        q = np.array(out[:], dtype=np.float64).reshape(2, 12)     # [non-quiet, quiet slot waves (node_kernel<LU>)][phase]
+        o = q.sum(axis=0)
         n, total = o[10], o[11]
         print(f"== {network} x {R}: {int(n / 100)} active waves per launch, mean wave lifetime {total / n:.0f} s_memtime ticks "
               f"(instrumented step, built for 6 waves per SIMD: {wall * 1e6:.1f} us)")
-        for i, name in enumerate(PHASES, start=1):
-            print(f"   {name:48s} {o[i] / n:9.0f} ticks  {100 * o[i] / total:5.1f} %")
+        print(f"   {'':48s} {'all':>15s}  {'non-quiet':>15s}  {'quiet':>15s}")
+        print(f"   {'waves per launch':48s} {n / 100:15.0f}  {q[0, 10] / 100:15.0f}  {q[1, 10] / 100:15.0f}")
+        cols = [(o, n, total)] + [(q[k], q[k, 10], q[k, 11]) for k in (0, 1)]
+        for i, name in enumerate(PHASES + ["lifetime"], start=1):
+            i = 11 if i == 10 else i
+            print(f"   {name:48s} " + "  ".join(f"{c[i] / max(cn, 1):7.0f} {100 * c[i] / max(ct, 1):5.1f} %" for c, cn, ct in cols))
         net.close()
 
 
