@@ -218,6 +218,37 @@ int pedn_read(pedn_sim* sim, int32_t field, int32_t t0, int32_t t1, int32_t link
 /* number of time indices field `field` keeps: T+1, or the size of its ring in PEDN_HIST_RECENT mode (time index t lives in
  * row t mod that size) */
 int pedn_history_rows(pedn_sim* sim, int32_t field);
+
+/* ---- evaluation metrics of every replica (rl/rl_utils.py:770-1512 of the reference, on what save_network_state would write) ----------
+ * Every history is read over its T+1 rows; rows no step has written read as zero (the hi rule of pedn_read).  The f32 fields
+ * travel_time, num_pedestrians and density are widened to f64 before any arithmetic; k_critical, k_jam and free_flow_speed are
+ * per replica, length and width the static ones.  Sums over (link, time) are per-link serial partial sums folded in link order:
+ * within rounding of the reference's single serial sum, bit-identical from run to run and for any split into windows.
+ *   pedn_metrics_begin        static set-up, accumulators zeroed.  link_flags[n_links]: bit 0 the link starts at an origin node,
+ *                             bit 1 it ends at a destination node, bit 2 it lies on some od path (all links when there is no path
+ *                             finder).  origin_rows / origin_len [n_origins]: demand row (-1 none) and the number of demand values of
+ *                             each origin node in the order of origin_nodes.  agent_ptr[n_agents + 1] / agent_links: the links of each
+ *                             agent (gater: real incoming, then real outgoing links; separator: forward, reverse).
+ *   pedn_metrics_accumulate   folds rows t0 <= t < t1 into the accumulators.  Windows must increase and must not overlap; rows that
+ *                             no window covers read as zero.  PEDN_E_ARG with pedn_read's message when a row has left a field's ring.
+ *   pedn_metrics_read         out[n_replicas][PEDN_N_METRICS] (indices below), agent_links[n_replicas][len(agent_links)][2] = per-link
+ *                             mean density and mean density / k_jam (NaN: no valid row), agents[n_replicas][n_agents][3] = mean of
+ *                             those over the agent's links and their number.  Either agent array may be NULL. */
+enum {
+  PEDN_M_THROUGHPUT = 0, PEDN_M_COMPLETED_DEMAND, PEDN_M_TOTAL_DEMAND,
+  PEDN_M_AVG_TRAVEL_TIME, PEDN_M_TT_NUM_LINKS,
+  PEDN_M_TOTAL_DELAY, PEDN_M_DELAY_INTENSITY, PEDN_M_DELAY_PERSON_TIME, PEDN_M_DELAY_NUM_LINKS,
+  PEDN_M_AVG_TIME_SPENT, PEDN_M_PERSON_TIME, PEDN_M_TOTAL_TRIPS, PEDN_M_NUM_ORIGIN_LINKS,
+  PEDN_M_SERVED_RATE, PEDN_M_TOTAL_INFLOW, PEDN_M_TOTAL_OUTFLOW, PEDN_M_NUM_DEST_LINKS,
+  PEDN_M_CONGESTION_TIME, PEDN_M_AVG_CONGESTION_DENSITY, PEDN_M_CONGESTION_FRACTION, PEDN_M_TOTAL_AREA_TIME,
+  PEDN_M_CONGESTED_ROWS, PEDN_M_COUNTED_ROWS,
+  PEDN_N_METRICS
+};
+int pedn_metrics_begin(pedn_sim* sim, const int32_t* link_flags, const int32_t* origin_rows, const int32_t* origin_len, int32_t n_origins,
+                       const int32_t* agent_ptr, const int32_t* agent_links, int32_t n_agents, double unit_time);
+int pedn_metrics_accumulate(pedn_sim* sim, int32_t t0, int32_t t1);
+int pedn_metrics_read(pedn_sim* sim, double* out, double* agent_links, double* agents);
+
 /* Everything the engine still owes the histories is enqueued on pedn_stream(): a link update left pending by the last pedn_step /
  * pedn_run (the next step's node kernel would have performed it), chains that are still forked, the rows a lazy reset declared
  * unwritten (cleared now).  Asynchronous.  After it, work ordered behind pedn_stream() sees every row of every field complete. */

@@ -133,7 +133,9 @@ struct pedn_sim {
   void* rl_pin = nullptr;      // pinned landing buffer of the RL step's observations + rewards (rl_fetch)
   size_t rl_pin_bytes = 0;
   std::string err;
+  struct MetricsState* metrics = nullptr;   // evaluation metrics (pedn_metrics.hpp)
 };
+static void metrics_free(pedn_sim* s);
 
 // the quiet words of the last step may not be used by the next launch (pedn_sim.quiet_valid)
 static inline void no_quiet(pedn_sim* s) { s->quiet_valid = -1; }
@@ -1091,6 +1093,7 @@ int pedn_destroy(pedn_sim* s) {
   if (s->clocked) hipDeviceSynchronize();   // clocked steps may still run on a caller's stream (or in a graph being replayed there)
   if (s->stream2) hipStreamSynchronize(s->stream2);
   if (s->stream) hipStreamSynchronize(s->stream);
+  metrics_free(s);
   for (void* p : s->allocs) hipFree(p);
   if (s->rl_pin) hipHostFree(s->rl_pin);
   for (pedn_sim::Stage& st : s->stage) {
@@ -2601,3 +2604,5 @@ extern "C" int pedn_debug_phases(unsigned long long* out, int zero) {
   return 0;
 }
 #endif
+
+#include "pedn_metrics.hpp"

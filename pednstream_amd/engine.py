@@ -178,6 +178,9 @@ def _load():
         "pedn_rl_clock_signature": (C.c_uint64, [P]),
         "pedn_flush": (C.c_int, [P]),
         "pedn_device_math": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, C.c_uint64, _F64P]),
+        "pedn_metrics_begin": (C.c_int, [P, _I32P, _I32P, _I32P, C.c_int32, _I32P, _I32P, C.c_int32, C.c_double]),
+        "pedn_metrics_accumulate": (C.c_int, [P, C.c_int32, C.c_int32]),
+        "pedn_metrics_read": (C.c_int, [P, _F64P, _F64P, _F64P]),
     }
     # the version first: a stale or alternate library (PEDN_HIP_LIB) must fail with this message, not with an AttributeError on a symbol
     lib.pedn_abi_version.restype, lib.pedn_abi_version.argtypes = C.c_int, []
@@ -206,7 +209,8 @@ EXPORTS = ["pedn_abi_version", "pedn_last_error", "pedn_create", "pedn_destroy",
            "pedn_device_ptr", "pedn_history_rows", "pedn_stream", "pedn_timer_begin", "pedn_timer_end", "pedn_reset", "pedn_reset_lazy", "pedn_device_math", "pedn_profile_step", "pedn_profile_run", "pedn_profile_timeline", "pedn_set_streams", "pedn_plan_info", "pedn_rl_configure",
            "pedn_rl_apply_actions", "pedn_rl_observe", "pedn_rl_fetch", "pedn_rl_step_many", "pedn_rl_step", "pedn_rl_device_ptr", "pedn_get_widths", "pedn_set_link_params",
            "pedn_set_od_weights_per_replica", "pedn_get_od_weights_per_replica", "pedn_get_link_params", "pedn_randomize_scenarios", "pedn_reset_widths",
-           "pedn_flush", "pedn_rl_clock_begin", "pedn_rl_step_clocked", "pedn_rl_clock_end", "pedn_rl_clocked", "pedn_rl_clock_signature"]
+           "pedn_flush", "pedn_rl_clock_begin", "pedn_rl_step_clocked", "pedn_rl_clock_end", "pedn_rl_clocked", "pedn_rl_clock_signature",
+           "pedn_metrics_begin", "pedn_metrics_accumulate", "pedn_metrics_read"]
 
 
 def _p(a, dtype=np.float64):
@@ -600,6 +604,34 @@ class Engine:
 
     def read_element(self, field, link, replica, t):
         return self.read_block(field, t, t + 1, link, link + 1, replica, replica + 1).reshape(-1)[0]
+
+    # -- evaluation metrics (include/pedn.h: pedn_metrics_*; pednstream_amd.metrics builds the arguments)
+    N_METRICS = 23
+
+    def metrics_begin(self, link_flags, origin_rows, origin_len, agent_ptr, agent_links, unit_time):
+        a = [np.ascontiguousarray(x, dtype=np.int32) for x in (link_flags, origin_rows, origin_len, agent_ptr, agent_links)]
+        assert a[0].shape == (self.n_links,) and a[1].shape == a[2].shape
+        n_agents = max(len(a[3]) - 1, 0)
+        self._metrics_keep = a
+        self._metrics_shape = (n_agents, len(a[4]) if n_agents else 0)
+        self._ck(self._lib.pedn_metrics_begin(self._h, _p(a[0], np.int32), _p(a[1], np.int32), _p(a[2], np.int32), len(a[1]),
+                                              _p(a[3], np.int32) if n_agents else None, _p(a[4], np.int32) if n_agents else None,
+                                              n_agents, float(unit_time)))
+
+    def metrics_accumulate(self, t0, t1):
+        rc = self._lib.pedn_metrics_accumulate(self._h, int(t0), int(t1))
+        if rc < 0:
+            msg = self._lib.pedn_last_error(self._h).decode()
+            raise (IndexError if "ring" in msg else RuntimeError)(f"pedn_metrics_accumulate failed ({rc}): {msg}")
+
+    def metrics_read(self):
+        """(metrics [n_replicas, N_METRICS], agent links [n_replicas, n_agent_links, 2], agents [n_replicas, n_agents, 3])."""
+        n_agents, n_alinks = self._metrics_shape
+        out = np.empty((self.n_replicas, self.N_METRICS))
+        al = np.empty((self.n_replicas, n_alinks, 2))
+        ag = np.empty((self.n_replicas, n_agents, 3))
+        self._ck(self._lib.pedn_metrics_read(self._h, _p(out), _p(al) if n_agents else None, _p(ag) if n_agents else None))
+        return out, al, ag
 
     def device_ptr(self, field):
         cols, stride = C.c_int64(), C.c_int64()

@@ -688,6 +688,13 @@ class Network:
         t1 = self.simulation_steps + 1 if t1 is None else t1
         return self._flush().read_block(fid, t0, t1)
 
+    def metrics(self, t0: int = 0, t1: int = None):
+        """The reference's evaluation metrics of every replica over rows t0 <= t < t1, computed on the device
+        (``pednstream_amd.metrics.network_metrics``)."""
+        from .metrics import network_metrics
+
+        return network_metrics(self, t0, t1)
+
     def synchronize(self):
         self._flush().synchronize()
 

@@ -19,6 +19,8 @@ is ever rewarded; ``reward_mode="all"`` rewards every gater.
 """
 import numpy as np
 
+from .network import LINK_FIELDS
+
 OBS_MODES = {"option1": 1, "option2": 2, "option3": 3, "option4": 4, "option5": 5}
 FEATURES_PER_LINK = {"option1": 3, "option2": 4, "option3": 5, "option4": 2, "option5": 7}
 
@@ -136,10 +138,15 @@ class VecPedNetEnv:
 
     def __init__(self, dataset, n_envs=1, obs_mode="option1", normalize_obs=False, action_gap=1, seed=0,
                  reward_mode="reference", data_dir="data", replica_offset=0, device=0, network=None, verbose=False,
-                 history="full"):
+                 history="full", track_metrics=False):
         """``history="recent"``: the device keeps only what the recurrence and the observations need (Network's ``history``):
         45_intersections x 2048 envs x T = 700 takes 3.9 GB instead of 19.3 GB; observations, rewards and every number of the
-        simulation are the same."""
+        simulation are the same.  ``track_metrics``: every step folds the rows it wrote into the evaluation metrics of every env
+        (``pednstream_amd.metrics``), ``reset`` starts them again, ``episode_metrics()`` returns them -- with recent history the only
+        way to get them, the rows are gone by the end of the episode.  With recent history and an ``action_gap`` longer than the
+        rings of travel_time / num_pedestrians / density (4 rows), ``step`` / ``step_async`` step such an env step in pieces that the
+        rings hold (same observations, rewards and histories, more launches); ``step_device`` refuses that combination.  One-shot
+        metric calls on a tracking env's network are refused (they would discard the tracked episode)."""
         from .env_loader import NetworkEnvGenerator
 
         if obs_mode not in OBS_MODES:
@@ -189,6 +196,10 @@ class VecPedNetEnv:
         self.action_low, self.action_high = np.array(lo, np.float32), np.array(hi, np.float32)
         self.sim_step = 1
         self._device_views = None
+        self.track_metrics = bool(track_metrics)
+        self._metrics = None
+        self._folded = 0
+        self._rows = None
 
     # ------------------------------------------------------------------------------------------------ API
     AUTO_VECTORISED_FROM = 65      # randomize(mode="auto"): batches of this many envs and more draw their scenarios on the device
@@ -252,18 +263,87 @@ class VecPedNetEnv:
         net._widths_stale = True
         net._tf_host = {}
         self.sim_step = 1
+        if self.track_metrics:
+            from .metrics import EpisodeMetrics
+
+            if self._metrics is None:
+                self._metrics = EpisodeMetrics(net, agents=True, tracking=True)
+            else:
+                self._metrics.restart()
+            self._folded = 0               # rows [0, _folded) are in the accumulators; row 0 (the reset's) is pending now
+            self._fold_pending()
         obs, _ = eng.rl_observe(self.sim_step, accumulate=False)
         return obs, {}
+
+    def _fold_pending(self, now=False):
+        """Fold the written rows not yet in the tracked metrics ([_folded, sim_step)) -- ``now``, or when the next env step would push
+        the oldest of them out of the history rings.  Full record: the rows stay, they are folded when the metrics are read (one launch
+        per read instead of one per step); recent history: every few steps, before the 4-row rings lose them."""
+        if self._metrics is None or self._folded >= self.sim_step:
+            return
+        rows = self._ring_rows()
+        if now or self._folded < self.sim_step + self.action_gap - rows:
+            self._metrics.add(self._folded, self.sim_step)
+            self._folded = self.sim_step
+
+    def _tracked_metrics(self):
+        """The tracked EpisodeMetrics with every written row folded in."""
+        if not self.track_metrics:
+            raise RuntimeError("construct the env with track_metrics=True")
+        if self._metrics is None:
+            raise RuntimeError("call reset() first")
+        self._fold_pending(now=True)
+        return self._metrics
+
+    def _tracked_piece(self):
+        """With tracking on: the longest run of sub-steps whose rows the history rings still hold when the run is folded in (recent-history
+        mode keeps 4 rows of travel_time / num_pedestrians / density), or None when a whole env step fits."""
+        if self._metrics is None:
+            return None
+        rows = self._ring_rows()
+        return rows if self.action_gap > rows else None
+
+    def _ring_rows(self):
+        """Time indices the engine keeps of travel_time / num_pedestrians / density (T + 1 with the full record)."""
+        if self._rows is None:
+            eng = self.network.engine()
+            self._rows = min(eng.history_rows(LINK_FIELDS[f][0]) for f in ("travel_time", "num_pedestrians", "density"))
+        return self._rows
+
+    def _rl_step_tracked(self, eng, actions, fetch, piece):
+        """One env step in pieces the rings hold: the first ``piece`` sub-steps (with the actions) through pedn_rl_step, each further
+        sub-step as network_loading + an observation that adds its rewards to the step's sum -- what pedn_rl_step does within one call --,
+        every piece folded into the metrics before its rows leave the rings."""
+        t0, t1 = self.sim_step, self.sim_step + self.action_gap
+        obs, rew = eng.rl_step(actions, t0, piece, fetch=False)
+        self._metrics.add(t0, t0 + piece)
+        for t in range(t0 + piece, t1):
+            eng.step(t)
+            obs, rew = eng.rl_observe(t, accumulate=True, fetch=fetch and t == t1 - 1)
+            self._metrics.add(t, t + 1)
+        self._folded = t1
+        return obs, rew
+
+    def episode_metrics(self):
+        """The evaluation metrics of every env over the episode so far (``track_metrics=True``): the dicts of
+        ``pednstream_amd.metrics.network_metrics``; ``pednstream_amd.metrics.agent_local_metrics(env)`` has the per-agent ones."""
+        return self._tracked_metrics().result()
 
     def step(self, actions, fetch=True):
         """actions [n_envs, n_actions] widths in metres (None = keep the current widths)."""
         if self.sim_step + self.action_gap - 1 > self.simulation_steps:
             raise IndexError("episode is over; call reset()")
         eng = self.network._flush()
-        obs, rew = eng.rl_step(actions, self.sim_step, self.action_gap, fetch=fetch)
+        piece = self._tracked_piece()
+        if piece is None:
+            obs, rew = eng.rl_step(actions, self.sim_step, self.action_gap, fetch=fetch)
+        else:
+            self._fold_pending(now=True)
+            obs, rew = self._rl_step_tracked(eng, actions, fetch, piece)
         self.sim_step += self.action_gap
         self.network.current_step = self.sim_step - 1
         self.network._widths_stale = True
+        self._fold_pending()
         terminated = (self.sim_step - 1) >= self.simulation_steps     # pz_pednet_env.py:592 evaluated before the increment
         return obs, rew, terminated, False, {}
 
@@ -272,10 +352,17 @@ class VecPedNetEnv:
         the launches are enqueued, nothing is waited for; ``step_wait`` fetches."""
         if self.sim_step + self.action_gap - 1 > self.simulation_steps:
             raise IndexError("episode is over; call reset()")
-        self.network._flush().rl_step(actions, self.sim_step, self.action_gap, fetch=False)
+        eng = self.network._flush()
+        piece = self._tracked_piece()
+        if piece is None:
+            eng.rl_step(actions, self.sim_step, self.action_gap, fetch=False)
+        else:
+            self._fold_pending(now=True)
+            self._rl_step_tracked(eng, actions, False, piece)
         self.sim_step += self.action_gap
         self.network.current_step = self.sim_step - 1
         self.network._widths_stale = True
+        self._fold_pending()
 
     def step_wait(self):
         obs, rew = self.network.engine().rl_fetch()
@@ -300,6 +387,9 @@ class VecPedNetEnv:
 
         if self.sim_step + self.action_gap - 1 > self.simulation_steps:
             raise IndexError("episode is over; call reset()")
+        if self._tracked_piece() is not None:
+            raise RuntimeError("step_device does not track metrics in recent-history mode with an action_gap longer than the history "
+                               "rings; use step(), or history='full'")
         eng = self.network._flush()
         ptr = 0
         if actions is not None:
@@ -329,6 +419,7 @@ class VecPedNetEnv:
         self.sim_step += self.action_gap
         self.network.current_step = self.sim_step - 1
         self.network._widths_stale = True
+        self._fold_pending()
         obs, rew = self.device_views()
         return obs, rew, (self.sim_step - 1) >= self.simulation_steps
 
@@ -350,7 +441,9 @@ class VecPedNetEnv:
         per policy step -- see ``GraphedRollout``.  ``generators``: every ``torch.Generator`` the two callables draw from other than the
         default one (torch must know them before the capture: ``CUDAGraph.register_generator_state``).  ``steps_per_replay`` > 1: that
         many consecutive iterations in ONE graph (``GraphedRollout.step`` then advances by that many policy steps; the tail of an episode
-        that does not fill a graph is stepped eagerly)."""
+        that does not fill a graph is stepped eagerly).  Not with ``track_metrics``: the replayed steps would not be folded in."""
+        if self.track_metrics:
+            raise RuntimeError("capture() does not track metrics: construct the env with track_metrics=False")
         return GraphedRollout(self, policy_fn, on_step, generators, steps_per_replay)
 
     def _ordered_behind_engine(self):
