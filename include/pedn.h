@@ -413,6 +413,30 @@ uint64_t pedn_rl_clock_signature(pedn_sim* sim);
 /* device buffers for zero-copy consumers: 0 actions (f64 [R][n_actions]), 1 observations (f32 [R][n_obs]), 2 rewards (f32 [R][n_agents]) */
 void* pedn_rl_device_ptr(pedn_sim* sim, int32_t which);
 
+/* ---- rule-based controllers on the device (rl/agents/rule_based.py, evaluated by rl/rl_utils.py:1513-1750) ----------------------
+ * A controller per agent of the pedn_rl_configure agent set computes the agent's next action from the float32 observation the step has
+ * just written, inside the observation part of the step's second launch (no extra launch, no host round trip between env steps):
+ *   kind 1  RuleBasedGaterAgent(outgoing_links, "option2", threshold): needs obs_mode 2; `threshold` is rounded to float32, `open[slot]`
+ *           is the float32 physical width of the slot's link (the "open" action and the action at a density equal to the threshold)
+ *   kind 2  RuleBasedSeparatorAgent(width, use_smoothing, buffer_size): window[a] = buffer_size with smoothing, 0 without (at most
+ *           PEDN_CTRL_MAX_WINDOW = 32); wide[a] != 0: the width is a binary64 numpy scalar (binary64 arithmetic without smoothing)
+ *   kind 0  no controller: the agent's action slots stay NaN (no action)
+ * Arrays are [n_agents], `open` is [n_actions].  Configuring empties every moving-average buffer and the episode sums, and fills the
+ * action rows with NaN; pedn_reset and pedn_ctrl_observe keep the buffers (they belong to the agent, not to the episode).
+ *   pedn_ctrl_observe(t)             the reset observation (pedn_rl_observe(t, 0)) through the controllers: episode sums back to 0,
+ *                                    the actions of the first env step into the action rows
+ *   pedn_ctrl_step(t, gap, n)        n env steps t, t + gap, ... (pedn_rl_step with the action rows as device actions) enqueued without a
+ *                                    host wait; on the last sub-step of each the controllers decide the next actions and every agent's
+ *                                    summed reward is added to its float32 episode sum.  Results: pedn_rl_device_ptr / pedn_rl_fetch
+ *   pedn_ctrl_read                   host copies of the action rows [R][n_actions] (f64) / episode sums [R][n_agents] (f32); NULL skips
+ *   pedn_ctrl_device_ptr(which)      0 action rows, 1 episode sums */
+int pedn_ctrl_configure(pedn_sim* sim, const int32_t* kind, const int32_t* window, const int32_t* wide, const float* threshold,
+                        const double* width, const float* open);
+int pedn_ctrl_observe(pedn_sim* sim, int32_t t);
+int pedn_ctrl_step(pedn_sim* sim, int32_t t, int32_t action_gap, int32_t n_steps);
+int pedn_ctrl_read(pedn_sim* sim, double* actions, float* episode_rewards);
+void* pedn_ctrl_device_ptr(pedn_sim* sim, int32_t which);
+
 /* Origin demand drawn on the device for every replica at once -- the arrays DemandGenerator builds on the host
  * (src/LTM/od_manager.py:92-155) for the patterns generate_random_demand_params picks (src/utils/env_loader.py:183-222):
  *   pattern 0 gaussian_peaks: Poisson(base + peak * (bump(T/4) + bump(3T/4))), bump(c)(t) = exp(-(t-c)^2 / (2 (T/20)^2)), t < T

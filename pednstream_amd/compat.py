@@ -13,7 +13,7 @@ import types
 
 
 def install(force: bool = False):
-    from . import config, env_loader, network, od_manager, output_handler, path_finder, rl_env
+    from . import agents, config, env_loader, network, od_manager, output_handler, path_finder, rl_env
 
     def mod(name, **attrs):
         if name in sys.modules and not force:
@@ -44,4 +44,8 @@ def install(force: bool = False):
     rl = mod("rl", PedNetParallelEnv=rl_env.PedNetParallelEnv)
     rl.pz_pednet_env = mod("rl.pz_pednet_env", PedNetParallelEnv=rl_env.PedNetParallelEnv)
     rl.discovery = mod("rl.discovery", AgentManager=rl_env.AgentManager)
+    # `from rl.agents.rule_based import RuleBasedGaterAgent` (rl/train_rl.py, rl/evaluate_and_visualize.py)
+    rl.agents = mod("rl.agents")
+    rl.agents.rule_based = mod("rl.agents.rule_based", BaseAgent=agents.BaseAgent, RuleBasedGaterAgent=agents.RuleBasedGaterAgent,
+                               RuleBasedSeparatorAgent=agents.RuleBasedSeparatorAgent)
     return src

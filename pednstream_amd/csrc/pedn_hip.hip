@@ -20,6 +20,7 @@
 
 #include "../../include/pedn.h"
 #include "pedn_kernels.hpp"
+#include "pedn_ctrl.hpp"
 
 // ------------------------------------------------------------------------------------------------- host side
 static thread_local std::string g_last_error;
@@ -97,6 +98,11 @@ struct pedn_sim {
   double* d_pair_pod = nullptr;
   double* d_turn_tab = nullptr;
   RlView rl{};
+  // rule-based controllers (pedn_ctrl_*, pedn_ctrl.hpp): device rows of next actions and episode sums, moving-average buffers
+  CtrlView ctrl{};
+  bool ctrl_ready = false;
+  bool ctrl_any = false;   // some agent has a controller (else a controlled step applies no actions at all)
+  int ctrl_rows = 0;       // moving-average rows allocated in ctrl.ring
   bool rl_ready = false;
   bool node_lp = false;   // PEDN_NODE_OPTIMAL: the node LP instead of the classic rule
   bool rl_fold = false;   // gater-only agent set: pedn_rl_step lets node_kernel apply the actions (no launch of rl_apply_kernel)
@@ -1524,8 +1530,10 @@ static void prewarm_chains(pedn_sim* s) {
 
 // lazy (owner-wave plan, pedn_run): the link update of t is left to node_kernel<LU>(t + 1) -- or to flush_links -- and this step's
 // node_kernel performs the pending one of t - 1.
+// cv != nullptr (observe >= 0): the observations are those of the last sub-step of a controlled env step -- the controller twin of the
+// second launch (ctrl_link_turn_kernel) also computes the next actions and adds the rewards to the episode sums
 static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe = -1, bool* observed = nullptr,
-                       const double* fold_actions = nullptr, int half = -1, bool lazy = false) {
+                       const double* fold_actions = nullptr, int half = -1, bool lazy = false, const CtrlView* cv = nullptr) {
   // half = -1: the whole batch on the engine's stream; 0 / 1: the first / second half of the replicas on stream / stream2 (the
   // caller, pedn_run, launches both halves of a step and does the per-step bookkeeping once, after the second one)
   if (half < 0 && t - 1 > s->valid_hi) {   // a step that skips ahead after a lazy reset (chains: their callers do this before the fork)
@@ -1604,7 +1612,12 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
     // instantiation by (per-replica parameters, observations in the launch, recent-history mode)
 #define PEDN_LT(PR_, OBS_) do { if (v.hist) launch(link_turn_kernel<PR_, OBS_, true>, grid, block, 4, v, t, nlb, ntb, nth, q, acc); \
                                 else launch(link_turn_kernel<PR_, OBS_, false>, grid, block, 4, v, t, nlb, ntb, nth, q, acc); } while (0)
-    if (obs_fused) {
+    if (obs_fused && cv) {
+      if (v.pr) { if (v.hist) launch(ctrl_link_turn_kernel<true, true>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv);
+                  else launch(ctrl_link_turn_kernel<true, false>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv); }
+      else { if (v.hist) launch(ctrl_link_turn_kernel<false, true>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv);
+             else launch(ctrl_link_turn_kernel<false, false>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv); }
+    } else if (obs_fused) {
       if (v.pr) PEDN_LT(true, true);
       else PEDN_LT(false, true);
     } else {
@@ -2246,6 +2259,7 @@ int pedn_rl_configure(pedn_sim* s, const pedn_rl_desc* d, int32_t* n_actions, in
     v.rl_actions = nullptr;
   }
   s->rl_ready = true;
+  s->ctrl_ready = s->ctrl_any = false;   // controllers belong to an agent set: configure them again
   if (n_actions) *n_actions = A;
   if (n_obs) *n_obs = O;
   return PEDN_OK;
@@ -2299,7 +2313,8 @@ static int rl_fetch(pedn_sim* s, float* obs, float* rewards) {
   return PEDN_OK;
 }
 
-int pedn_rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards) {
+// (cv: the controller twin, see launch_step)
+static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards, const CtrlView* cv) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
   if (t < 0 || t > s->v.T1 - 1) return fail(s, PEDN_E_ARG, "time step outside 0..T");
@@ -2308,10 +2323,18 @@ int pedn_rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, floa
   if (t > s->valid_hi) catch_up(s, t);   // observations of a step that has not run read its rows as they were initialised
   DevView& v = s->v;
   RlView& q = s->rl;
-  if (v.hist) hipLaunchKernelGGL(rl_observe_kernel<true>, dim3((unsigned)q.n_agents * (unsigned)(v.RS / 64)), dim3(256), 0, s->stream, v, q, t, accumulate);
-  else hipLaunchKernelGGL(rl_observe_kernel<false>, dim3((unsigned)q.n_agents * (unsigned)(v.RS / 64)), dim3(256), 0, s->stream, v, q, t, accumulate);
+  const dim3 grid((unsigned)q.n_agents * (unsigned)(v.RS / 64));
+  if (cv) {
+    if (v.hist) hipLaunchKernelGGL(ctrl_observe_kernel<true>, grid, dim3(256), 0, s->stream, v, q, t, accumulate, *cv);
+    else hipLaunchKernelGGL(ctrl_observe_kernel<false>, grid, dim3(256), 0, s->stream, v, q, t, accumulate, *cv);
+  } else if (v.hist) hipLaunchKernelGGL(rl_observe_kernel<true>, grid, dim3(256), 0, s->stream, v, q, t, accumulate);
+  else hipLaunchKernelGGL(rl_observe_kernel<false>, grid, dim3(256), 0, s->stream, v, q, t, accumulate);
   HIP_TRY(s, hipGetLastError());
   return rl_fetch(s, obs, rewards);
+}
+
+int pedn_rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards) {
+  return rl_observe(s, t, accumulate, obs, rewards, nullptr);
 }
 
 int pedn_rl_fetch(pedn_sim* s, float* obs, float* rewards) {
@@ -2322,7 +2345,16 @@ int pedn_rl_fetch(pedn_sim* s, float* obs, float* rewards) {
   return rl_fetch(s, obs, rewards);
 }
 
+// cv: a controlled env step (pedn_ctrl_step) -- its last sub-step observes through the controller twins
+static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t t, int32_t action_gap, float* obs, float* rewards,
+                   const CtrlView* cv);
+
 int pedn_rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t t, int32_t action_gap, float* obs, float* rewards) {
+  return rl_step(s, actions, on_device, t, action_gap, obs, rewards, nullptr);
+}
+
+static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t t, int32_t action_gap, float* obs, float* rewards,
+                   const CtrlView* cv) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   if (action_gap < 1 || t < 1 || t + action_gap - 1 > s->v.T1 - 1) return fail(s, PEDN_E_ARG, "step range outside 1..T");
   int rc = PEDN_OK;
@@ -2379,17 +2411,18 @@ int pedn_rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t 
     bool observed = false;
     // (always two launches per env step: the observations are a second launch either way, and with the rows of t + 1 riding in it the
     // two launches are shorter than the single-launch / owner-wave plans -- profiles/r04_rl_small_batches.txt, r04_rl_owner.txt)
+    const CtrlView* ck = last ? cv : nullptr;
     if (two) {
       s->run_chains = 2;
-      for (int c = 0; c < 2; ++c) launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, c, false);
+      for (int c = 0; c < 2; ++c) launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, c, false, ck);
       s->run_chains = 1;
       if ((last && (obs || rewards)) || !observed) join_forked(s);
     } else
-      if ((rc = launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, -1, false)) != PEDN_OK) return rc;
+      if ((rc = launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, -1, false, ck)) != PEDN_OK) return rc;
       if (k == 0 && fold_stage && (rc = stage_commit(s, fold_stage)) != PEDN_OK) return rc;   // its only reader has been launched
     HIP_TRY(s, hipGetLastError());
     if (!observed) {
-      if ((rc = pedn_rl_observe(s, t + k, k > 0, last ? obs : nullptr, last ? rewards : nullptr)) != PEDN_OK) return rc;
+      if ((rc = rl_observe(s, t + k, k > 0, last ? obs : nullptr, last ? rewards : nullptr, ck)) != PEDN_OK) return rc;
     } else if (last && (obs || rewards)) {
       if ((rc = rl_fetch(s, obs, rewards)) != PEDN_OK) return rc;
     }
@@ -2536,6 +2569,113 @@ int pedn_rl_step_many(pedn_sim** sims, int32_t n, const double* actions, int32_t
 void* pedn_rl_device_ptr(pedn_sim* s, int32_t which) {
   if (!s || !s->rl_ready) return nullptr;
   return which == 0 ? (void*)s->rl.actions : which == 1 ? (void*)s->rl.obs : which == 2 ? (void*)s->rl.rew : nullptr;
+}
+
+// ---- rule-based controllers on the device (pedn_ctrl.hpp) ----------------------------------------------------------------------
+int pedn_ctrl_configure(pedn_sim* s, const int32_t* kind, const int32_t* window, const int32_t* wide, const float* threshold,
+                        const double* width, const float* open) {
+  if (!s || !kind || !window || !wide || !threshold || !width || !open) return fail(s, PEDN_E_ARG, "null argument");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);
+  const RlView& q = s->rl;
+  std::vector<int32_t> type((size_t)q.n_agents);
+  HIP_TRY(s, hipMemcpy(type.data(), q.agent_type, type.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<CtrlAgent> ag((size_t)q.n_agents);
+  int rows = 0;
+  bool any = false;
+  for (int a = 0; a < q.n_agents; ++a) {
+    CtrlAgent& c = ag[a];
+    c.kind = kind[a];
+    if (c.kind < 0 || c.kind > 2) return fail(s, PEDN_E_ARG, "controller kind must be 0 (none), 1 (gater rule) or 2 (separator rule)");
+    if (c.kind == 1 && type[a] != 1) return fail(s, PEDN_E_ARG, "agent " + std::to_string(a) + " is not a gater");
+    if (c.kind == 1 && q.obs_mode != 2) return fail(s, PEDN_E_ARG, "the gater rule reads densities: obs_mode must be option2");
+    if (c.kind == 2 && type[a] != 0) return fail(s, PEDN_E_ARG, "agent " + std::to_string(a) + " is not a separator");
+    c.window = c.kind == 2 ? window[a] : 0;
+    if (c.window < 0 || c.window > PEDN_CTRL_MAX_WINDOW)
+      return fail(s, PEDN_E_ARG, "moving-average window outside 0.." + std::to_string(PEDN_CTRL_MAX_WINDOW));
+    c.wide = wide[a] != 0;
+    c.ring = rows;
+    rows += c.window;
+    c.thr = threshold[a];
+    c.w64 = width[a];
+    c.w32 = (float)width[a];
+    any = any || c.kind != 0;
+  }
+  const DevView& v = s->v;
+  CtrlView& cv = s->ctrl;
+  int rc;
+  // (sizes depend only on the agent set: allocated once per pedn_rl_configure, the moving-average rows grow when a call needs more)
+  static_assert(sizeof(CtrlAgent) == 32, "CtrlAgent is uploaded as bytes");
+  if (!cv.actions || s->ctrl_ready == false) {
+    CtrlAgent* d_ag;
+    float* d_open;
+    if ((rc = dalloc(s, (size_t)q.n_agents, &d_ag)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)q.A, &d_open)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)v.R * q.A, &cv.actions)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)v.R * q.n_agents, &cv.ep)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)q.n_agents * v.RS, &cv.count)) != PEDN_OK) return rc;
+    cv.agent = d_ag;
+    cv.open = d_open;
+    cv.ring = nullptr;
+    s->ctrl_rows = 0;
+  }
+  if (rows > s->ctrl_rows) {
+    if ((rc = dalloc(s, (size_t)rows * v.RS, &cv.ring)) != PEDN_OK) return rc;
+    s->ctrl_rows = rows;
+  }
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  HIP_TRY(s, hipMemcpy(const_cast<CtrlAgent*>(cv.agent), ag.data(), ag.size() * sizeof(CtrlAgent), hipMemcpyHostToDevice));
+  HIP_TRY(s, hipMemcpy(const_cast<float*>(cv.open), open, (size_t)q.A * sizeof(float), hipMemcpyHostToDevice));
+  std::vector<double> nan((size_t)v.R * q.A, __builtin_nan(""));   // no action until the first observation decides one
+  HIP_TRY(s, hipMemcpy(cv.actions, nan.data(), nan.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(s, hipMemset(cv.ep, 0, (size_t)v.R * q.n_agents * sizeof(float)));
+  HIP_TRY(s, hipMemset(cv.count, 0, (size_t)q.n_agents * v.RS * sizeof(int32_t)));   // every moving-average buffer empty
+  cv.RS = v.RS;
+  cv.ep_mode = 1;
+  s->ctrl_ready = true;
+  s->ctrl_any = any;
+  return PEDN_OK;
+}
+
+int pedn_ctrl_observe(pedn_sim* s, int32_t t) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ctrl_ready) return fail(s, PEDN_E_ARG, "pedn_ctrl_configure has not been called");
+  CtrlView cv = s->ctrl;
+  cv.ep_mode = 2;
+  return rl_observe(s, t, 0, nullptr, nullptr, &cv);
+}
+
+int pedn_ctrl_step(pedn_sim* s, int32_t t, int32_t action_gap, int32_t n_steps) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ctrl_ready) return fail(s, PEDN_E_ARG, "pedn_ctrl_configure has not been called");
+  if (n_steps < 0 || action_gap < 1 || t < 1 || t + (int64_t)n_steps * action_gap - 1 > s->v.T1 - 1)
+    return fail(s, PEDN_E_ARG, "step range outside 1..T");
+  CtrlView cv = s->ctrl;
+  cv.ep_mode = 1;
+  for (int i = 0; i < n_steps; ++i) {
+    const int rc = rl_step(s, s->ctrl_any ? s->ctrl.actions : nullptr, 1, t + i * action_gap, action_gap, nullptr, nullptr, &cv);
+    if (rc != PEDN_OK) return rc;
+  }
+  return PEDN_OK;
+}
+
+int pedn_ctrl_read(pedn_sim* s, double* actions, float* episode_rewards) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ctrl_ready) return fail(s, PEDN_E_ARG, "pedn_ctrl_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);
+  const size_t R = (size_t)s->v.R;
+  if (actions) HIP_TRY(s, hipMemcpyAsync(actions, s->ctrl.actions, R * s->rl.A * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  if (episode_rewards)
+    HIP_TRY(s, hipMemcpyAsync(episode_rewards, s->ctrl.ep, R * s->rl.n_agents * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  return PEDN_OK;
+}
+
+void* pedn_ctrl_device_ptr(pedn_sim* s, int32_t which) {
+  if (!s || !s->ctrl_ready) return nullptr;
+  return which == 0 ? (void*)s->ctrl.actions : which == 1 ? (void*)s->ctrl.ep : nullptr;
 }
 
 int pedn_device_math(int32_t device, int32_t op, int32_t n, const double* a, const double* b, uint64_t seed, double* out) {

@@ -1384,11 +1384,20 @@ __global__ void rl_apply_kernel(DevView v, RlView q) {
 // arithmetic (speed_calc with the same Philox key), so the parts of that launch stay independent.
 // lds: 3 * PEDN_MAX_DEGREE * 64 floats of the workgroup's LDS
 #define PEDN_OBS_LDS_FLOATS (3 * PEDN_MAX_DEGREE * 64)
-template <bool FUSED, bool HIST>
-__device__ __forceinline__ void rl_observe_body(const DevView& v, const RlView& q, int t, int accumulate, unsigned block, float* lds) {
+// CTRL (the controller twins ctrl_observe_kernel / ctrl_link_turn_kernel, pedn_ctrl.hpp): wave 0 also adds the reward to the episode sums
+// and computes the agent's next action from the observation it has just written; the gate widths take a fourth LDS array
+#define PEDN_CTRL_LDS_FLOATS (4 * PEDN_MAX_DEGREE * 64)
+struct CtrlView;
+template <bool CTRL>
+__device__ __forceinline__ void ctrl_decide(const CtrlView& cv, const RlView& q, int ag, int type, int n, int r, const float* o,
+                                            const float (*sD)[64], const float (*sG)[64], int lane, float reward_sum);
+template <bool FUSED, bool HIST, bool CTRL = false>
+__device__ __forceinline__ void rl_observe_body(const DevView& v, const RlView& q, int t, int accumulate, unsigned block, float* lds,
+                                                const CtrlView* cv = nullptr) {
   float (*const sT)[64] = reinterpret_cast<float (*)[64]>(lds);
   float (*const sD)[64] = reinterpret_cast<float (*)[64]>(lds + PEDN_MAX_DEGREE * 64);
   float (*const sKc)[64] = reinterpret_cast<float (*)[64]>(lds + 2 * PEDN_MAX_DEGREE * 64);
+  float (*const sG)[64] = reinterpret_cast<float (*)[64]>(lds + 3 * PEDN_MAX_DEGREE * 64);   // (CTRL only)
   const int RS = v.RS, L = v.L, Lall = v.Lall;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)(threadIdx.x & 63);
@@ -1455,6 +1464,7 @@ __device__ __forceinline__ void rl_observe_body(const DevView& v, const RlView& 
       sT[w][lane] = tt_l + tt_r;  // T_ell + T_ell_reverse, float32 (pz_pednet_env.py:566)
       sD[w][lane] = dens;
       sKc[w][lane] = (float)P.kc;
+      if (CTRL) sG[w][lane] = gate;
     }
   }
   __syncthreads();
@@ -1482,6 +1492,7 @@ __device__ __forceinline__ void rl_observe_body(const DevView& v, const RlView& 
     float* rw = q.rew + (size_t)r * q.n_agents + ag;
     const float add = rewarded ? reward : 0.0f;
     *rw = (accumulate && rewarded) ? *rw + add : (accumulate ? *rw : add);
+    if (CTRL) ctrl_decide<CTRL>(*cv, q, ag, type, n, r, o, sD, sG, lane, *rw);
   }
 }
 
@@ -1503,12 +1514,10 @@ __global__ __launch_bounds__(256) void rl_observe_kernel(DevView v, RlView q, in
 // when the first workgroups retire: with every turning-fraction workgroup in front, a third of the link update started only after
 // the short rows had finished and ended long after the long rows (delft x 1024: 20.8 us for 12 us of critical path).
 // (OBS = false: the instantiation ordinary stepping uses carries neither the LDS nor the registers of the third part)
-template <bool PR, bool OBS, bool HIST, bool CLK = false>
-__global__ __launch_bounds__(256, 4) void link_turn_kernel(DevView v, int t, unsigned n_link_blocks, unsigned n_tp_blocks, unsigned n_tp_heavy, RlView q,
-                                                           int accumulate) {
-  // one LDS buffer for whichever part this workgroup is (the observation part needs 6 KB of the turning fractions' 35.5 KB)
-  __shared__ double lds[PEDN_TF_LDS_DOUBLES];
-  static_assert(sizeof(double) * PEDN_TF_LDS_DOUBLES >= sizeof(float) * PEDN_OBS_LDS_FLOATS, "observation rows must fit");
+// (CTRL: the part of ctrl_link_turn_kernel, pedn_ctrl.hpp -- the observation blocks also run the agents' controllers)
+template <bool PR, bool OBS, bool HIST, bool CLK, bool CTRL>
+__device__ __forceinline__ void link_turn_body(DevView& v, int t, unsigned n_link_blocks, unsigned n_tp_blocks, unsigned n_tp_heavy, const RlView& q,
+                                               int accumulate, double* lds, const CtrlView* cv) {
   // role of this workgroup (one call site per part: each is inlined once)
   const unsigned b = blockIdx.x;
   if (CLK) {   // device clock (see node_clock): this launch runs the step node_kernel left in clock[1]
@@ -1535,11 +1544,20 @@ __global__ __launch_bounds__(256, 4) void link_turn_kernel(DevView v, int t, uns
     if (PR) link_pr_body<true, HIST>(v, t, gid);
     else link_body<HIST>(v, t, gid);
   } else if (OBS) {
-    rl_observe_body<true, HIST>(v, q, t, accumulate, b - n_link_blocks - n_tp_blocks, reinterpret_cast<float*>(lds));
+    rl_observe_body<true, HIST, CTRL>(v, q, t, accumulate, b - n_link_blocks - n_tp_blocks, reinterpret_cast<float*>(lds), cv);
   }
 #ifdef PEDN_PHASE_PROFILE
   if ((threadIdx.x & 63) == 0 && b < PEDN_LT_BLOCKS) atomicMax(&g_lt_time[b * 4 + 2], (unsigned long long)wall_clock64());
 #endif
+}
+
+template <bool PR, bool OBS, bool HIST, bool CLK = false>
+__global__ __launch_bounds__(256, 4) void link_turn_kernel(DevView v, int t, unsigned n_link_blocks, unsigned n_tp_blocks, unsigned n_tp_heavy, RlView q,
+                                                           int accumulate) {
+  // one LDS buffer for whichever part this workgroup is (the observation part needs 6 KB of the turning fractions' 35.5 KB)
+  __shared__ double lds[PEDN_TF_LDS_DOUBLES];
+  static_assert(sizeof(double) * PEDN_TF_LDS_DOUBLES >= sizeof(float) * PEDN_OBS_LDS_FLOATS, "observation rows must fit");
+  link_turn_body<PR, OBS, HIST, CLK, false>(v, t, n_link_blocks, n_tp_blocks, n_tp_heavy, q, accumulate, lds, nullptr);
 }
 
 // ---- state initialisation / host <-> device helpers ---------------------------------------------------------

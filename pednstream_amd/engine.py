@@ -181,6 +181,11 @@ def _load():
         "pedn_metrics_begin": (C.c_int, [P, _I32P, _I32P, _I32P, C.c_int32, _I32P, _I32P, C.c_int32, C.c_double]),
         "pedn_metrics_accumulate": (C.c_int, [P, C.c_int32, C.c_int32]),
         "pedn_metrics_read": (C.c_int, [P, _F64P, _F64P, _F64P]),
+        "pedn_ctrl_configure": (C.c_int, [P, _I32P, _I32P, _I32P, _F32P, _F64P, _F32P]),
+        "pedn_ctrl_observe": (C.c_int, [P, C.c_int32]),
+        "pedn_ctrl_step": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32]),
+        "pedn_ctrl_read": (C.c_int, [P, _F64P, _F32P]),
+        "pedn_ctrl_device_ptr": (C.c_void_p, [P, C.c_int32]),
     }
     # the version first: a stale or alternate library (PEDN_HIP_LIB) must fail with this message, not with an AttributeError on a symbol
     lib.pedn_abi_version.restype, lib.pedn_abi_version.argtypes = C.c_int, []
@@ -210,7 +215,8 @@ EXPORTS = ["pedn_abi_version", "pedn_last_error", "pedn_create", "pedn_destroy",
            "pedn_rl_apply_actions", "pedn_rl_observe", "pedn_rl_fetch", "pedn_rl_step_many", "pedn_rl_step", "pedn_rl_device_ptr", "pedn_get_widths", "pedn_set_link_params",
            "pedn_set_od_weights_per_replica", "pedn_get_od_weights_per_replica", "pedn_get_link_params", "pedn_randomize_scenarios", "pedn_reset_widths",
            "pedn_flush", "pedn_rl_clock_begin", "pedn_rl_step_clocked", "pedn_rl_clock_end", "pedn_rl_clocked", "pedn_rl_clock_signature",
-           "pedn_metrics_begin", "pedn_metrics_accumulate", "pedn_metrics_read"]
+           "pedn_metrics_begin", "pedn_metrics_accumulate", "pedn_metrics_read",
+           "pedn_ctrl_configure", "pedn_ctrl_observe", "pedn_ctrl_step", "pedn_ctrl_read", "pedn_ctrl_device_ptr"]
 
 
 def _p(a, dtype=np.float64):
@@ -632,6 +638,33 @@ class Engine:
         ag = np.empty((self.n_replicas, n_agents, 3))
         self._ck(self._lib.pedn_metrics_read(self._h, _p(out), _p(al) if n_agents else None, _p(ag) if n_agents else None))
         return out, al, ag
+
+    # -- rule-based controllers (include/pedn.h: pedn_ctrl_*; VecPedNetEnv.set_controllers builds the arguments)
+    CTRL_MAX_WINDOW = 32
+
+    def ctrl_configure(self, kind, window, wide, threshold, width, open_width):
+        a = [np.ascontiguousarray(x, dtype=np.int32) for x in (kind, window, wide)]
+        thr = np.ascontiguousarray(threshold, dtype=np.float32)
+        w = np.ascontiguousarray(width, dtype=np.float64)
+        op = np.ascontiguousarray(open_width, dtype=np.float32)
+        assert all(x.shape == (self.rl_n_agents,) for x in a + [thr, w]) and op.shape == (self.rl_n_actions,)
+        rc = self._lib.pedn_ctrl_configure(self._h, _p(a[0], np.int32), _p(a[1], np.int32), _p(a[2], np.int32), _p(thr, np.float32), _p(w),
+                                           _p(op, np.float32))
+        if rc < 0:
+            raise ValueError(self._lib.pedn_last_error(self._h).decode())
+
+    def ctrl_observe(self, t):
+        self._ck(self._lib.pedn_ctrl_observe(self._h, int(t)))
+
+    def ctrl_step(self, t, action_gap, n_steps):
+        self._ck(self._lib.pedn_ctrl_step(self._h, int(t), int(action_gap), int(n_steps)))
+
+    def ctrl_read(self, actions=True, episode_rewards=True):
+        """(action rows [n_replicas, n_actions] float64 or None, episode sums [n_replicas, n_agents] float32 or None)."""
+        a = np.empty((self.n_replicas, self.rl_n_actions)) if actions else None
+        e = np.empty((self.n_replicas, self.rl_n_agents), dtype=np.float32) if episode_rewards else None
+        self._ck(self._lib.pedn_ctrl_read(self._h, None if a is None else _p(a), None if e is None else _p(e, np.float32)))
+        return a, e
 
     def device_ptr(self, field):
         cols, stride = C.c_int64(), C.c_int64()

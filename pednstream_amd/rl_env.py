@@ -200,6 +200,8 @@ class VecPedNetEnv:
         self._metrics = None
         self._folded = 0
         self._rows = None
+        self._controllers = None       # set_controllers: {agent_id: agent or None}
+        self._ctrl_reset = False
 
     # ------------------------------------------------------------------------------------------------ API
     AUTO_VECTORISED_FROM = 65      # randomize(mode="auto"): batches of this many envs and more draw their scenarios on the device
@@ -272,8 +274,113 @@ class VecPedNetEnv:
                 self._metrics.restart()
             self._folded = 0               # rows [0, _folded) are in the accumulators; row 0 (the reset's) is pending now
             self._fold_pending()
-        obs, _ = eng.rl_observe(self.sim_step, accumulate=False)
+        if self._controllers is not None:      # the reset observation also decides the first actions and starts the episode sums
+            eng.ctrl_observe(self.sim_step)
+            obs, _ = eng.rl_fetch()
+            self._ctrl_reset = True
+        else:
+            obs, _ = eng.rl_observe(self.sim_step, accumulate=False)
         return obs, {}
+
+    # ------------------------------------------------------------------------------------------------ rule-based controllers
+    def set_controllers(self, controllers):
+        """Run the reference's rule-based agents on the device for every env (pednstream_amd/csrc/pedn_ctrl.hpp): ``{agent_id:
+        RuleBasedGaterAgent | RuleBasedSeparatorAgent | None}``; agents not named have no controller (no action, like an agent missing
+        from an action dict).  A gater agent's links must be this env's links of that agent and the env must observe ``option2``; a
+        separator agent's width must be a Python number or a numpy float64.  The moving-average buffers start empty and then belong to
+        this configuration: ``reset`` keeps them, like the agent object's own buffer (the object itself is not updated).  Call ``reset``
+        before ``step_controlled``."""
+        from .agents import RuleBasedGaterAgent, RuleBasedSeparatorAgent
+
+        eng = self.network.engine()
+        n = len(self.possible_agents)
+        kind, window, wide = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        thr, width, open_w = np.zeros(n, np.float32), np.zeros(n), np.zeros(self.n_actions, np.float32)
+        for aid in controllers:
+            if aid not in self.action_slices:
+                raise ValueError(f"Unknown agent: {aid}")
+        for i, aid in enumerate(self.possible_agents):
+            agent = controllers.get(aid)
+            if agent is None:
+                continue
+            kind_of = self.agent_manager.get_agent_type(aid)
+            if isinstance(agent, RuleBasedGaterAgent):
+                if kind_of != "gate":
+                    raise ValueError(f"{aid} is not a gater agent")
+                if self.obs_mode != "option2":
+                    raise ValueError(f"RuleBasedGaterAgent reads densities: the env must observe 'option2', not {self.obs_mode!r}")
+                mine = [l.link_id for l in self.agent_manager.get_gater_outgoing_links(aid)]
+                theirs = [getattr(l, "link_id", None) for l in agent.outgoing_links]
+                if theirs != mine:
+                    raise ValueError(f"{aid}: the agent's outgoing links {theirs} are not the env's {mine}")
+                kind[i], thr[i] = 1, np.float32(agent.threshold_density)
+                open_w[self.action_slices[aid]] = np.array([l.width for l in agent.outgoing_links], dtype=np.float32)
+            elif isinstance(agent, RuleBasedSeparatorAgent):
+                if kind_of != "sep":
+                    raise ValueError(f"{aid} is not a separator agent")
+                w = agent.road_width
+                if isinstance(w, np.floating) and not isinstance(w, np.float64) or not isinstance(w, (int, float, np.integer)):
+                    raise ValueError(f"{aid}: the separator width must be a Python number or a numpy float64, got {type(w).__name__}")
+                if agent.use_smoothing:
+                    size = agent.buffer_size
+                    if not isinstance(size, (int, np.integer)) or not 1 <= size <= eng.CTRL_MAX_WINDOW:
+                        raise ValueError(f"{aid}: buffer_size must be an integer in 1..{eng.CTRL_MAX_WINDOW}, got {size!r}")
+                    if agent._link_inflow_buffer:
+                        raise ValueError(f"{aid}: the agent's moving-average buffer is not empty; the device starts from an empty one")
+                    window[i] = size
+                kind[i], width[i], wide[i] = 2, float(w), int(isinstance(w, np.float64))
+            else:
+                raise TypeError(f"{aid}: only RuleBasedGaterAgent / RuleBasedSeparatorAgent run on the device (a torch policy goes "
+                                f"through capture()), got {type(agent).__name__}")
+        self.network._flush()
+        eng.ctrl_configure(kind, window, wide, thr, width, open_w)
+        self._controllers = {aid: controllers.get(aid) for aid in self.possible_agents}
+        self._ctrl_reset = False
+
+    def step_controlled(self, n_env_steps=None, fetch=True):
+        """``n_env_steps`` env steps (default: to the end of the episode) whose actions the controllers of ``set_controllers`` decide
+        on the device from each step's observation; no host round trip between them.  Returns ``(obs, rewards, terminated)`` of the
+        last one like ``step`` (``fetch=False``: ``(None, None, terminated)``, the buffers stay on the device -- ``device_views``)."""
+        if self._controllers is None:
+            raise RuntimeError("call set_controllers() first")
+        if not self._ctrl_reset:
+            raise RuntimeError("call reset() after set_controllers(): the reset observation decides the first actions")
+        left = (self.simulation_steps - self.sim_step + 1) // self.action_gap
+        n = left if n_env_steps is None else int(n_env_steps)
+        if left < 1 or n > left:
+            raise IndexError("episode is over; call reset()" if left < 1 else f"only {left} env steps are left in the episode")
+        if self._tracked_piece() is not None:
+            raise RuntimeError("step_controlled does not track metrics in recent-history mode with an action_gap longer than the history "
+                               "rings; use history='full'")
+        eng = self.network._flush()
+        # tracked metrics with recent history: fold every env step's rows before they leave the rings
+        chunk = n if self._metrics is None or self._ring_rows() > self.simulation_steps else 1
+        done = 0
+        while done < n:
+            k = min(chunk, n - done)
+            eng.ctrl_step(self.sim_step, self.action_gap, k)
+            self.sim_step += k * self.action_gap
+            done += k
+            self._fold_pending()
+        self.network.current_step = self.sim_step - 1
+        self.network._widths_stale = True
+        obs = rew = None
+        if fetch:
+            obs, rew = eng.rl_fetch()
+        return obs, rew, (self.sim_step - 1) >= self.simulation_steps
+
+    def episode_rewards(self):
+        """[n_envs, n_agents] float32: every agent's rewards summed over the env steps since the last reset, in float32 like the
+        reference's evaluation loop (rl/rl_utils.py:1544,1593-1599).  Kept by ``step_controlled``."""
+        if self._controllers is None:
+            raise RuntimeError("call set_controllers() first")
+        return self.network.engine().ctrl_read(actions=False)[1]
+
+    def controller_actions(self):
+        """[n_envs, n_actions] float64: the actions the controllers decided for the next env step (NaN: no controller)."""
+        if self._controllers is None:
+            raise RuntimeError("call set_controllers() first")
+        return self.network.engine().ctrl_read(episode_rewards=False)[0]
 
     def _fold_pending(self, now=False):
         """Fold the written rows not yet in the tracked metrics ([_folded, sim_step)) -- ``now``, or when the next env step would push
