@@ -553,6 +553,11 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
 
   if (m->history_mode != PEDN_HIST_FULL && m->history_mode != PEDN_HIST_RECENT) return fail(nullptr, PEDN_E_ARG, "unknown history_mode");
   if (m->node_model != PEDN_NODE_CLASSIC && m->node_model != PEDN_NODE_OPTIMAL) return fail(nullptr, PEDN_E_ARG, "unknown node_model");
+  // node_step forms the element offset of a column inside a history row, col * RS + r0, and the elements of a row in 32 bits (rowq / rowd in
+  // pedn_kernels.hpp).  A row of 2^31 elements would be 16 GB of every binary64 field per step: no full-record or ring allocation that fits a
+  // device comes near it, so such a batch is refused here instead of being given a 64-bit path of its own.
+  if (((size_t)L + (size_t)m->n_vlinks) * (((size_t)n_replicas + 127) / 128 * 128) >= ((size_t)1 << 31))
+    return fail(nullptr, PEDN_E_ARG, "links x replicas must stay below 2^31 (one history row)");
 
   HIP_TRY(nullptr, hipSetDevice(device));
   pedn_sim* s = new pedn_sim();
@@ -1022,6 +1027,8 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     v.quiet_npos = (int32_t)rec.size();
     if (s->quiet) {   // [2][slot positions][RS / 64][own | inbox]: melbourne x 1024 ~ 0.3 MB
       const size_t nq = (size_t)2 * rec.size() * (size_t)(v.RS / 64) * 2;
+      // (node_step indexes the words of one step, nq / 2, in 32 bits)
+      if (nq / 2 >= ((size_t)1 << 31)) TRY(fail(s, PEDN_E_ARG, "too many quiet words"));
       TRY(dalloc(s, nq, &s->d_quiet));
       HIP_TRY(s, hipMemset(s->d_quiet, 0, nq * sizeof(uint32_t)));
     }
@@ -1408,6 +1415,32 @@ int pedn_get_widths(pedn_sim* s, int32_t which, double* values) {
   return PEDN_OK;
 }
 
+// Row bases of a node-kernel launch of step t (DevView.rb, node_step): the rows of t, t - 1, t - 2 (wrapped as wrap_idx does) and
+// t - 1 - W of the fields node_step addresses at a row every wave shares, mapped to their place in a full record or a ring as R64 / R32
+// do in the kernels.  A row the step cannot touch (t - 1 - W < 0: the window has not filled, t - 2 of a step the LU kernel never runs) gets
+// the field's first row.  Called when vn.quiet is what the launch will carry: quiet_rd / quiet_wr are the halves of steps t - 1 and t.
+static void row_bases(DevView& vn, int t) {
+  const size_t n64 = (size_t)vn.L * vn.RS, n64a = (size_t)vn.Lall * vn.RS;   // elements of a row: inflow .. cumulative_outflow hold the virtual links too
+  auto wrap = [&](int i) { if (i < 0) i += vn.T1; return i < 0 || i >= vn.T1 ? 0 : i; };
+  auto r64 = [&](int F, int i) { return (char*)(vn.f64[F] + (size_t)(vn.hist ? (i & vn.m64[F]) : i) * (F < F_S ? n64a : n64)); };
+  auto r32 = [&](int G, int i) { return (char*)(vn.f32[G] + (size_t)(vn.hist ? (i & vn.m32[G]) : i) * n64); };
+  const int tp = wrap(t - 1), tq = wrap(t - 2), tw = t - 1 - vn.W >= 0 ? wrap(t - 1 - vn.W) : 0, tt = wrap(t);
+  vn.rb[RB_IN_P] = r64(F_IN, tp); vn.rb[RB_IN_T] = r64(F_IN, tt);
+  vn.rb[RB_OUT_P] = r64(F_OUT, tp); vn.rb[RB_OUT_T] = r64(F_OUT, tt);
+  vn.rb[RB_CI_P] = r64(F_CI, tp); vn.rb[RB_CI_T] = r64(F_CI, tt);
+  vn.rb[RB_CO_P] = r64(F_CO, tp); vn.rb[RB_CO_T] = r64(F_CO, tt);
+  vn.rb[RB_S_Q] = r64(F_S, tq); vn.rb[RB_S_P] = r64(F_S, tp);
+  vn.rb[RB_R_Q] = r64(F_R, tq); vn.rb[RB_R_P] = r64(F_R, tp);
+  vn.rb[RB_GATE_P] = r64(F_GATE, tp);
+  vn.rb[RB_N_Q] = r32(G_N, tq); vn.rb[RB_N_P] = r32(G_N, tp);
+  vn.rb[RB_K_P] = r32(G_K, tp); vn.rb[RB_V_P] = r32(G_V, tp); vn.rb[RB_TT_P] = r32(G_TT, tp);
+  vn.rb[RB_LF_P] = r32(G_LF, tp); vn.rb[RB_ATT_P] = r32(G_ATT, tp);
+  vn.rb[RB_TT_W] = r32(G_TT, tw);
+  const size_t half = (size_t)vn.quiet_npos * (size_t)(vn.RS / 64) * 2;   // [slot position][replica group][own | inbox] of one step
+  vn.quiet_rd = vn.quiet ? vn.quiet + (size_t)((t - 1) & 1) * half : nullptr;
+  vn.quiet_wr = vn.quiet ? vn.quiet + (size_t)(t & 1) * half : nullptr;
+}
+
 // lu: the instantiation whose slot waves perform the link update of step t-1 themselves (node_kernel<..., LU = true>)
 // tf: ... and compute their own rows of turning fractions (node_kernel<.., TF> / with helper waves node_kernel_h)
 static node_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf) {
@@ -1512,6 +1545,7 @@ static void prewarm_chains(pedn_sim* s) {
   if (s->chains < 2) return;
   DevView v = s->v;
   v.slot_rec = s->d_slot_rec + (size_t)s->n_blocks * 8;   // the idle block
+  row_bases(v, 2);
   DevView vl = s->v;
   vl.n_pairs_corr = 0;
   vl.n_trow = 0;
@@ -1569,6 +1603,7 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   vn.zg64 = zero_gate(s, zhw64, t);
   vn.zg32 = lu ? zero_gate(s, zhw32, t - 1) : 0;
   if (vn.zg64 || vn.zg32) ++s->zgated;
+  row_bases(vn, t);
   const unsigned rgroups = (unsigned)(v.subRS / 64);
   // the turning fractions of t + 1 ride in the launch behind node_kernel(t) -- except behind the last step of the horizon, where
   // pair_pod / turn_tab have no row T + 1 to read (they hold T + 1 rows, 0..T) and nothing would consume the result

@@ -62,6 +62,27 @@ template <typename T>
 __device__ __forceinline__ T* rowp(T* base, int t, int col, int cols, int RS, int r0) {
   return base + (((size_t)t * (size_t)cols + (size_t)col) * (size_t)RS + (size_t)r0);
 }
+// Row bases (DevView.rb): where the host knew the launch's step index, the start of row RB_k arrives in the kernel-argument segment and
+// the wave adds the element offset `off` = col * RS + r0 of its segment, computed once per column -- a scalar load and one 64-bit add per
+// access instead of the multiply chain above.  RB = false (the clocked step, whose t the host does not see): the chain, as before.
+template <bool RB, typename T>
+__device__ __forceinline__ T* rowq(const DevView& v, int k, uint32_t off, T* base, int t, int col, int cols, int RS, int r0) {
+  if constexpr (RB) return reinterpret_cast<T*>(v.rb[k]) + off;
+  else return rowp(base, t, col, cols, RS, r0);
+}
+// ... a row index t >= 0 that depends on data (per lane or per link): t * rstr (the elements of a row, < 2^31: pedn_create) + off, one
+// 64-bit multiply-add
+template <typename T>
+__device__ __forceinline__ T* rowd(T* base, int t, uint32_t rstr, uint32_t off) {
+  return base + ((size_t)(uint32_t)t * (size_t)rstr + (size_t)off);
+}
+// ... lane `lane` (replica r) of column col of a plain [cols][RS] array.  (Not the running sum: read in the batch and written behind the speed,
+// its address in this form stays alive in between and node_kernel<LU> answers with 4 vector spills.)
+template <bool RB, typename T>
+__device__ __forceinline__ T& colr(T* base, uint32_t off, int lane, int col, int RS, int r) {
+  if constexpr (RB) return (base + off)[lane];
+  else return base[(size_t)col * RS + r];
+}
 __device__ __forceinline__ float clip01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
 __device__ __forceinline__ double clip_d(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }  // np.clip
 // Link parameters as seen by one lane: the shared record, or (PR) the replica's own k_critical / k_jam / free-flow speed
@@ -110,8 +131,11 @@ struct SlotIn {
 // ci_look = cumulative_inflow[max(0, t' + 1 - tau)] of the link, loaded by the caller (tau from x.att_in as below) so that the load is
 // in flight while the caller draws the receiving side's binomial
 // vhi: DevView.valid_hi as it stands for THIS step (the host's value, or the device clock's -- see node_kernel)
-template <bool HIST>
-__device__ double send_flow(const DevView& v, const LinkP& P, int l, int tp, int r, const SlotIn& x, double ci_look, const int vhi, uint32_t& fl) {
+// RB: the diffusion look-backs are addressed as rowd(.., lrs + r) with lrs = l * RS (the lane's element offset inside a row is formed from r
+// where it is used: one more vector register alive across the binomials is one too many for node_kernel)
+template <bool HIST, bool RB = false>
+__device__ double send_flow(const DevView& v, const LinkP& P, int l, int tp, int r, const SlotIn& x, double ci_look, const int vhi, uint32_t& fl,
+                            const uint32_t lrs = 0u) {
   const int RS = v.RS, T1 = v.T1;
   const float nself = x.n_in, nrev = x.n_out, kk = x.k_in, att = x.att_in;
   float dens = P.sep ? kk : (nself + nrev) / P.area32;
@@ -133,8 +157,14 @@ __device__ double send_flow(const DevView& v, const LinkP& P, int l, int tp, int
     if (free_flow) {
       const double* in = v.f64[F_IN];
       const int w0 = wrap_idx(tp - tau, T1, fl), w1 = wrap_idx(tp - tau - 1, T1, fl), w2 = wrap_idx(tp - tau - 2, T1, fl), w3 = wrap_idx(tp - tau - 3, T1, fl);
-      i0 = in[at(w0, l, v.Lall, RS, r)], i1 = in[at(w1, l, v.Lall, RS, r)];
-      i2 = in[at(w2, l, v.Lall, RS, r)], i3 = in[at(w3, l, v.Lall, RS, r)];
+      if constexpr (RB) {
+        const uint32_t rstr = (uint32_t)v.Lall * (uint32_t)RS, lo = lrs + (uint32_t)r;
+        i0 = *rowd(in, w0, rstr, lo), i1 = *rowd(in, w1, rstr, lo);
+        i2 = *rowd(in, w2, rstr, lo), i3 = *rowd(in, w3, rstr, lo);
+      } else {
+        i0 = in[at(w0, l, v.Lall, RS, r)], i1 = in[at(w1, l, v.Lall, RS, r)];
+        i2 = in[at(w2, l, v.Lall, RS, r)], i3 = in[at(w3, l, v.Lall, RS, r)];
+      }
       // lazy reset: a wrapped index lands in a row of the FUTURE, which holds the last episode's value instead of the untouched 0
       i0 = w0 > vhi ? 0.0 : i0; i1 = w1 > vhi ? 0.0 : i1; i2 = w2 > vhi ? 0.0 : i2; i3 = w3 > vhi ? 0.0 : i3;
     }
@@ -763,12 +793,16 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
   constexpr bool QU = LU && !TF && !CLK;
   // zero elision (DevView.zg64 / zg32): not in the clocked step, whose step index the host does not see, nor in recent-history mode
   constexpr bool ZE = !CLK && !HIST;
-  const size_t qgroup = (size_t)(RS >> 6), qslot = (size_t)by * 8 + wave, qrg = (size_t)(r0 >> 6);
+  // row bases (DevView.rb, rowq): wherever the host knew t
+  constexpr bool RB = !CLK;
+  // the slot's pair of quiet words inside one step's half of DevView.quiet (< 2^31 words: pedn_create)
+  const uint32_t qgroup = (uint32_t)(RS >> 6), qrg = (uint32_t)(r0 >> 6);
+  const uint32_t qoff = (((uint32_t)by * 8u + (uint32_t)wave) * qgroup + qrg) << 1;
   // lean quiet step (QL; DevView.quiet_lean): the column pass and the row sums of a slot whose products are all +0.0 (row0, below)
   constexpr bool QL = QU && !LP;
   bool quiet = false;
   if (QU && v.quiet != nullptr && v.quiet_use) {
-    const uint2 qw = *reinterpret_cast<const uint2*>(v.quiet + ((((size_t)(tp & 1) * (size_t)v.quiet_npos + qslot) * qgroup + qrg) << 1));
+    const uint2 qw = *reinterpret_cast<const uint2*>(v.quiet_rd + qoff);
     quiet = qw.x == (uint32_t)t && qw.y == (uint32_t)t;   // (launch t - 1 stores t)
   }
   PH(1, lane + node);
@@ -783,6 +817,10 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
   bool qz = false;   // QU: this lane's share of the quiet word of step t (virtual pairs: never quiet)
   double s_i = 0.0, r_i = 0.0, qo = 0.0, qi = 0.0, co_prev = 0.0, ci_prev = 0.0;
   int lin = 0, lout = 0, kind = 0;
+  // element offsets of the wave's segment inside a history row or a plain [L][RS] array, columns lin / lout (< 2^31: pedn_create)
+  uint32_t oin = 0, oout = 0;
+#define RIN(K, BASE, ROW, COLS) rowq<RB>(v, K, oin, BASE, ROW, lin, COLS, RS, r0)
+#define ROUT(K, BASE, ROW, COLS) rowq<RB>(v, K, oout, BASE, ROW, lout, COLS, RS, r0)
   // QL: every P[slot][j] * s_i of this wave's row is +0.0 in all 64 lanes (wave-uniform) -- then so is every g_slot,j that the column
   // passes leave in the row (a = +0.0: b = r_j * (a / D_j) is +-0.0 or NaN, b < a is false, g = floor(a)), and the row sums are +0.0
   bool row0 = false;
@@ -807,6 +845,8 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     kind = W.kind;
     lin = W.lin;
     lout = W.lout;
+    oin = (uint32_t)lin * (uint32_t)RS + (uint32_t)r0;
+    oout = (uint32_t)lout * (uint32_t)RS + (uint32_t)r0;
     const int turn0 = W.turn0 + slot * (m - 1);
     // turning fractions of row `slot` (SlotRec.dyn): imposed / default ones from tf or the replica-uniform shortcut tf_u; those
     // of a dynamic node (path_finder.py:591-715) from the buffer turn_frac_kernel filled for this step, or -- every product of
@@ -844,44 +884,45 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
         // word) and sending_flow[t'-1] are +0.0; the code below runs unchanged on them.  (receiving_flow, the running sum and the travel
         // times are not zero on an empty corridor.)
         lu_rs = v.rsum[(size_t)lin * RS + r];
-        lu_old = lu_win ? rowp(v.f32[G_TT], R32(G_TT, tp - v.W), lin, L, RS, r0)[lane] : 0.0f;
+        lu_old = lu_win ? RIN(RB_TT_W, v.f32[G_TT], R32(G_TT, tp - v.W), L)[lane] : 0.0f;
         x.co_in = 0.0;
         x.s_prev = 0.0;
         x.co_sw = 0.0;
         x.ci_out = 0.0;
-        x.r_prev = rowp(v.f64[F_R], R64(F_R, tm1), lout, L, RS, r0)[lane];
+        x.r_prev = ROUT(RB_R_Q, v.f64[F_R], R64(F_R, tm1), L)[lane];
       } else {
         if (!LU) {
-          x.n_in = rowp(v.f32[G_N], R32(G_N, tp), lin, L, RS, r0)[lane];
-          x.n_out = rowp(v.f32[G_N], R32(G_N, tp), lout, L, RS, r0)[lane];
+          x.n_in = RIN(RB_N_P, v.f32[G_N], R32(G_N, tp), L)[lane];
+          x.n_out = ROUT(RB_N_P, v.f32[G_N], R32(G_N, tp), L)[lane];
           // density[t'] of a plain link is num_pedestrians[t'] / float32(length * width) (link.py:136): recomputed from n_in with the
           // link update's own division instead of being read back; a separator's density depends on its width at that time
-          x.k_in = Pin.sep ? rowp(v.f32[G_K], R32(G_K, tp), lin, L, RS, r0)[lane] : 0.0f;
-          x.att_in = rowp(v.f32[G_ATT], R32(G_ATT, tp), lin, L, RS, r0)[lane];
+          x.k_in = Pin.sep ? RIN(RB_K_P, v.f32[G_K], R32(G_K, tp), L)[lane] : 0.0f;
+          x.att_in = RIN(RB_ATT_P, v.f32[G_ATT], R32(G_ATT, tp), L)[lane];
         } else {
           // inputs of the link update of step t' for the corridor (lin, lout): all of them written by the launches before this one
-          lu_ia = rowp(v.f64[F_IN], R64(F_IN, tp), lin, Lall, RS, r0)[lane];
-          lu_oa = rowp(v.f64[F_OUT], R64(F_OUT, tp), lin, Lall, RS, r0)[lane];
-          lu_ib = rowp(v.f64[F_IN], R64(F_IN, tp), lout, Lall, RS, r0)[lane];
-          lu_ob = rowp(v.f64[F_OUT], R64(F_OUT, tp), lout, Lall, RS, r0)[lane];
-          lu_pa = rowp(v.f32[G_N], R32(G_N, tp - 1), lin, L, RS, r0)[lane];
-          lu_pb = rowp(v.f32[G_N], R32(G_N, tp - 1), lout, L, RS, r0)[lane];
+          lu_ia = RIN(RB_IN_P, v.f64[F_IN], R64(F_IN, tp), Lall)[lane];
+          lu_oa = RIN(RB_OUT_P, v.f64[F_OUT], R64(F_OUT, tp), Lall)[lane];
+          lu_ib = ROUT(RB_IN_P, v.f64[F_IN], R64(F_IN, tp), Lall)[lane];
+          lu_ob = ROUT(RB_OUT_P, v.f64[F_OUT], R64(F_OUT, tp), Lall)[lane];
+          lu_pa = RIN(RB_N_Q, v.f32[G_N], R32(G_N, tp - 1), L)[lane];
+          lu_pb = ROUT(RB_N_Q, v.f32[G_N], R32(G_N, tp - 1), L)[lane];
           lu_rs = v.rsum[(size_t)lin * RS + r];
-          lu_old = lu_win ? rowp(v.f32[G_TT], R32(G_TT, tp - v.W), lin, L, RS, r0)[lane] : 0.0f;
-          if (Pin.sep) lu_npa = v.sepnp[(size_t)lin * RS + r];
-          if (Pout.sep) lu_npb = v.sepnp[(size_t)lout * RS + r];
+          lu_old = lu_win ? RIN(RB_TT_W, v.f32[G_TT], R32(G_TT, tp - v.W), L)[lane] : 0.0f;
+          if (Pin.sep) lu_npa = colr<RB>(v.sepnp, oin, lane, lin, RS, r);
+          if (Pout.sep) lu_npb = colr<RB>(v.sepnp, oout, lane, lout, RS, r);
         }
-        x.co_in = rowp(v.f64[F_CO], R64(F_CO, tp), lin, Lall, RS, r0)[lane];
-        x.s_prev = rowp(v.f64[F_S], R64(F_S, tm1), lin, L, RS, r0)[lane];
-        x.co_sw = rowp(v.f64[F_CO], R64(F_CO, t_sw), lout, Lall, RS, r0)[lane];
-        x.ci_out = rowp(v.f64[F_CI], R64(F_CI, tp), lout, Lall, RS, r0)[lane];
-        x.r_prev = rowp(v.f64[F_R], R64(F_R, tm1), lout, L, RS, r0)[lane];
+        x.co_in = RIN(RB_CO_P, v.f64[F_CO], R64(F_CO, tp), Lall)[lane];
+        x.s_prev = RIN(RB_S_Q, v.f64[F_S], R64(F_S, tm1), L)[lane];
+        x.co_sw = RB ? rowd(v.f64[F_CO], R64(F_CO, t_sw), (uint32_t)Lall * (uint32_t)RS, oout)[lane]
+                     : rowp(v.f64[F_CO], R64(F_CO, t_sw), lout, Lall, RS, r0)[lane];
+        x.ci_out = ROUT(RB_CI_P, v.f64[F_CI], R64(F_CI, tp), Lall)[lane];
+        x.r_prev = ROUT(RB_R_Q, v.f64[F_R], R64(F_R, tm1), L)[lane];
       }
       const double fu = v.front_u[lin], bu = v.back_u[lout];
-      x.front_in = fu == fu ? fu : v.front[(size_t)lin * RS + r];
-      x.back_out = bu == bu ? bu : v.back[(size_t)lout * RS + r];
-      x.sepw_in = Pin.sep ? v.sepw[(size_t)lin * RS + r] : 0.0;
-      x.sepw_out = Pout.sep ? v.sepw[(size_t)lout * RS + r] : 0.0;
+      x.front_in = fu == fu ? fu : colr<RB>(v.front, oin, lane, lin, RS, r);
+      x.back_out = bu == bu ? bu : colr<RB>(v.back, oout, lane, lout, RS, r);
+      x.sepw_in = Pin.sep ? colr<RB>(v.sepw, oin, lane, lin, RS, r) : 0.0;
+      x.sepw_out = Pout.sep ? colr<RB>(v.sepw, oout, lane, lout, RS, r) : 0.0;
     };
     int tw0 = 0, tw1 = 0;
     if (inl_row && !HELP) {   // the row's record: one vector load per half, in flight with the batch below
@@ -892,8 +933,8 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     if (inl_row && !HELP) turn_frac_body<PR, true, HIST, true>(v, t, 0u, my_tf, W.trow, r0, tw0, tw1);
     if (lin >= L) {  // virtual pair: origin demand in, unlimited sink out (node.py:176,186)
       s_i = v.demand[((size_t)W.demand_row * v.T1 + tp) * RS + r];
-      co_prev = rowp(v.f64[F_CO], R64(F_CO, tp), lin, Lall, RS, r0)[lane];
-      ci_prev = rowp(v.f64[F_CI], R64(F_CI, tp), lout, Lall, RS, r0)[lane];
+      co_prev = RIN(RB_CO_P, v.f64[F_CO], R64(F_CO, tp), Lall)[lane];
+      ci_prev = ROUT(RB_CI_P, v.f64[F_CI], R64(F_CI, tp), Lall)[lane];
       if (kind == 1) {
         if (inl_row) {
 #pragma unroll
@@ -919,8 +960,8 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
           if (fabs(a - cur) > v.rl_max_delta_gate) a = cur + clip_d(a - cur, -v.rl_max_delta_gate, v.rl_max_delta_gate);
           a = clip_d(a, 0.0, Pout.width);
           x.back_out = x.front_in = a;
-          v.back[(size_t)lout * RS + r] = a;
-          v.front[(size_t)lin * RS + r] = a;
+          colr<RB>(v.back, oout, lane, lout, RS, r) = a;
+          colr<RB>(v.front, oin, lane, lin, RS, r) = a;
         }
       }
       if (kind == 1) {
@@ -947,18 +988,18 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
         // zero elision (ZE, DevView.zg32): row t' of both fields holds +0.0 already -- one vote per pair, a -0.0 is still stored.
         // (Stored ahead of the speed: with the vote behind it, 8 vector spills)
         if (!(ZE && v.zg32 && __all((__float_as_int(na) | __float_as_int(ka)) == 0))) {
-          rowp(v.f32[G_N], R32(G_N, tp), lin, L, RS, r0)[lane] = na;
-          rowp(v.f32[G_K], R32(G_K, tp), lin, L, RS, r0)[lane] = ka;
+          RIN(RB_N_P, v.f32[G_N], R32(G_N, tp), L)[lane] = na;
+          RIN(RB_K_P, v.f32[G_K], R32(G_K, tp), L)[lane] = ka;
         }
         const SpeedOut so = speed_calc(v, Pin, lin, tp, r, ka, kb, lu_rs, lu_old, nz);
-        rowp(v.f32[G_V], R32(G_V, tp), lin, L, RS, r0)[lane] = so.spd;
-        rowp(v.f32[G_TT], R32(G_TT, tp), lin, L, RS, r0)[lane] = so.tt;
-        if (!(ZE && v.zg32 && __all(__float_as_int(so.lf) == 0))) rowp(v.f32[G_LF], R32(G_LF, tp), lin, L, RS, r0)[lane] = so.lf;
-        if (lu_win) rowp(v.f32[G_ATT], R32(G_ATT, tp), lin, L, RS, r0)[lane] = so.att;
+        RIN(RB_V_P, v.f32[G_V], R32(G_V, tp), L)[lane] = so.spd;
+        RIN(RB_TT_P, v.f32[G_TT], R32(G_TT, tp), L)[lane] = so.tt;
+        if (!(ZE && v.zg32 && __all(__float_as_int(so.lf) == 0))) RIN(RB_LF_P, v.f32[G_LF], R32(G_LF, tp), L)[lane] = so.lf;
+        if (lu_win) RIN(RB_ATT_P, v.f32[G_ATT], R32(G_ATT, tp), L)[lane] = so.att;
         v.rsum[(size_t)lin * RS + r] = so.rs;
         // recorded width of the OUTGOING link (link.py:188 / :451-452): its back gate as loaded above, before any action of this step
         const double go = Pout.sep ? x.sepw_out : lu_gate;
-        if (go != Pout.width || v.hist) rowp(v.f64[F_GATE], R64(F_GATE, tp), lout, L, RS, r0)[lane] = go;
+        if (go != Pout.width || v.hist) ROUT(RB_GATE_P, v.f64[F_GATE], R64(F_GATE, tp), L)[lane] = go;
         x.n_in = na; x.n_out = nb; x.k_in = ka; x.att_in = so.att;
         // quiet word of this step, part 1 (part 2 below the node's flows): num_pedestrians[t'] of the incoming link, the shock-wave
         // look-back of at least one step that the next launch's quiet batch assumes, never a separator on either side, and no negative
@@ -979,17 +1020,18 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
       if (idx_s > tp + 1) idx_s = tp + 1;   // a zero / negative / garbage avg_travel_time must not take the load past the rows written so far
       // (a quiet corridor: +0.0 at every row <= t' -- a look-back of 0 steps, idx_s = t' + 1, is loaded as by the full batch)
       double ci_look = 0.0;
-      if (!(QU && quiet) || idx_s > tp) ci_look = v.f64[F_CI][at(R64(F_CI, idx_s), lin, Lall, RS, r)];
+      if (!(QU && quiet) || idx_s > tp) ci_look = RB ? *rowd(v.f64[F_CI], R64(F_CI, idx_s), (uint32_t)Lall * (uint32_t)RS, (uint32_t)lin * (uint32_t)RS + (uint32_t)r)
+                                                     : v.f64[F_CI][at(R64(F_CI, idx_s), lin, Lall, RS, r)];
       // (lazy reset: a zero look-back -- the PEDN_F_SAME_STEP case -- reads the row of THIS step, which an ordinary reset left at 0)
       ci_look = idx_s > vhi ? 0.0 : ci_look;
       const double rp = recv_reverse_peds(v, Pout, lout, tp, r, x, fl);
-      s_i = early ? 0.0 : send_flow<HIST>(v, Pin, lin, tp, r, x, ci_look, vhi, fl);
+      s_i = early ? 0.0 : send_flow<HIST, RB>(v, Pin, lin, tp, r, x, ci_look, vhi, fl, (uint32_t)lin * (uint32_t)RS);
       PH(3, s_i);
-      rowp(v.f64[F_S], R64(F_S, tp), lin, L, RS, r0)[lane] = s_i;  // link.py:268,367
+      RIN(RB_S_P, v.f64[F_S], R64(F_S, tp), L)[lane] = s_i;  // link.py:268,367
       if (s_i < 0.0) fl |= PEDN_F_NEG_FLOW;
       r_i = recv_flow(v, Pout, lout, tp, r, x, s_i, rp, fl);
       PH(4, r_i);
-      rowp(v.f64[F_R], R64(F_R, tp), lout, L, RS, r0)[lane] = r_i;  // node.py:206
+      ROUT(RB_R_P, v.f64[F_R], R64(F_R, tp), L)[lane] = r_i;  // node.py:206
     }
     if (s_i < 0.0 || r_i < 0.0) fl |= PEDN_F_NEG_FLOW;
 
@@ -1088,19 +1130,19 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
       if (qo < 0.0 || qi < 0.0) fl |= PEDN_F_NEG_FLOW;
     }
     // Node.update_links (node.py:146-162; link.py:19-25)
-    double* const p_out = rowp(v.f64[F_OUT], R64(F_OUT, t), lin, Lall, RS, r0) + lane;
-    double* const p_in = rowp(v.f64[F_IN], R64(F_IN, t), lout, Lall, RS, r0) + lane;
+    double* const p_out = RIN(RB_OUT_T, v.f64[F_OUT], R64(F_OUT, t), Lall) + lane;
+    double* const p_in = ROUT(RB_IN_T, v.f64[F_IN], R64(F_IN, t), Lall) + lane;
     const double co_t = co_prev + qo, ci_t = ci_prev + qi;
     // zero elision (ZE, DevView.zg64): row t of the four fields holds +0.0 already, so a pair of rows whose values are +0.0 in all 64
     // lanes is not stored -- decided per wave (a 512-byte row segment is written whole or not at all), by the bits (-0.0 is stored)
     // (each vote right at its pair of stores: node_kernel lives on its last vector register, see node_kernel_waves)
     if (fl) atomicOr(&v.flags[r], fl);
     if (!(ZE && v.zg64 && __all((__double_as_longlong(qo) | __double_as_longlong(co_t)) == 0))) {
-      rowp(v.f64[F_CO], R64(F_CO, t), lin, Lall, RS, r0)[lane] = co_t;
+      RIN(RB_CO_T, v.f64[F_CO], R64(F_CO, t), Lall)[lane] = co_t;
       *p_out = qo;
     }
     if (!(ZE && v.zg64 && __all((__double_as_longlong(qi) | __double_as_longlong(ci_t)) == 0))) {
-      rowp(v.f64[F_CI], R64(F_CI, t), lout, Lall, RS, r0)[lane] = ci_t;
+      ROUT(RB_CI_T, v.f64[F_CI], R64(F_CI, t), Lall)[lane] = ci_t;
       *p_in = qi;
     }
     if (QU && v.quiet != nullptr) {
@@ -1111,9 +1153,8 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
            __double_as_longlong(qi) == 0 && __double_as_longlong(co_t) == 0 && __double_as_longlong(ci_t) == 0;
       const uint32_t word = __all(qz) ? (uint32_t)t + 1u : 0u;
       if (lane == 0) {
-        uint32_t* const qw = v.quiet + (size_t)(t & 1) * (size_t)v.quiet_npos * qgroup * 2;
-        qw[(qslot * qgroup + qrg) * 2] = word;
-        if (W.mirror >= 0) qw[((size_t)W.mirror * qgroup + qrg) * 2 + 1] = word;
+        v.quiet_wr[qoff] = word;
+        if (W.mirror >= 0) v.quiet_wr[(((uint32_t)W.mirror * qgroup + qrg) << 1) + 1u] = word;
       }
     }
   }
@@ -1127,6 +1168,8 @@ __device__ __forceinline__ void node_step(const DevView& v, const int t, const i
     g_phase[w * 12 + 11] += ph[9] - ph[0];
   }
 #endif
+#undef RIN
+#undef ROUT
 }
 
 // Register budget of node_kernel = waves per SIMD its allocation aims at: 8 with shared link parameters and at most 6 corridors per

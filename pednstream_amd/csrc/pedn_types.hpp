@@ -9,6 +9,12 @@
 // ------------------------------------------------------------------------------------------------- device view
 enum { F_IN = 0, F_OUT, F_CI, F_CO, F_S, F_R, F_GATE };
 enum { G_TT = 0, G_ATT, G_N, G_K, G_V, G_LF };
+// History rows that node_step(t) addresses at a row index every wave of the launch shares (DevView.rb; t' = t - 1, t'' = t - 2 wrapped
+// as wrap_idx does): RB_<field>_<T: row t, P: row t', Q: row t'', W: row t' - W>
+enum {
+  RB_IN_P = 0, RB_IN_T, RB_OUT_P, RB_OUT_T, RB_CI_P, RB_CI_T, RB_CO_P, RB_CO_T, RB_S_Q, RB_S_P, RB_R_Q, RB_R_P, RB_GATE_P,
+  RB_N_Q, RB_N_P, RB_K_P, RB_V_P, RB_TT_P, RB_LF_P, RB_ATT_P, RB_TT_W, RB_COUNT
+};
 
 struct LinkP {  // static per-link parameters, wave-uniform on the device
   double length, width, vf, kc, kj, gamma, act, bi, noise;
@@ -145,4 +151,10 @@ struct DevView {
   // Lean quiet step (PEDN_QUIET_LEAN; set with DevView.quiet): a slot wave whose column / row of the node's products P * s holds +0.0 in
   // all 64 lanes skips its column pass / row sums, whose results that fixes (node_step)
   int32_t quiet_lean;
+  // Row bases (node_step, every node kernel but the clocked one): first byte of the history row RB_k of this launch's step, through the same
+  // full-record / ring mapping as R64 / R32 -- the same for every wave of the grid, so the host forms them once per launch (row_bases in
+  // pedn_hip.hip) and a wave adds only its column's element offset.  quiet_rd / quiet_wr: the halves of DevView.quiet that launch t reads
+  // (step t - 1) and writes (step t).  Unset in the engine's own view: set only in the copy a node-kernel launch carries.
+  char* rb[RB_COUNT];
+  uint32_t *quiet_rd, *quiet_wr;
 };
