@@ -413,6 +413,37 @@ uint64_t pedn_rl_clock_signature(pedn_sim* sim);
 /* device buffers for zero-copy consumers: 0 actions (f64 [R][n_actions]), 1 observations (f32 [R][n_obs]), 2 rewards (f32 [R][n_agents]) */
 void* pedn_rl_device_ptr(pedn_sim* sim, int32_t which);
 
+/* ---- running observation / reward normalisation on the device (rl/rl_utils.py:57-300: RunningMeanStd, RunningNormalizeWrapper) -----
+ * Off by default.  While on, ONE more launch follows whichever launch wrote the observation and reward buffers -- in pedn_rl_observe,
+ * pedn_rl_step (host and device actions) and pedn_rl_step_clocked (on the caller's stream, constant arguments: it is captured with the
+ * step) -- and writes normalised rows into two buffers of their own; the raw buffers stay as they are.  The contract (DESIGN section 11,
+ * restated in numpy by tests/norm_model.py): binary64 statistics that live on the device and survive pedn_reset; per tracked observation
+ * column the batch mean and variance over the env axis, summed in one fixed order that depends on n_envs alone (pedn_norm.hpp), merged
+ * with the operation order of RunningMeanStd._update_from_moments; out = f32(clip((x - mean) / sqrt(var + 1e-8), +-clip_obs)) with the
+ * statistics AFTER the update; untracked columns are copied.  Rewards: ret[e][a] = r + gamma * ret[e][a] * (1 - terminated), agent after
+ * agent merged into one scalar triple, out = f32(clip(r / sqrt(ret_var + 1e-8), +-clip_reward)); pedn_reset zeroes ret.  With one env
+ * this is the reference wrapper bit for bit.
+ *   pedn_rl_norm_configure   tracked_mask [n_obs]: 1 = normalise the column, 0 = copy it (the gate width of every link of a gater);
+ *                            agent_of_column [n_obs]: the agent a column belongs to (the per-agent count of get/set_stats).  Switches
+ *                            the normalisation on with fresh statistics (mean 0, var 1, count 1e-4), training on; norm_obs = norm_reward
+ *                            = 0 switches it off (the two arrays may then be NULL).  Refused together with pedn_ctrl_configure;
+ *                            pedn_rl_step_many refuses engines that normalise.  pedn_rl_configure switches it off.
+ *   pedn_rl_norm_set_training  0: the statistics are frozen (rows are still normalised, returns still discounted)
+ *   pedn_rl_norm_get_stats / pedn_rl_norm_set_stats   mean [n_obs], var [n_obs] (entries of untracked columns are not used), count
+ *                            [n_agents], ret_stats [3] = mean, var, count of the returns; NULL skips an array
+ *   pedn_rl_norm_device_ptr  0 normalised observations (f32 [R][n_obs]), 1 normalised rewards (f32 [R][n_agents]), 2 / 3 / 4 mean / var /
+ *                            count per column (f64 [n_obs]), 5 returns (f64 [R][n_agents]), 6 ret_stats (f64 [3]); NULL while off
+ * While on, pedn_rl_fetch and the obs / rewards arguments of pedn_rl_observe / pedn_rl_step hand out the NORMALISED rows (after
+ * pedn_rl_observe the rewards are the raw ones: no step, nothing to discount); pedn_rl_fetch_raw and pedn_rl_device_ptr keep handing out
+ * the raw ones.  pedn_rl_clock_signature covers the switch and the launch's arguments. */
+int pedn_rl_norm_configure(pedn_sim* sim, int32_t norm_obs, int32_t norm_reward, double clip_obs, double clip_reward, double gamma,
+                           const int32_t* tracked_mask, const int32_t* agent_of_column);
+int pedn_rl_norm_set_training(pedn_sim* sim, int32_t training);
+int pedn_rl_norm_get_stats(pedn_sim* sim, double* mean, double* var, double* count, double* ret_stats);
+int pedn_rl_norm_set_stats(pedn_sim* sim, const double* mean, const double* var, const double* count, const double* ret_stats);
+void* pedn_rl_norm_device_ptr(pedn_sim* sim, int32_t which);
+int pedn_rl_fetch_raw(pedn_sim* sim, float* obs, float* rewards);
+
 /* ---- rule-based controllers on the device (rl/agents/rule_based.py, evaluated by rl/rl_utils.py:1513-1750) ----------------------
  * A controller per agent of the pedn_rl_configure agent set computes the agent's next action from the float32 observation the step has
  * just written, inside the observation part of the step's second launch (no extra launch, no host round trip between env steps):

@@ -48,4 +48,8 @@ def install(force: bool = False):
     rl.agents = mod("rl.agents")
     rl.agents.rule_based = mod("rl.agents.rule_based", BaseAgent=agents.BaseAgent, RuleBasedGaterAgent=agents.RuleBasedGaterAgent,
                                RuleBasedSeparatorAgent=agents.RuleBasedSeparatorAgent)
+    # `from rl.rl_utils import RunningNormalizeWrapper` (rl/train_rl.py, rl/evaluate_and_visualize.py): statistics on the device
+    from . import normalize
+
+    rl.rl_utils = mod("rl.rl_utils", RunningNormalizeWrapper=normalize.RunningNormalizeWrapper, RunningMeanStd=normalize.RunningMeanStd)
     return src

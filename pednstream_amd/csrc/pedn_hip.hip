@@ -21,6 +21,7 @@
 #include "../../include/pedn.h"
 #include "pedn_kernels.hpp"
 #include "pedn_ctrl.hpp"
+#include "pedn_norm.hpp"
 
 // ------------------------------------------------------------------------------------------------- host side
 static thread_local std::string g_last_error;
@@ -140,6 +141,10 @@ struct pedn_sim {
   size_t rl_pin_bytes = 0;
   std::string err;
   struct MetricsState* metrics = nullptr;   // evaluation metrics (pedn_metrics.hpp)
+  // running normalisation (pedn_rl_norm_*, pedn_norm.hpp): the view its launch carries; buffers belong to the agent set
+  NormView nv = {};
+  bool norm_on = false, norm_alloc = false;
+  std::vector<int32_t> h_norm_tracked, h_norm_agent;   // [O]: tracked mask, agent of every column
 };
 static void metrics_free(pedn_sim* s);
 
@@ -512,6 +517,8 @@ static inline void join_forked(pedn_sim* s);
 typedef void (*node_kernel_fn)(DevView, int);
 static node_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf);
 static int clock_end(pedn_sim* s);
+static void norm_launch(pedn_sim* s, hipStream_t st, int rewards, int term);
+static int norm_reset_returns(pedn_sim* s);
 static void prewarm_chains(pedn_sim* s);
 static int fork_chains(pedn_sim* s, int n);
 
@@ -1132,6 +1139,8 @@ int pedn_reset(pedn_sim* s) {
   s->last_t = -1;
   s->link_pending = -1;   // discarded: the state it would complete is being cleared
   no_quiet(s);
+  int rc = norm_reset_returns(s);
+  if (rc != PEDN_OK) return rc;
   return reset_state(s);
 }
 
@@ -1143,6 +1152,8 @@ int pedn_reset_lazy(pedn_sim* s) {
   s->last_t = -1;
   s->link_pending = -1;
   no_quiet(s);
+  int rc = norm_reset_returns(s);
+  if (rc != PEDN_OK) return rc;
   return reset_state_lazy(s);
 }
 
@@ -2295,6 +2306,8 @@ int pedn_rl_configure(pedn_sim* s, const pedn_rl_desc* d, int32_t* n_actions, in
   }
   s->rl_ready = true;
   s->ctrl_ready = s->ctrl_any = false;   // controllers belong to an agent set: configure them again
+  s->norm_on = s->norm_alloc = false;    // so does the running normalisation
+  memset(&s->nv, 0, sizeof s->nv);
   if (n_actions) *n_actions = A;
   if (n_obs) *n_obs = O;
   return PEDN_OK;
@@ -2327,9 +2340,10 @@ int pedn_rl_apply_actions(pedn_sim* s, const double* actions, int32_t on_device)
 
 // observations / rewards -> the caller's buffers: both copies land in ONE pinned buffer, one wait for the stream, then two memcpys (into
 // pageable memory each copy is staged and waited for by the runtime on its own)
-static int rl_fetch(pedn_sim* s, float* obs, float* rewards) {
+static int rl_fetch(pedn_sim* s, float* obs, float* rewards, bool raw = false) {
   if (!obs && !rewards) return PEDN_OK;
-  const RlView& q = s->rl;
+  RlView q = s->rl;
+  if (s->norm_on && !raw) { q.obs = s->nv.obs_n; q.rew = s->nv.rew_n; }   // (contiguous like the raw pair)
   const size_t nb_obs = (size_t)s->v.R * q.O * sizeof(float), nb_rew = (size_t)s->v.R * q.n_agents * sizeof(float);
   if (s->rl_pin_bytes < nb_obs + nb_rew) {
     if (s->rl_pin) HIP_TRY(s, hipHostFree(s->rl_pin));
@@ -2349,7 +2363,8 @@ static int rl_fetch(pedn_sim* s, float* obs, float* rewards) {
 }
 
 // (cv: the controller twin, see launch_step)
-static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards, const CtrlView* cv) {
+// norm: 0 no normalisation launch (a sub-step inside an env step), 1 behind an observation alone, 2 behind an env step (term: its terminated flag)
+static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards, const CtrlView* cv, int norm = 0, int term = 0) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
   if (t < 0 || t > s->v.T1 - 1) return fail(s, PEDN_E_ARG, "time step outside 0..T");
@@ -2364,12 +2379,13 @@ static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, fl
     else hipLaunchKernelGGL(ctrl_observe_kernel<false>, grid, dim3(256), 0, s->stream, v, q, t, accumulate, *cv);
   } else if (v.hist) hipLaunchKernelGGL(rl_observe_kernel<true>, grid, dim3(256), 0, s->stream, v, q, t, accumulate);
   else hipLaunchKernelGGL(rl_observe_kernel<false>, grid, dim3(256), 0, s->stream, v, q, t, accumulate);
+  if (norm) norm_launch(s, s->stream, norm == 2, term);
   HIP_TRY(s, hipGetLastError());
   return rl_fetch(s, obs, rewards);
 }
 
 int pedn_rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards) {
-  return rl_observe(s, t, accumulate, obs, rewards, nullptr);
+  return rl_observe(s, t, accumulate, obs, rewards, nullptr, 1);
 }
 
 int pedn_rl_fetch(pedn_sim* s, float* obs, float* rewards) {
@@ -2378,6 +2394,14 @@ int pedn_rl_fetch(pedn_sim* s, float* obs, float* rewards) {
   HIP_TRY(s, hipSetDevice(s->device));
   join_forked(s);   // (ends a clocked section; both chains' work in front of the copies)
   return rl_fetch(s, obs, rewards);
+}
+
+int pedn_rl_fetch_raw(pedn_sim* s, float* obs, float* rewards) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);
+  return rl_fetch(s, obs, rewards, true);
 }
 
 // cv: a controlled env step (pedn_ctrl_step) -- its last sub-step observes through the controller twins
@@ -2434,7 +2458,8 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
   const bool by_batch = s->v.RS >= 4096 || (s->v.pr && s->v.RS >= 1024);
   // on_device == 2: the caller chains this call between its own streams and pedn_stream() with events (no host synchronisation):
   // everything must then be ordered by the engine's stream alone
-  const bool two = on_device != 2 && (s->rl_chains == 2 || (s->rl_chains == 0 && by_batch)) && s->warmed_chains >= 2 && s->v.RS >= 256 && s->fuse_obs && (!actions || (fold != nullptr && on_device)) && !obs && !rewards &&
+  const int term = t + action_gap - 1 >= s->v.T1 - 1 ? 1 : 0;   // pz_pednet_env.py:592
+  const bool two = !s->norm_on && on_device != 2 && (s->rl_chains == 2 || (s->rl_chains == 0 && by_batch)) && s->warmed_chains >= 2 && s->v.RS >= 256 && s->fuse_obs && (!actions || (fold != nullptr && on_device)) && !obs && !rewards &&
                    s->link_pending < 0 && !(s->v.n_trow > 0 && !s->fuse_tp);
   if (!two) join_forked(s);
   else if (!s->forked) {
@@ -2457,9 +2482,11 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
       if (k == 0 && fold_stage && (rc = stage_commit(s, fold_stage)) != PEDN_OK) return rc;   // its only reader has been launched
     HIP_TRY(s, hipGetLastError());
     if (!observed) {
-      if ((rc = rl_observe(s, t + k, k > 0, last ? obs : nullptr, last ? rewards : nullptr, ck)) != PEDN_OK) return rc;
-    } else if (last && (obs || rewards)) {
-      if ((rc = rl_fetch(s, obs, rewards)) != PEDN_OK) return rc;
+      if ((rc = rl_observe(s, t + k, k > 0, last ? obs : nullptr, last ? rewards : nullptr, ck, last ? 2 : 0, term)) != PEDN_OK) return rc;
+    } else if (last) {
+      norm_launch(s, s->stream, 1, term);
+      HIP_TRY(s, hipGetLastError());
+      if ((obs || rewards) && (rc = rl_fetch(s, obs, rewards)) != PEDN_OK) return rc;
     }
   }
   return PEDN_OK;
@@ -2542,6 +2569,7 @@ int pedn_rl_step_clocked(pedn_sim* s, const double* actions, int32_t action_gap,
     else { if (v.hist) hipLaunchKernelGGL((link_turn_kernel<false, true, true, true>), grid, block, 0, st, v, -1, nlb, ntb, nth, q, acc);
            else hipLaunchKernelGGL((link_turn_kernel<false, true, false, true>), grid, block, 0, st, v, -1, nlb, ntb, nth, q, acc); }
   }
+  norm_launch(s, st, 1, -1);   // (constant arguments: `terminated` comes from the clock)
   HIP_TRY(s, hipGetLastError());
   return PEDN_OK;
 }
@@ -2568,6 +2596,9 @@ uint64_t pedn_rl_clock_signature(pedn_sim* s) {
   mix(&s->rl, sizeof s->rl);
   const int64_t sel[8] = {s->rl_fold, s->n_tf_heavy_quads, s->n_blocks, (int64_t)s->node_lds, s->max_degree, s->node_lp, s->fuse_tp, s->fuse_obs};
   mix(sel, sizeof sel);
+  const int64_t on = s->norm_on;   // the normalisation launch and its view (zeroed while off; configure fills every byte it hashes)
+  mix(&on, sizeof on);
+  mix(&s->nv, sizeof s->nv);
   return h;
 }
 
@@ -2584,6 +2615,8 @@ int pedn_rl_step_many(pedn_sim** sims, int32_t n, const double* actions, int32_t
   if (!sims || n < 1) return fail(nullptr, PEDN_E_ARG, "no engines");
   for (int k = 0; k < n; ++k)
     if (!sims[k] || !sims[k]->rl_ready) return fail(sims[k], PEDN_E_ARG, "null handle or pedn_rl_configure has not been called");
+  for (int k = 0; k < n; ++k)
+    if (sims[k]->norm_on) return fail(sims[k], PEDN_E_ARG, "pedn_rl_step_many does not run the running normalisation (statistics are per engine)");
   size_t row = 0;
   for (int k = 0; k < n; ++k) {   // every engine's launches first (own stream each: they overlap) ...
     pedn_sim* s = sims[k];
@@ -2606,11 +2639,157 @@ void* pedn_rl_device_ptr(pedn_sim* s, int32_t which) {
   return which == 0 ? (void*)s->rl.actions : which == 1 ? (void*)s->rl.obs : which == 2 ? (void*)s->rl.rew : nullptr;
 }
 
+
+// ---- running observation / reward normalisation on the device (pedn_norm.hpp) --------------------------------------------------
+static void norm_launch(pedn_sim* s, hipStream_t st, int rewards, int term) {
+  if (!s->norm_on) return;
+  const unsigned blocks = (unsigned)((s->nv.O + PEDN_NORM_COLS - 1) / PEDN_NORM_COLS) + 1u;   // + the reward workgroup
+  hipLaunchKernelGGL(norm_kernel, dim3(blocks), dim3(1024), 0, st, s->nv, rewards, term);
+}
+
+static int norm_reset_returns(pedn_sim* s) {   // a new episode: the discounted returns start again, the statistics stay
+  if (!s->norm_alloc) return PEDN_OK;
+  HIP_TRY(s, hipMemsetAsync(s->nv.ret, 0, (size_t)s->v.R * s->rl.n_agents * sizeof(double), s->stream));
+  return PEDN_OK;
+}
+
+static int norm_init_stats(pedn_sim* s) {
+  const int O = s->rl.O;
+  std::vector<double> h((size_t)3 * O + 3);
+  for (int c = 0; c < O; ++c) { h[c] = 0.0; h[(size_t)O + c] = 1.0; h[(size_t)2 * O + c] = 1e-4; }
+  h[(size_t)3 * O] = 0.0; h[(size_t)3 * O + 1] = 1.0; h[(size_t)3 * O + 2] = 1e-4;
+  HIP_TRY(s, hipMemcpy(s->nv.mean, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_configure(pedn_sim* s, int32_t norm_obs, int32_t norm_reward, double clip_obs, double clip_reward, double gamma,
+                           const int32_t* tracked_mask, const int32_t* agent_of_column) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: a captured graph is checked against the signature before its next replay)
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  const RlView& q = s->rl;
+  if (!norm_obs && !norm_reward) {   // off: the fetches hand out the raw rows again; the statistics are discarded
+    s->norm_on = false;
+    const NormView keep = s->nv;
+    memset(&s->nv, 0, sizeof s->nv);
+    if (s->norm_alloc) {   // (the buffers stay with the agent set)
+      s->nv.obs_n = keep.obs_n; s->nv.rew_n = keep.rew_n; s->nv.mean = keep.mean; s->nv.var = keep.var; s->nv.count = keep.count;
+      s->nv.ret = keep.ret; s->nv.ret_stats = keep.ret_stats; s->nv.tracked = keep.tracked;
+    }
+    return PEDN_OK;
+  }
+  if (s->ctrl_ready) return fail(s, PEDN_E_ARG, "controllers and the running normalisation cannot be combined");
+  if (!tracked_mask || !agent_of_column) return fail(s, PEDN_E_ARG, "null argument");
+  if (!(clip_obs > 0.0) || !(clip_reward > 0.0)) return fail(s, PEDN_E_ARG, "clip_obs and clip_reward must be positive");
+  if (q.n_agents > PEDN_NORM_MAX_AGENTS) return fail(s, PEDN_E_ARG, "more than 1024 agents");
+  if ((int64_t)s->v.R * std::max(q.O, q.n_agents) > 0x7fffffff) return fail(s, PEDN_E_ARG, "observation buffer too large for the normalisation kernel");
+  for (int c = 0; c < q.O; ++c)
+    if (agent_of_column[c] < 0 || agent_of_column[c] >= q.n_agents) return fail(s, PEDN_E_ARG, "agent_of_column out of range");
+  int rc;
+  NormView n;
+  memset(&n, 0, sizeof n);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
+  if (!s->norm_alloc) {
+    double* d = nullptr;
+    float* f = nullptr;
+    int32_t* m = nullptr;
+    const size_t n_ret = (size_t)s->v.R * q.n_agents;
+    if ((rc = dalloc(s, (size_t)3 * q.O + 3 + n_ret, &d)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)s->v.R * q.O + n_ret, &f)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)q.O, &m)) != PEDN_OK) return rc;
+    n.mean = d; n.var = d + q.O; n.count = d + 2 * (size_t)q.O; n.ret_stats = d + 3 * (size_t)q.O; n.ret = n.ret_stats + 3;
+    n.obs_n = f; n.rew_n = f + (size_t)s->v.R * q.O;
+    n.tracked = m;
+    HIP_TRY(s, hipMemset(f, 0, ((size_t)s->v.R * q.O + n_ret) * sizeof(float)));
+  } else {
+    const NormView& o = s->nv;
+    n.mean = o.mean; n.var = o.var; n.count = o.count; n.ret_stats = o.ret_stats; n.ret = o.ret; n.obs_n = o.obs_n; n.rew_n = o.rew_n; n.tracked = o.tracked;
+  }
+  n.obs = q.obs; n.rew = q.rew; n.clock = s->d_clock;
+  n.R = s->v.R; n.O = q.O; n.n_agents = q.n_agents; n.T = s->v.T1 - 1;
+  n.norm_obs = norm_obs ? 1 : 0; n.norm_reward = norm_reward ? 1 : 0; n.training = 1;
+  n.clip_obs = clip_obs; n.clip_reward = clip_reward; n.gamma = gamma;
+  s->nv = n;
+  s->norm_alloc = true;
+  s->h_norm_tracked.assign(tracked_mask, tracked_mask + q.O);
+  for (int32_t& t : s->h_norm_tracked) t = t ? 1 : 0;
+  s->h_norm_agent.assign(agent_of_column, agent_of_column + q.O);
+  HIP_TRY(s, hipMemcpy(const_cast<int32_t*>(n.tracked), s->h_norm_tracked.data(), (size_t)q.O * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(s, hipMemset(n.ret, 0, (size_t)s->v.R * q.n_agents * sizeof(double)));
+  if ((rc = norm_init_stats(s)) != PEDN_OK) return rc;
+  s->norm_on = true;
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_set_training(pedn_sim* s, int32_t training) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->norm_on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);   // (the flag travels in the launch's arguments: a clocked section ends, a captured graph is captured again)
+  s->nv.training = training ? 1 : 0;
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_get_stats(pedn_sim* s, double* mean, double* var, double* count, double* ret_stats) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->norm_on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  const int O = s->nv.O;
+  std::vector<double> h((size_t)3 * O + 3);
+  HIP_TRY(s, hipMemcpy(h.data(), s->nv.mean, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (mean) memcpy(mean, h.data(), (size_t)O * sizeof(double));
+  if (var) memcpy(var, h.data() + O, (size_t)O * sizeof(double));
+  if (count) {   // per agent: the count of its tracked columns (they all carry the same one)
+    for (int a = 0; a < s->nv.n_agents; ++a) count[a] = 1e-4;
+    for (int c = O - 1; c >= 0; --c)
+      if (s->h_norm_tracked[c]) count[s->h_norm_agent[c]] = h[(size_t)2 * O + c];
+  }
+  if (ret_stats) memcpy(ret_stats, h.data() + (size_t)3 * O, 3 * sizeof(double));
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_set_stats(pedn_sim* s, const double* mean, const double* var, const double* count, const double* ret_stats) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->norm_on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  const int O = s->nv.O;
+  std::vector<double> h((size_t)3 * O + 3);
+  HIP_TRY(s, hipMemcpy(h.data(), s->nv.mean, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (mean) memcpy(h.data(), mean, (size_t)O * sizeof(double));
+  if (var) memcpy(h.data() + O, var, (size_t)O * sizeof(double));
+  if (count)
+    for (int c = 0; c < O; ++c) h[(size_t)2 * O + c] = count[s->h_norm_agent[c]];
+  if (ret_stats) memcpy(h.data() + (size_t)3 * O, ret_stats, 3 * sizeof(double));
+  HIP_TRY(s, hipMemcpy(s->nv.mean, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  return PEDN_OK;
+}
+
+void* pedn_rl_norm_device_ptr(pedn_sim* s, int32_t which) {
+  if (!s || !s->norm_on) return nullptr;
+  const NormView& n = s->nv;
+  switch (which) {
+    case 0: return n.obs_n;
+    case 1: return n.rew_n;
+    case 2: return n.mean;
+    case 3: return n.var;
+    case 4: return n.count;
+    case 5: return n.ret;
+    case 6: return n.ret_stats;
+  }
+  return nullptr;
+}
+
 // ---- rule-based controllers on the device (pedn_ctrl.hpp) ----------------------------------------------------------------------
 int pedn_ctrl_configure(pedn_sim* s, const int32_t* kind, const int32_t* window, const int32_t* wide, const float* threshold,
                         const double* width, const float* open) {
   if (!s || !kind || !window || !wide || !threshold || !width || !open) return fail(s, PEDN_E_ARG, "null argument");
   if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  if (s->norm_on) return fail(s, PEDN_E_ARG, "controllers and the running normalisation cannot be combined: switch the normalisation off first");
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
   const RlView& q = s->rl;

@@ -186,6 +186,12 @@ def _load():
         "pedn_ctrl_step": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32]),
         "pedn_ctrl_read": (C.c_int, [P, _F64P, _F32P]),
         "pedn_ctrl_device_ptr": (C.c_void_p, [P, C.c_int32]),
+        "pedn_rl_norm_configure": (C.c_int, [P, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _I32P, _I32P]),
+        "pedn_rl_norm_set_training": (C.c_int, [P, C.c_int32]),
+        "pedn_rl_norm_get_stats": (C.c_int, [P, _F64P, _F64P, _F64P, _F64P]),
+        "pedn_rl_norm_set_stats": (C.c_int, [P, _F64P, _F64P, _F64P, _F64P]),
+        "pedn_rl_norm_device_ptr": (C.c_void_p, [P, C.c_int32]),
+        "pedn_rl_fetch_raw": (C.c_int, [P, C.c_void_p, C.c_void_p]),
     }
     # the version first: a stale or alternate library (PEDN_HIP_LIB) must fail with this message, not with an AttributeError on a symbol
     lib.pedn_abi_version.restype, lib.pedn_abi_version.argtypes = C.c_int, []
@@ -216,7 +222,9 @@ EXPORTS = ["pedn_abi_version", "pedn_last_error", "pedn_create", "pedn_destroy",
            "pedn_set_od_weights_per_replica", "pedn_get_od_weights_per_replica", "pedn_get_link_params", "pedn_randomize_scenarios", "pedn_reset_widths",
            "pedn_flush", "pedn_rl_clock_begin", "pedn_rl_step_clocked", "pedn_rl_clock_end", "pedn_rl_clocked", "pedn_rl_clock_signature",
            "pedn_metrics_begin", "pedn_metrics_accumulate", "pedn_metrics_read",
-           "pedn_ctrl_configure", "pedn_ctrl_observe", "pedn_ctrl_step", "pedn_ctrl_read", "pedn_ctrl_device_ptr"]
+           "pedn_ctrl_configure", "pedn_ctrl_observe", "pedn_ctrl_step", "pedn_ctrl_read", "pedn_ctrl_device_ptr",
+           "pedn_rl_norm_configure", "pedn_rl_norm_set_training", "pedn_rl_norm_get_stats", "pedn_rl_norm_set_stats", "pedn_rl_norm_device_ptr",
+           "pedn_rl_fetch_raw"]
 
 
 def _p(a, dtype=np.float64):
@@ -665,6 +673,48 @@ class Engine:
         e = np.empty((self.n_replicas, self.rl_n_agents), dtype=np.float32) if episode_rewards else None
         self._ck(self._lib.pedn_ctrl_read(self._h, None if a is None else _p(a), None if e is None else _p(e, np.float32)))
         return a, e
+
+    # -- running normalisation (include/pedn.h: pedn_rl_norm_*; VecPedNetEnv.set_running_norm builds the arguments)
+    def rl_norm_configure(self, norm_obs, norm_reward, clip_obs=50.0, clip_reward=10.0, gamma=0.99, tracked_mask=None, agent_of_column=None):
+        if not norm_obs and not norm_reward:
+            self._ck(self._lib.pedn_rl_norm_configure(self._h, 0, 0, 1.0, 1.0, 0.0, None, None))
+            return
+        m = np.ascontiguousarray(tracked_mask, dtype=np.int32)
+        a = np.ascontiguousarray(agent_of_column, dtype=np.int32)
+        assert m.shape == a.shape == (self.rl_n_obs,), (m.shape, a.shape)
+        rc = self._lib.pedn_rl_norm_configure(self._h, int(bool(norm_obs)), int(bool(norm_reward)), float(clip_obs), float(clip_reward),
+                                              float(gamma), _p(m, np.int32), _p(a, np.int32))
+        if rc < 0:
+            raise ValueError(self._lib.pedn_last_error(self._h).decode())
+
+    def rl_norm_set_training(self, training):
+        self._ck(self._lib.pedn_rl_norm_set_training(self._h, int(bool(training))))
+
+    def rl_norm_get_stats(self):
+        """(mean [n_obs], var [n_obs], count [n_agents], ret_stats [3]) float64."""
+        mean, var = np.empty(self.rl_n_obs), np.empty(self.rl_n_obs)
+        count, ret = np.empty(self.rl_n_agents), np.empty(3)
+        self._ck(self._lib.pedn_rl_norm_get_stats(self._h, _p(mean), _p(var), _p(count), _p(ret)))
+        return mean, var, count, ret
+
+    def rl_norm_set_stats(self, mean=None, var=None, count=None, ret_stats=None):
+        arrs = []
+        for x, n in ((mean, self.rl_n_obs), (var, self.rl_n_obs), (count, self.rl_n_agents), (ret_stats, 3)):
+            if x is not None:
+                x = np.ascontiguousarray(x, dtype=np.float64)
+                assert x.shape == (n,), (x.shape, n)
+            arrs.append(x)
+        self._ck(self._lib.pedn_rl_norm_set_stats(self._h, *[None if x is None else _p(x) for x in arrs]))
+
+    def rl_norm_device_ptr(self, which):
+        return self._lib.pedn_rl_norm_device_ptr(self._h, int(which))
+
+    def rl_fetch_raw(self):
+        """Host copies of the RAW observation / reward buffers, whether or not the normalisation is on (pedn_rl_fetch_raw)."""
+        obs = np.empty((self.n_replicas, self.rl_n_obs), dtype=np.float32)
+        rew = np.empty((self.n_replicas, self.rl_n_agents), dtype=np.float32)
+        self._ck(self._lib.pedn_rl_fetch_raw(self._h, obs.ctypes.data_as(C.c_void_p), rew.ctypes.data_as(C.c_void_p)))
+        return obs, rew
 
     def device_ptr(self, field):
         cols, stride = C.c_int64(), C.c_int64()

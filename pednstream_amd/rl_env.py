@@ -196,12 +196,14 @@ class VecPedNetEnv:
         self.action_low, self.action_high = np.array(lo, np.float32), np.array(hi, np.float32)
         self.sim_step = 1
         self._device_views = None
+        self._raw_views = None
         self.track_metrics = bool(track_metrics)
         self._metrics = None
         self._folded = 0
         self._rows = None
         self._controllers = None       # set_controllers: {agent_id: agent or None}
         self._ctrl_reset = False
+        self._norm = None              # set_running_norm: the configuration dict while the normalisation is on
 
     # ------------------------------------------------------------------------------------------------ API
     AUTO_VECTORISED_FROM = 65      # randomize(mode="auto"): batches of this many envs and more draw their scenarios on the device
@@ -282,6 +284,118 @@ class VecPedNetEnv:
             obs, _ = eng.rl_observe(self.sim_step, accumulate=False)
         return obs, {}
 
+    # ------------------------------------------------------------------------------------------------ running normalisation
+    def norm_layout(self):
+        """(tracked [n_obs] bool, agent_of_column [n_obs] int32): which observation columns the running normalisation tracks -- all but
+        the last feature (the gate width) of every link of a gater agent, rl/rl_utils.py:195-234 -- and the agent each column belongs to."""
+        tracked, agent = np.ones(self.n_obs, dtype=bool), np.zeros(self.n_obs, dtype=np.int32)
+        for i, (aid, ty) in enumerate(zip(self.possible_agents, self._types)):
+            sl = self.obs_slices[aid]
+            agent[sl] = i
+            if ty == 1:
+                tracked[sl.start + self.features_per_link - 1:sl.stop:self.features_per_link] = False
+        return tracked, agent
+
+    def set_running_norm(self, norm_obs=True, norm_reward=False, clip_obs=50.0, clip_reward=10.0, gamma=0.99, training=True):
+        """The reference's RunningNormalizeWrapper (rl/rl_utils.py:86-300) for the whole batch, on the device (pednstream_amd/csrc/
+        pedn_norm.hpp; the contract is DESIGN section 11): online mean / variance per observation column over ALL envs (the gate width
+        of every link of a gater is left as it is), rewards optionally divided by the running std of the discounted returns.  One more
+        launch per observation; ``reset`` / ``step`` / ``step_async`` + ``step_wait`` / ``step_device`` / ``device_views`` / ``capture``
+        then hand out the normalised rows, ``raw_views`` / ``true_rewards`` the raw ones.  Statistics start fresh with every call, live
+        on the device, survive ``reset`` (the discounted returns do not) and are the same bit for bit whichever way the env is stepped.
+        ``set_running_norm(None)`` switches it off.  Not together with ``set_controllers``, not in ``MultiScenarioVecEnv``; statistics
+        are not merged across ranks."""
+        eng = self.network.engine()
+        if norm_obs is None or (not norm_obs and not norm_reward):
+            if self._norm is not None:
+                self.network._flush()
+                eng.rl_norm_configure(False, False)
+            self._norm, self._device_views = None, None
+            return
+        if self._controllers is not None:
+            raise ValueError("set_running_norm cannot be combined with set_controllers")
+        if self._tracked_piece() is not None or (self.track_metrics and self.action_gap > self._ring_rows()):
+            raise ValueError("set_running_norm does not step an env step in pieces (track_metrics with recent history and an action_gap "
+                             "longer than the history rings); use history='full'")
+        if not (clip_obs > 0 and clip_reward > 0):
+            raise ValueError("clip_obs and clip_reward must be positive")
+        tracked, agent = self.norm_layout()
+        self.network._flush()
+        eng.rl_norm_configure(norm_obs, norm_reward, clip_obs, clip_reward, gamma, tracked.astype(np.int32), agent)
+        self._norm = dict(norm_obs=bool(norm_obs), norm_reward=bool(norm_reward), clip_obs=float(clip_obs), clip_reward=float(clip_reward),
+                          gamma=float(gamma), training=True)
+        self._device_views = None
+        if not training:
+            self.set_training(False)
+
+    def _need_norm(self):
+        if self._norm is None:
+            raise RuntimeError("call set_running_norm() first")
+
+    def set_training(self, training):
+        """False: the running statistics are frozen (rows are still normalised with them)."""
+        self._need_norm()
+        self.network.engine().rl_norm_set_training(training)
+        self._norm["training"] = bool(training)
+
+    def get_normalization_stats(self):
+        """The reference's dict (rl/rl_utils.py:273-287): ``{'obs_rms': {agent: {'mean', 'var', 'count'}}, 'ret_rms': {...}}``, mean / var
+        over the agent's TRACKED features; read from the device."""
+        self._need_norm()
+        mean, var, count, ret = self.network.engine().rl_norm_get_stats()
+        tracked, agent = self.norm_layout()
+        out = {"obs_rms": {}}
+        for i, aid in enumerate(self.possible_agents):
+            cols = np.flatnonzero(tracked & (agent == i))
+            out["obs_rms"][aid] = {"mean": mean[cols].tolist(), "var": var[cols].tolist(), "count": float(count[i])}
+        if self._norm["norm_reward"]:
+            out["ret_rms"] = {"mean": float(ret[0]), "var": float(ret[1]), "count": float(ret[2])}
+        return out
+
+    def set_normalization_stats(self, stats):
+        """Load statistics saved by ``get_normalization_stats`` (or by the reference's wrapper): agents the env does not have are skipped,
+        like rl/rl_utils.py:289-300."""
+        self._need_norm()
+        eng = self.network.engine()
+        mean, var, count, ret = eng.rl_norm_get_stats()
+        tracked, agent = self.norm_layout()
+        for i, aid in enumerate(self.possible_agents):
+            d = stats["obs_rms"].get(aid)
+            if d is None:
+                continue
+            cols = np.flatnonzero(tracked & (agent == i))
+            m, v = np.asarray(d["mean"], dtype=np.float64).reshape(-1), np.asarray(d["var"], dtype=np.float64).reshape(-1)
+            if m.shape != cols.shape or v.shape != cols.shape:
+                raise ValueError(f"{aid}: expected {len(cols)} tracked features, got mean {m.shape} / var {v.shape}")
+            mean[cols], var[cols], count[i] = m, v, float(d["count"])
+        if "ret_rms" in stats and self._norm["norm_reward"]:
+            r = stats["ret_rms"]
+            ret = np.array([float(np.asarray(r["mean"]).reshape(-1)[0]), float(np.asarray(r["var"]).reshape(-1)[0]), float(r["count"])])
+        eng.rl_norm_set_stats(mean, var, count, ret)
+
+    def raw_views(self):
+        """(obs, rewards) float32 torch tensors that alias the RAW device buffers, normalisation on or off."""
+        if self._raw_views is None:
+            self._raw_views = self._views(False)
+        return self._raw_views
+
+    def true_rewards(self):
+        """[n_envs, n_agents] float32 host copy of the last step's un-normalised rewards (the reference's ``infos[aid]['true_reward']``)."""
+        return self.network.engine().rl_fetch_raw()[1]
+
+    def raw_observations(self):
+        """[n_envs, n_obs] float32 host copy of the last un-normalised observations."""
+        return self.network.engine().rl_fetch_raw()[0]
+
+    def _views(self, normalised):
+        import torch
+
+        eng = self.network.engine()
+        dev = torch.device("cuda", self.network.device)
+        ptr = (lambda w: eng.rl_norm_device_ptr(w - 1)) if normalised else eng.rl_device_ptr
+        view = lambda which, cols: torch.as_tensor(_DeviceBuffer(ptr(which), (self.n_envs, cols), "<f4"), device=dev)
+        return (view(1, self.n_obs), view(2, len(self.possible_agents)))
+
     # ------------------------------------------------------------------------------------------------ rule-based controllers
     def set_controllers(self, controllers):
         """Run the reference's rule-based agents on the device for every env (pednstream_amd/csrc/pedn_ctrl.hpp): ``{agent_id:
@@ -332,6 +446,8 @@ class VecPedNetEnv:
             else:
                 raise TypeError(f"{aid}: only RuleBasedGaterAgent / RuleBasedSeparatorAgent run on the device (a torch policy goes "
                                 f"through capture()), got {type(agent).__name__}")
+        if self._norm is not None:
+            raise ValueError("set_controllers cannot be combined with set_running_norm: switch the normalisation off first")
         self.network._flush()
         eng.ctrl_configure(kind, window, wide, thr, width, open_w)
         self._controllers = {aid: controllers.get(aid) for aid in self.possible_agents}
@@ -531,14 +647,10 @@ class VecPedNetEnv:
         return obs, rew, (self.sim_step - 1) >= self.simulation_steps
 
     def device_views(self):
-        """(obs [n_envs, n_obs], rewards [n_envs, n_agents]): float32 torch tensors that ALIAS the engine's device buffers."""
+        """(obs [n_envs, n_obs], rewards [n_envs, n_agents]): float32 torch tensors that ALIAS the engine's device buffers -- the
+        normalised ones while ``set_running_norm`` is on (``raw_views`` has the raw ones)."""
         if self._device_views is None:
-            import torch
-
-            eng = self.network.engine()
-            dev = torch.device("cuda", self.network.device)
-            view = lambda which, cols: torch.as_tensor(_DeviceBuffer(eng.rl_device_ptr(which), (self.n_envs, cols), "<f4"), device=dev)
-            self._device_views = (view(1, self.n_obs), view(2, len(self.possible_agents)))
+            self._device_views = self._views(self._norm is not None)
         return self._device_views
 
     def capture(self, policy_fn, on_step=None, generators=(), steps_per_replay=1):
@@ -629,6 +741,7 @@ class GraphedRollout:
             raise RuntimeError("the environment of this rollout is closed")
         if env.sim_step + env.action_gap - 1 > env.simulation_steps:
             raise IndexError("episode is over; call reset()")
+        self.obs, self.rew = env.device_views()      # (set_running_norm switches them; a stale graph is noticed by its signature below)
         eng = env.network._flush() if not env.network.engine().rl_clocked() else env.network.engine()
         fits = env.sim_step + self.n * env.action_gap - 1 <= env.simulation_steps
         with torch.cuda.device(self.dev):
@@ -777,8 +890,9 @@ class PedNetParallelEnv:
                     row[0, sl] = np.asarray(actions[aid], dtype=np.float64).reshape(-1)
         obs, rew, term, trunc, _ = self._vec.step(row)
         rewards = {a: float(rew[0, i]) for i, a in enumerate(self.possible_agents)}
-        for a, r in rewards.items():
-            self._cumulative_rewards[a] += r
+        true = rew[0] if self._vec._norm is None else self._vec.true_rewards()[0]     # the env's own bookkeeping counts raw rewards
+        for i, a in enumerate(self.possible_agents):
+            self._cumulative_rewards[a] += float(true[i])
         return (self._dict(obs[0]), rewards, {a: term for a in self.possible_agents},
                 {a: False for a in self.possible_agents}, self._infos())
 
@@ -866,6 +980,10 @@ class MultiScenarioVecEnv:
             g.network.current_step = g.sim_step - 1
             g.network._widths_stale = True
         return obs, rew, (g0.sim_step - 1) >= g0.simulation_steps, False, {}
+
+    def set_running_norm(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv does not run the running normalisation: its groups are separate engines with statistics of "
+                         "their own")
 
     def close(self):
         for g in self.groups:

@@ -27,15 +27,18 @@ except Exception:  # noqa: BLE001
 
 class PedNetSB3VecEnv(_Base):
     def __init__(self, dataset, n_envs=1, randomize=False, normalize_obs=True, obs_mode="option1", action_gap=1, seed=0,
-                 detailed_infos=False, **kw):
+                 detailed_infos=False, running_norm=None, **kw):
         """``randomize``: every reset draws a new scenario per env (``reset(options={'randomize': True})``: the reference's random
         stream up to 64 envs, drawn on the device above -- ``VecPedNetEnv.randomize``); the reference's ``make_env(randomize=...)``
         accepts the flag and never uses it (rl/train_ppo_sb3.py:143-169).  ``detailed_infos``: every step's info dicts carry what the
         reference's wrapper reports (``step``, ``cumulative_reward`` of the first agent, ``individual_rewards``) -- 2 us per env per
         step of host time; off, a step's infos are empty dicts except at the end of an episode.  Other keywords go to ``VecPedNetEnv``
-        (``reward_mode``, ``history``, ``data_dir``, ``device`` ...)."""
+        (``reward_mode``, ``history``, ``data_dir``, ``device`` ...).  ``running_norm``: True, or a dict of ``VecPedNetEnv.set_running_norm``
+        keywords -- observations and rewards then come normalised by the batch's running statistics on the device."""
         self.vec = VecPedNetEnv(dataset, n_envs=n_envs, obs_mode=obs_mode, normalize_obs=normalize_obs, action_gap=action_gap,
                                 seed=seed, **kw)
+        if running_norm:
+            self.vec.set_running_norm(**(running_norm if isinstance(running_norm, dict) else {}))
         self.agents = list(self.vec.possible_agents)
         self.randomize, self.detailed_infos = bool(randomize), bool(detailed_infos)
         observation_space = _make_box(-np.inf, np.inf, (self.vec.n_obs,))                     # :62-67
