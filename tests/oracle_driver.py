@@ -66,10 +66,11 @@ def lib():
 class Oracle:
     """One replica of the CPU restatement."""
 
-    def __init__(self, model: dict, seed=0, replica=0, mode="philox"):
+    def __init__(self, model: dict, seed=0, replica=0, mode="philox", desc=None):
+        """desc: build_model_desc(model), where many replicas of one model share it (the oracle copies what it keeps)"""
         self.L = lib()
         self.model = model
-        desc, self._keep = build_model_desc(model)
+        desc, self._keep = desc or build_model_desc(model)
         self.h = C.c_void_p(self.L.pedn_oracle_create(C.byref(desc), int(seed), int(replica),
                                                       {"philox": 0, "meanfield": 1}[mode]))
         self.T1 = int(model["T"]) + 1

@@ -10,6 +10,7 @@ from golden_util import ALL_FIELDS, DIGEST_CASES, Golden, apply_mutation, build_
 from pednstream_amd import engine as eng
 from pednstream_amd.flatten import flatten_network
 from pednstream_amd.network import LINK_FIELDS
+from sparse_oracle import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -123,7 +124,8 @@ def test_engine_reproduces_full_horizon_reference_runs(case):
 
 def test_config2_nine_intersections_256_replicas_vs_oracle_and_goldens():
     """BASELINE config #2: nine_intersections x 256 replicas, per-replica demand and RNG key; replicas 0..3 against the
-    reference goldens, replicas 0..7 and 255 against the CPU oracle, all bit-exact (f32 fields included)."""
+    reference goldens, replicas 0..7 and 255 against the CPU oracle, all bit-exact (f32 fields included; against the oracle by bits: the
+    sign of a zero counts)."""
     R, steps = 256, 160
     g0 = Golden("nine_replica0")
     net = build_network(g0, n_replicas=R, rng_seed=0)
@@ -146,7 +148,7 @@ def test_config2_nine_intersections_256_replicas_vs_oracle_and_goldens():
         o.run(1, steps)
         for name in ALL_FIELDS:
             mine = blocks[name][:, :e.n_links, r].T
-            assert np.array_equal(mine, o.field(name)[:e.n_links, :steps]), (r, name)
+            assert_same_bits(mine, o.field(name)[:e.n_links, :steps], f"replica {r}, {name}", "[link, t]")
     net.close()
 
 
@@ -154,7 +156,7 @@ def test_config2_nine_intersections_256_replicas_vs_oracle_and_goldens():
                                                  ("delft", 192, 500), ("melbourne", 256, 500), ("45_intersections", 128, 700),
                                                  ("nine_intersections", 64, 500), ("small_network", 64, 500)])
 def test_engine_equals_oracle_on_large_networks(name, replicas, steps):
-    """Same seeded inputs through the HIP path and the CPU oracle; sampled replicas, all fields bit-exact."""
+    """Same seeded inputs through the HIP path and the CPU oracle; sampled replicas, all fields equal by bits (-0.0 is not +0.0)."""
     from pednstream_amd import NetworkEnvGenerator
     from golden_util import DATA
 
@@ -170,7 +172,7 @@ def test_engine_equals_oracle_on_large_networks(name, replicas, steps):
         for fname in ALL_FIELDS:
             fid = LINK_FIELDS[fname][0]
             mine = e.read_block(fid, 0, steps, rep0=r, rep1=r + 1)[:, :, 0].T
-            assert np.array_equal(mine[:e.n_links], o.field(fname)[:e.n_links, :steps]), (r, fname)
+            assert_same_bits(mine[:e.n_links], o.field(fname)[:e.n_links, :steps], f"replica {r}, {fname}", "[link, t]")
     net.close()
 
 
@@ -685,9 +687,9 @@ def test_fuzz_random_networks_engine_equals_oracle(fuse_tp, general, lds_limit, 
                 continue                 # after a raise site the reference stops; values past it are not defined
             for fname in ALL_FIELDS:
                 mine = e.read_block(LINK_FIELDS[fname][0], 0, T, rep0=r, rep1=r + 1)[:, :, 0].T
-                assert np.array_equal(mine[:e.n_links], o.field(fname)[:e.n_links, :T]), (seed, r, fname)
+                assert_same_bits(mine[:e.n_links], o.field(fname)[:e.n_links, :T], f"seed {seed}, replica {r}, {fname}", "[link, t]")
             tf = np.concatenate([e.get_turning_fractions(nd.index, r) for nd in net.nodes.values()])
-            assert np.array_equal(tf, o.tf()), (seed, r)
+            assert_same_bits(tf, o.tf(), f"seed {seed}, replica {r}, turning fractions", "[turn]")
             ran += 1
         net.close()
     assert ran >= 60
