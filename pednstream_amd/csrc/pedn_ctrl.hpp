@@ -36,26 +36,6 @@ struct CtrlView {
   int32_t RS;               // replica stride of ring / count rows
 };
 
-// np.add.reduce of float32 values v(0..n-1), n <= 128: a sequential sum below 8 values, NumPy's pairwise_sum block above
-template <class F>
-__device__ __forceinline__ float numpy_sum_f32(int n, F v) {
-  if (n < 8) {
-    float s = 0.0f;
-    for (int i = 0; i < n; ++i) s = s + v(i);
-    return s;
-  }
-  float r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = v(j);
-  int i = 8;
-  for (; i < n - (n % 8); i += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = r[j] + v(i + j);
-  float s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) s = s + v(i);
-  return 0.0f + s;
-}
-
 template <bool CTRL>
 __device__ __forceinline__ void ctrl_decide(const CtrlView& cv, const RlView& q, int ag, int type, int n, int r, const float* o,
                                             const float (*sD)[64], const float (*sG)[64], int lane, float reward_sum) {

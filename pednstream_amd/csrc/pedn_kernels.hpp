@@ -1430,6 +1430,26 @@ __global__ void rl_apply_kernel(DevView v, RlView q) {
 // CTRL (the controller twins ctrl_observe_kernel / ctrl_link_turn_kernel, pedn_ctrl.hpp): wave 0 also adds the reward to the episode sums
 // and computes the agent's next action from the observation it has just written; the gate widths take a fourth LDS array
 #define PEDN_CTRL_LDS_FLOATS (4 * PEDN_MAX_DEGREE * 64)
+// np.add.reduce of float32 values v(0..n-1), n <= 128: a sequential sum below 8 values, NumPy's pairwise_sum block above
+template <class F>
+__device__ __forceinline__ float numpy_sum_f32(int n, F v) {
+  if (n < 8) {
+    float s = 0.0f;
+    for (int i = 0; i < n; ++i) s = s + v(i);
+    return s;
+  }
+  float r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = v(j);
+  int i = 8;
+  for (; i < n - (n % 8); i += 8)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = r[j] + v(i + j);
+  float s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) s = s + v(i);
+  return 0.0f + s;
+}
+
 struct CtrlView;
 template <bool CTRL>
 __device__ __forceinline__ void ctrl_decide(const CtrlView& cv, const RlView& q, int ag, int type, int n, int r, const float* o,
@@ -1515,18 +1535,16 @@ __device__ __forceinline__ void rl_observe_body(const DevView& v, const RlView& 
     float reward = 0.0f;
     bool rewarded = false;
     if (type == 1) {  // reward terms in link order, float32 throughout (pz_pednet_env.py:557-577)
-      float lr = 0.0f, dens_sum = 0.0f;
-      for (int i = 0; i < n; ++i) {
+      float lr = 0.0f;
+      for (int i = 0; i < n; ++i) {  // a Python loop over the links: sequential
         const float d = sD[i][lane];
         lr = (i == 0) ? 0.0f - sT[i][lane] : lr - sT[i][lane];
         if (d > 4.0f) lr = lr - 10.0f * (d - sKc[i][lane]);
-        dens_sum = (i == 0) ? d : dens_sum + d;
       }
-      if (n > 1) {  // np.mean of float32: sequential float32 sum / n
-        const float avg = dens_sum / (float)n;
-        float dsum = 0.0f;
-        for (int i = 0; i < n; ++i) { const float d = fabsf(sD[i][lane] - avg); dsum = (i == 0) ? d : dsum + d; }
-        lr = lr - 10.0f * (dsum / (float)n);
+      if (n > 1) {  // two np.mean of float32 values (:573-574): NumPy's summation order, which at 8 links is not the sequential one
+        const float avg = numpy_sum_f32(n, [&](int i) { return sD[i][lane]; }) / (float)n;
+        const float dev = numpy_sum_f32(n, [&](int i) { return fabsf(sD[i][lane] - avg); }) / (float)n;
+        lr = lr - 10.0f * dev;
       }
       reward = lr;
       rewarded = true;

@@ -11,6 +11,8 @@ FPL = {"option1": 3, "option2": 4, "option3": 5, "option4": 2, "option5": 7}
 
 
 class RlOracle:
+    mean = staticmethod(np.mean)     # the reward's two means (pz_pednet_env.py:573-574); tests/wide_agents.py swaps in another order
+
     def __init__(self, net, model, spec, obs_mode, normalize, action_gap, seed=0, replica=0, reward_mode="reference",
                  link_kc=None, link_kj=None):
         """spec: list of {"id", "type", "links": [link ids "u_v"]} in agent order.  link_kc / link_kj: k_critical / k_jam per
@@ -116,8 +118,8 @@ class RlOracle:
                     elif self.obs_mode == "option3":
                         x[s] /= 6.0; x[s + 1] /= 20.0; x[s + 2] /= 20.0
             if len(dens_all) > 1:
-                avg = np.mean(dens_all)
-                lr -= 10.0 * np.mean(np.abs(np.array(dens_all) - avg))
+                avg = self.mean(dens_all)
+                lr -= 10.0 * self.mean(np.abs(np.array(dens_all) - avg))
             obs.append(x)
             rewards.append(np.float32(lr))
         if self.reward_mode == "reference":           # `return rewards` inside the loop, pz_pednet_env.py:581

@@ -14,7 +14,10 @@ from pednstream_amd.agents import RuleBasedGaterAgent, RuleBasedSeparatorAgent
 from pednstream_amd.evaluation import evaluate_agents, summarize_runs
 
 CTRL_CASES = ["ctrl_nine_gate3", "ctrl_one_gate3", "ctrl_small_gate08", "ctrl_nine_gate3_g2n", "ctrl_corridor_sep",
-              "ctrl_corridor_sep_smooth", "ctrl_corridor_sep_smooth_2ep"]
+              "ctrl_corridor_sep_smooth", "ctrl_corridor_sep_smooth_2ep",
+              # a gater with 8 links (threshold 3 and 0.0) and moving-average windows other than 5 (tests/test_wide_agents_host.py)
+              "ctrl_hub8_gate", "ctrl_hub8_gate0", "ctrl_corridor_sep_w1", "ctrl_corridor_sep_w8", "ctrl_corridor_sep_w13",
+              "ctrl_corridor_sep_w32"]
 
 
 def load(case):

@@ -83,12 +83,14 @@ def test_controlled_steps_reproduce_the_reference_fixture(case):
 _host_loop = {}
 
 
-def host_loop_episode(case, B):
+def host_loop_episode(case, B, replicas=None):
     """The same episode for B envs through ``step`` with one set of numpy agents per env (the reference's evaluation loop, env by
-    env): final observations, the last rewards and the float32 episode sums."""
-    if (case, B) not in _host_loop:
+    env): final observations, the last rewards and the float32 episode sums.  replicas: only these envs have agents (the others
+    get no action; envs do not interact) and only their rows are returned, in this order."""
+    if (case, B, replicas) not in _host_loop:
         g, info, env = make_env(case, B)
-        agents = [device_agents(env, info) for _ in range(B)]
+        chosen = range(B) if replicas is None else replicas
+        agents = {r: device_agents(env, info) for r in chosen}
         ep = np.zeros((B, len(env.possible_agents)), np.float32)
         for e in range(info["episodes"]):
             obs, _ = env.reset()
@@ -96,14 +98,14 @@ def host_loop_episode(case, B):
             done = False
             while not done:
                 row = np.full((B, env.n_actions), np.nan)
-                for r in range(B):
+                for r in chosen:
                     for aid, ag in agents[r].items():
                         row[r, env.action_slices[aid]] = ag.take_action(obs[r, env.obs_slices[aid]], deterministic=True)
                 obs, rew, done, _, _ = env.step(row)
                 ep = ep + rew
-        _host_loop[(case, B)] = (obs, rew, ep)
+        _host_loop[(case, B, replicas)] = tuple(x[list(chosen)] for x in (obs, rew, ep))
         env.close()
-    return _host_loop[(case, B)]
+    return _host_loop[(case, B, replicas)]
 
 
 @pytest.mark.parametrize("case,B,plan", [("ctrl_nine_gate3", B, p) for B in (1, 64, 320, 2048) for p in PLANS] +
@@ -112,7 +114,8 @@ def host_loop_episode(case, B):
                          [("ctrl_small_gate08", 2048, "default"), ("ctrl_one_gate3", 320, "default")])
 def test_whole_episodes_of_many_envs(case, B, plan, monkeypatch):
     """step_controlled() to the end of the episode in one call: replica 0 against the fixture, the first 64 replicas against the
-    same episode stepped through ``step`` with the numpy agents."""
+    same episode stepped through ``step`` with the numpy agents -- and, beyond one group of 64, the replicas B // 2 and B // 2 + 63 (the
+    second half-batch chain under PEDN_RL_CHAINS=2) and B - 1 (the last segment) against such a loop over just those replicas."""
     g, info, env = make_env(case, B, monkeypatch, plan)
     z = g.z
     env.set_controllers(device_agents(env, info))
@@ -129,6 +132,10 @@ def test_whole_episodes_of_many_envs(case, B, plan, monkeypatch):
     h_obs, h_rew, h_ep = host_loop_episode(case, 64)
     assert same(obs[:n], h_obs[:n]) and same(rew[:n], h_rew[:n]) and same(ep[:n], h_ep[:n])
     env.close()
+    if B > 64:
+        far = (B // 2, B // 2 + 63, B - 1)
+        h_obs, h_rew, h_ep = host_loop_episode(case, B, far)
+        assert same(obs[list(far)], h_obs) and same(rew[list(far)], h_rew) and same(ep[list(far)], h_ep)
 
 
 def test_controlled_episode_in_stretches_and_with_recent_history():

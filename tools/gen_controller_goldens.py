@@ -8,6 +8,7 @@ Modelled on oracle/gen_golden.py:rl_case: the reference's ActionApplier / Observ
 take_action on every observation until the episode terminates, episode_true_rewards[a] = 0.0; += rewards[a].  Every fixture holds
 per-step actions, observations, rewards and episode sums, and the digests of the 13 per-link arrays at every time index.
 """
+import copy
 import importlib.util
 import json
 import os
@@ -15,10 +16,14 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
 import ref_harness as rh  # noqa: E402  (sets the numpy environment before numpy is imported)
 from gen_golden import save, step_digests  # noqa: E402
 
 import numpy as np  # noqa: E402
+
+import wide_agents as wa  # noqa: E402  (the hub with 8 spokes)
 
 NP_SEED = 20261003
 
@@ -33,8 +38,10 @@ def rule_based_module():
 
 
 def controller_case(case, name, obs_mode="option2", normalize=False, action_gap=1, threshold=3, smoothing=None, episodes=1,
-                    seed=0, replica=0):
-    """smoothing None: gaters at `threshold`; False / True: separators without / with a moving average (buffer_size 5)."""
+                    seed=0, replica=0, buffer_size=5, direct=None):
+    """smoothing None: gaters at `threshold`; False / True: separators without / with a moving average over `buffer_size` values.
+    direct: (adjacency, params, origins, destinations) of a network built with the reference's Network itself instead of scenario
+    `name` (oracle/gen_golden.py:direct_case)."""
     ref = rh.load_reference()
     rb = rule_based_module()
     agents = None
@@ -43,7 +50,11 @@ def controller_case(case, name, obs_mode="option2", normalize=False, action_gap=
     state = static = None
     for e in range(episodes):
         np.random.seed(NP_SEED)                    # the same demand every episode (a reset without randomisation)
-        net = ref["env"].NetworkEnvGenerator().create_network(name)
+        if direct is None:
+            net = ref["env"].NetworkEnvGenerator().create_network(name)
+        else:
+            adj, params, origins, dests = direct
+            net = ref["network"].Network(np.array(adj), copy.deepcopy(params), origin_nodes=list(origins), destination_nodes=list(dests))
         if static is None:
             static = rh.dump_static(net)
         env = rh.RefEnvShim(net, obs_mode=obs_mode, normalize_obs=normalize, action_gap=action_gap)
@@ -54,7 +65,7 @@ def controller_case(case, name, obs_mode="option2", normalize=False, action_gap=
             for a in ids:
                 if am.get_agent_type(a) == "sep":
                     if smoothing is not None:
-                        agents[a] = rb.RuleBasedSeparatorAgent(am.get_separator_links(a)[0].width, use_smoothing=smoothing, buffer_size=5)
+                        agents[a] = rb.RuleBasedSeparatorAgent(am.get_separator_links(a)[0].width, use_smoothing=smoothing, buffer_size=buffer_size)
                 elif smoothing is None:
                     agents[a] = rb.RuleBasedGaterAgent(am.get_gater_outgoing_links(a), obs_mode, threshold_density=threshold)
             spec = []
@@ -103,7 +114,10 @@ def controller_case(case, name, obs_mode="option2", normalize=False, action_gap=
                        if isinstance(ag, rb.RuleBasedGaterAgent) else
                        {"kind": "sep", "width": ag.road_width, "use_smoothing": ag.use_smoothing, "buffer_size": ag.buffer_size})
                    for a, ag in agents.items()}
-    info = {"scenario": name, "seed": seed, "replica": replica, "mode": "philox", "np_seed": NP_SEED, "mutations": [],
+    where = {"scenario": name} if direct is None else {
+        "scenario": None, "adjacency": np.array(direct[0]).tolist(), "params": direct[1], "origin_nodes": list(direct[2]),
+        "destination_nodes": list(direct[3]), "tf_nodes": [], "tf_values": []}
+    info = {**where, "seed": seed, "replica": replica, "mode": "philox", "np_seed": NP_SEED, "mutations": [],
             "rl": {"obs_mode": obs_mode, "normalize": normalize, "action_gap": action_gap, "agents": spec},
             "controllers": controllers, "episodes": episodes, "env_steps": len(acts) // episodes}
     save(case, static, payload, {"draws": {}, "steps_run": steps_run}, info)
@@ -117,6 +131,12 @@ CASES = {
     "ctrl_corridor_sep": lambda: controller_case("ctrl_corridor_sep", "long_corridor", smoothing=False),
     "ctrl_corridor_sep_smooth": lambda: controller_case("ctrl_corridor_sep_smooth", "long_corridor", smoothing=True),
     "ctrl_corridor_sep_smooth_2ep": lambda: controller_case("ctrl_corridor_sep_smooth_2ep", "long_corridor", smoothing=True, episodes=2),
+    "ctrl_hub8_gate": lambda: controller_case("ctrl_hub8_gate", None, threshold=3, direct=wa.hub8(**wa.HUB_CTRL)),
+    "ctrl_hub8_gate0": lambda: controller_case("ctrl_hub8_gate0", None, threshold=0.0, direct=wa.hub8(**wa.HUB_CTRL)),
+    "ctrl_corridor_sep_w1": lambda: controller_case("ctrl_corridor_sep_w1", "long_corridor", smoothing=True, buffer_size=1),
+    "ctrl_corridor_sep_w8": lambda: controller_case("ctrl_corridor_sep_w8", "long_corridor", smoothing=True, buffer_size=8),
+    "ctrl_corridor_sep_w13": lambda: controller_case("ctrl_corridor_sep_w13", "long_corridor", smoothing=True, buffer_size=13, episodes=2),
+    "ctrl_corridor_sep_w32": lambda: controller_case("ctrl_corridor_sep_w32", "long_corridor", smoothing=True, buffer_size=32),
 }
 
 if __name__ == "__main__":
