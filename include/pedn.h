@@ -444,6 +444,43 @@ int pedn_rl_norm_set_stats(pedn_sim* sim, const double* mean, const double* var,
 void* pedn_rl_norm_device_ptr(pedn_sim* sim, int32_t which);
 int pedn_rl_fetch_raw(pedn_sim* sim, float* obs, float* rewards);
 
+/* ---- on-policy rollout store and advantage estimates on the device (rl/agents/PPO_org.py:201-354,518-567; rl/rl_utils.py:1754-1773) ----
+ * A device-resident store of `capacity` transitions of every env, filled by ONE launch per policy step, and the reference's TD targets,
+ * GAE and advantage normalisation for all n_envs x n_agents trajectories.  The contract (restated in numpy by
+ * tests/rollout_model.py), IEEE binary32, nothing fused:
+ *   td_target[t] = r[t] + (f32(gamma) * v[t + 1]) * (1 - done[t]),  td_delta[t] = td_target[t] - v[t]
+ *   c = f32(gamma * lmbda) (the product in binary64); carry = +0; t = T - 1 .. 0: carry = c * carry + td_delta[t], adv[t] = carry
+ * (the carry is not masked by done: a fill is one episode, or a prefix of one).  With one env this is the reference's compute_gae bit
+ * for bit.  Normalised advantages: per agent over all T * n_envs entries in binary64, (x - mean) / (std + 1e-8) with the unbiased std;
+ * sums over the env axis in the fixed order of the running normalisation, the T row sums added in increasing t.
+ * Arrays, every one [row][env][...]: 0 actions f64 [cap][R][n_actions], 1 values f32 [cap + 1][R][n_agents] (row t = V(s_t) as given to
+ * the record of row t; row `rows` = the bootstrap value of pedn_rollout_finish), 2 rewards f32 [cap][R][n_agents], 3 done f32 [cap][R],
+ * 4 observations f32 [cap + 1][R][n_obs] (NULL unless store_obs; row 0 = the observation at pedn_rollout_begin, row k + 1 = the one
+ * behind step k), 5 td_target, 6 advantages, 7 normalised advantages f32 [cap][R][n_agents], 8 state int32 [4] = cursor, ticket,
+ * overflow.  Observations and rewards are read from the buffers pedn_rl_fetch hands out (the normalised rows while pedn_rl_norm_configure
+ * has the normalisation on).
+ *   pedn_rollout_configure   allocates the store (a previous one is freed).  pedn_rl_configure drops it; pedn_rl_clock_signature covers it.
+ *   pedn_rollout_begin       cursor = 0, overflow = 0, observation row 0 = the current observation; on pedn_stream()
+ *   pedn_rollout_record      one launch on `stream` (NULL = pedn_stream()); actions f64 [R][n_actions] and values f32 [R][n_agents] are
+ *                            device pointers (NULL = zeros).  done = term, or, inside a clocked section, whether the device clock stands
+ *                            at the horizon.  No allocation, no synchronisation, no event query: safe under stream capture, and the
+ *                            arguments are constant, so a captured record is replayed with the step.  A record beyond the capacity
+ *                            writes nothing and raises the overflow flag.
+ *   pedn_rollout_finish      synchronises the device; rows = min(cursor, capacity); values[rows] = last_values (device, NULL = zeros)
+ *   pedn_rollout_compute     td_target and advantages of rows [0, rows) (one launch), normalised advantages when `normalize` (three more)
+ *   pedn_gae                 the same arithmetic on plain device pointers, no handle: rewards / dones / td_target / adv [T][lanes],
+ *                            values [T + 1][lanes]; one launch on `stream`.  values = NULL: `rewards` holds td_delta itself (the argument
+ *                            of the reference's compute_gae), only adv is written */
+int pedn_rollout_configure(pedn_sim* sim, int32_t capacity, int32_t store_obs);
+int pedn_rollout_free(pedn_sim* sim);
+int pedn_rollout_begin(pedn_sim* sim);
+int pedn_rollout_record(pedn_sim* sim, const double* actions, const float* values, int32_t term, void* stream);
+int pedn_rollout_finish(pedn_sim* sim, const float* last_values, int32_t* rows, int32_t* overflow);
+int pedn_rollout_compute(pedn_sim* sim, double gamma, double lmbda, int32_t normalize);
+void* pedn_rollout_device_ptr(pedn_sim* sim, int32_t which);
+int pedn_gae(const float* rewards, const float* values, const float* dones, int32_t T, int32_t lanes, double gamma, double lmbda,
+             float* td_target, float* adv, void* stream);
+
 /* ---- rule-based controllers on the device (rl/agents/rule_based.py, evaluated by rl/rl_utils.py:1513-1750) ----------------------
  * A controller per agent of the pedn_rl_configure agent set computes the agent's next action from the float32 observation the step has
  * just written, inside the observation part of the step's second launch (no extra launch, no host round trip between env steps):

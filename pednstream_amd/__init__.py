@@ -4,10 +4,12 @@ Public surface (mirrors the reference's for this path):
     NetworkEnvGenerator   scenario directory -> Network            (reference src/utils/env_loader.py)
     Network               network_loading(t), links, nodes, ...    (reference src/LTM/network.py)
     load_config           YAML/JSON scenario -> config dict         (reference src/utils/config.py)
+    RolloutStore, gae, compute_gae   on-policy rollouts and GAE on the device (reference rl/agents/PPO_org.py, rl/rl_utils.py)
 """
 from .config import load_config
 from .env_loader import NetworkEnvGenerator
 from .network import Network
+from .rollout import RolloutStore, compute_gae, gae
 
-__all__ = ["NetworkEnvGenerator", "Network", "load_config"]
+__all__ = ["NetworkEnvGenerator", "Network", "load_config", "RolloutStore", "gae", "compute_gae"]
 __version__ = "0.1.0"

@@ -49,7 +49,9 @@ def install(force: bool = False):
     rl.agents.rule_based = mod("rl.agents.rule_based", BaseAgent=agents.BaseAgent, RuleBasedGaterAgent=agents.RuleBasedGaterAgent,
                                RuleBasedSeparatorAgent=agents.RuleBasedSeparatorAgent)
     # `from rl.rl_utils import RunningNormalizeWrapper` (rl/train_rl.py, rl/evaluate_and_visualize.py): statistics on the device
-    from . import normalize
+    # ... and `from rl.rl_utils import compute_gae` (rl/agents/PPO_org.py and its siblings): the device kernel
+    from . import normalize, rollout
 
-    rl.rl_utils = mod("rl.rl_utils", RunningNormalizeWrapper=normalize.RunningNormalizeWrapper, RunningMeanStd=normalize.RunningMeanStd)
+    rl.rl_utils = mod("rl.rl_utils", RunningNormalizeWrapper=normalize.RunningNormalizeWrapper, RunningMeanStd=normalize.RunningMeanStd,
+                      compute_gae=rollout.compute_gae)
     return src

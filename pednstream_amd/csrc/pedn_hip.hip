@@ -22,6 +22,7 @@
 #include "pedn_kernels.hpp"
 #include "pedn_ctrl.hpp"
 #include "pedn_norm.hpp"
+#include "pedn_rollout.hpp"
 
 // ------------------------------------------------------------------------------------------------- host side
 static thread_local std::string g_last_error;
@@ -145,6 +146,11 @@ struct pedn_sim {
   NormView nv = {};
   bool norm_on = false, norm_alloc = false;
   std::vector<int32_t> h_norm_tracked, h_norm_agent;   // [O]: tracked mask, agent of every column
+  // rollout store (pedn_rollout_*, pedn_rollout.hpp): the view its launches carry (zeroed while there is none) and its own allocations
+  RolloutView ro = {};
+  bool ro_on = false, ro_begun = false, ro_finished = false;
+  int ro_rows = 0;
+  std::vector<void*> ro_allocs;
 };
 static void metrics_free(pedn_sim* s);
 
@@ -519,6 +525,8 @@ static node_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf);
 static int clock_end(pedn_sim* s);
 static void norm_launch(pedn_sim* s, hipStream_t st, int rewards, int term);
 static int norm_reset_returns(pedn_sim* s);
+static void rollout_drop(pedn_sim* s);
+static void rollout_sources(pedn_sim* s);
 static void prewarm_chains(pedn_sim* s);
 static int fork_chains(pedn_sim* s, int n);
 
@@ -1114,6 +1122,7 @@ int pedn_destroy(pedn_sim* s) {
   if (s->stream2) hipStreamSynchronize(s->stream2);
   if (s->stream) hipStreamSynchronize(s->stream);
   metrics_free(s);
+  rollout_drop(s);
   for (void* p : s->allocs) hipFree(p);
   if (s->rl_pin) hipHostFree(s->rl_pin);
   for (pedn_sim::Stage& st : s->stage) {
@@ -2308,6 +2317,7 @@ int pedn_rl_configure(pedn_sim* s, const pedn_rl_desc* d, int32_t* n_actions, in
   s->ctrl_ready = s->ctrl_any = false;   // controllers belong to an agent set: configure them again
   s->norm_on = s->norm_alloc = false;    // so does the running normalisation
   memset(&s->nv, 0, sizeof s->nv);
+  rollout_drop(s);                       // and a rollout store (its rows have the agent set's widths)
   if (n_actions) *n_actions = A;
   if (n_obs) *n_obs = O;
   return PEDN_OK;
@@ -2599,6 +2609,9 @@ uint64_t pedn_rl_clock_signature(pedn_sim* s) {
   const int64_t on = s->norm_on;   // the normalisation launch and its view (zeroed while off; configure fills every byte it hashes)
   mix(&on, sizeof on);
   mix(&s->nv, sizeof s->nv);
+  const int64_t store = s->ro_on;   // a record launch captured with the step carries the store's view (zeroed while there is none)
+  mix(&store, sizeof store);
+  mix(&s->ro, sizeof s->ro);
   return h;
 }
 
@@ -2678,6 +2691,7 @@ int pedn_rl_norm_configure(pedn_sim* s, int32_t norm_obs, int32_t norm_reward, d
       s->nv.obs_n = keep.obs_n; s->nv.rew_n = keep.rew_n; s->nv.mean = keep.mean; s->nv.var = keep.var; s->nv.count = keep.count;
       s->nv.ret = keep.ret; s->nv.ret_stats = keep.ret_stats; s->nv.tracked = keep.tracked;
     }
+    rollout_sources(s);
     return PEDN_OK;
   }
   if (s->ctrl_ready) return fail(s, PEDN_E_ARG, "controllers and the running normalisation cannot be combined");
@@ -2719,6 +2733,7 @@ int pedn_rl_norm_configure(pedn_sim* s, int32_t norm_obs, int32_t norm_reward, d
   HIP_TRY(s, hipMemset(n.ret, 0, (size_t)s->v.R * q.n_agents * sizeof(double)));
   if ((rc = norm_init_stats(s)) != PEDN_OK) return rc;
   s->norm_on = true;
+  rollout_sources(s);
   return PEDN_OK;
 }
 
@@ -2782,6 +2797,174 @@ void* pedn_rl_norm_device_ptr(pedn_sim* s, int32_t which) {
     case 6: return n.ret_stats;
   }
   return nullptr;
+}
+
+// ---- rollout store and advantage estimates on the device (pedn_rollout.hpp) ----------------------------------------
+static void rollout_drop(pedn_sim* s) {
+  for (void* p : s->ro_allocs) hipFree(p);
+  s->ro_allocs.clear();
+  memset(&s->ro, 0, sizeof s->ro);
+  s->ro_on = s->ro_begun = s->ro_finished = false;
+  s->ro_rows = 0;
+}
+
+// the rows a record launch copies are the ones the fetches hand out
+static void rollout_sources(pedn_sim* s) {
+  if (!s->ro_on) return;
+  s->ro.obs_src = s->norm_on ? s->nv.obs_n : s->rl.obs;
+  s->ro.rew_src = s->norm_on ? s->nv.rew_n : s->rl.rew;
+}
+
+static unsigned rollout_blocks(size_t elems) { return (unsigned)std::min<size_t>(std::max<size_t>((elems + 1023) / 1024, 1), 2048); }
+
+int pedn_rollout_free(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: a captured record launch is not replayed over freed rows, pedn_rl_clock_signature)
+  HIP_TRY(s, hipDeviceSynchronize());
+  rollout_drop(s);
+  return PEDN_OK;
+}
+
+int pedn_rollout_configure(pedn_sim* s, int32_t capacity, int32_t store_obs) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  if (capacity < 1) return fail(s, PEDN_E_ARG, "capacity < 1");
+  int rc = pedn_rollout_free(s);
+  if (rc != PEDN_OK) return rc;
+  const RlView& q = s->rl;
+  const size_t N = (size_t)s->v.R, cap = (size_t)capacity, nv = N * q.n_agents;
+  if (nv > 0x7fffffffull) return fail(s, PEDN_E_ARG, "more than 2^31 trajectories");   // (a lane index is an int; rows are addressed in 64 bits)
+  RolloutView r;
+  memset(&r, 0, sizeof r);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
+  auto take = [&](size_t bytes, void** out) -> int {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess) return fail(s, PEDN_E_NOMEM, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    s->ro_allocs.push_back(p);
+    const hipError_t z = hipMemset(p, 0, std::max<size_t>(bytes, 16));
+    if (z != hipSuccess) return fail(s, PEDN_E_DEVICE, std::string("hipMemset: ") + hipGetErrorString(z));
+    *out = p;
+    return PEDN_OK;
+  };
+  if ((rc = take(cap * N * q.A * sizeof(double), (void**)&r.actions)) != PEDN_OK || (rc = take((cap + 1) * nv * sizeof(float), (void**)&r.values)) != PEDN_OK ||
+      (rc = take(cap * nv * sizeof(float), (void**)&r.rewards)) != PEDN_OK || (rc = take(cap * N * sizeof(float), (void**)&r.done)) != PEDN_OK ||
+      (rc = take(cap * nv * sizeof(float), (void**)&r.td_target)) != PEDN_OK || (rc = take(cap * nv * sizeof(float), (void**)&r.adv)) != PEDN_OK ||
+      (rc = take(cap * nv * sizeof(float), (void**)&r.adv_n)) != PEDN_OK || (rc = take(2 * cap * q.n_agents * sizeof(double), (void**)&r.rowsum)) != PEDN_OK ||
+      (rc = take(4 * sizeof(int32_t), (void**)&r.state)) != PEDN_OK ||
+      (store_obs && (rc = take((cap + 1) * N * q.O * sizeof(float), (void**)&r.obs)) != PEDN_OK)) {
+    const std::string keep = s->err;
+    rollout_drop(s);
+    return fail(s, rc, keep);
+  }
+  r.clock = s->d_clock;
+  r.cap = capacity; r.N = s->v.R; r.A = q.n_agents; r.n_actions = q.A; r.n_obs = q.O; r.T = s->v.T1 - 1;
+  s->ro = r;
+  s->ro_on = true;
+  rollout_sources(s);
+  return PEDN_OK;
+}
+
+int pedn_rollout_begin(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro_on) return fail(s, PEDN_E_ARG, "pedn_rollout_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: the cursor goes back behind everything recorded so far)
+  const RolloutView& r = s->ro;
+  hipLaunchKernelGGL(rollout_begin_kernel, dim3(rollout_blocks(r.obs ? (size_t)r.N * r.n_obs : 1)), dim3(256), 0, s->stream, r);
+  HIP_TRY(s, hipGetLastError());
+  s->ro_begun = true;
+  s->ro_finished = false;
+  s->ro_rows = 0;
+  return PEDN_OK;
+}
+
+// (no allocation, no synchronisation, no event query: safe under stream capture)
+int pedn_rollout_record(pedn_sim* s, const double* actions, const float* values, int32_t term, void* stream) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro_on || !s->ro_begun) return fail(s, PEDN_E_ARG, "pedn_rollout_begin has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  const RolloutView& r = s->ro;
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  const size_t widest = (size_t)r.N * std::max(std::max(r.obs ? r.n_obs : 0, 2 * r.n_actions), r.A);
+  hipLaunchKernelGGL(rollout_record_kernel, dim3(rollout_blocks(widest)), dim3(256), 0, st, r, actions, values, s->clocked ? -1 : (term ? 1 : 0));
+  HIP_TRY(s, hipGetLastError());
+  s->ro_finished = false;
+  return PEDN_OK;
+}
+
+int pedn_rollout_finish(pedn_sim* s, const float* last_values, int32_t* rows, int32_t* overflow) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro_on || !s->ro_begun) return fail(s, PEDN_E_ARG, "pedn_rollout_begin has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);   // (ends a clocked section)
+  HIP_TRY(s, hipDeviceSynchronize());   // records may sit on a caller's stream
+  const RolloutView& r = s->ro;
+  int32_t h[4] = {0, 0, 0, 0};
+  HIP_TRY(s, hipMemcpy(h, r.state, sizeof h, hipMemcpyDeviceToHost));
+  const int n = std::min(h[0], r.cap);
+  const size_t nv = (size_t)r.N * r.A;
+  if (last_values) HIP_TRY(s, hipMemcpy(r.values + (size_t)n * nv, last_values, nv * sizeof(float), hipMemcpyDeviceToDevice));
+  else HIP_TRY(s, hipMemset(r.values + (size_t)n * nv, 0, nv * sizeof(float)));
+  HIP_TRY(s, hipDeviceSynchronize());
+  s->ro_rows = n;
+  s->ro_finished = true;
+  if (rows) *rows = n;
+  if (overflow) *overflow = h[2];
+  return PEDN_OK;
+}
+
+static void gae_launch(const float* rew, const float* val, const float* done, int T, int lanes, int done_div, double gamma, double lmbda,
+                       float* td, float* adv, hipStream_t st) {
+  const float g = (float)gamma, c = (float)(gamma * lmbda);   // (the product in binary64, rounded once)
+  const dim3 grid((unsigned)((lanes + 255) / 256));
+  if (val) hipLaunchKernelGGL(rollout_gae_kernel<false>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
+  else hipLaunchKernelGGL(rollout_gae_kernel<true>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
+}
+
+int pedn_rollout_compute(pedn_sim* s, double gamma, double lmbda, int32_t normalize) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro_on || !s->ro_finished) return fail(s, PEDN_E_ARG, "pedn_rollout_finish has not been called");
+  const RolloutView& r = s->ro;
+  const int T = s->ro_rows;
+  if (T < 1) return fail(s, PEDN_E_ARG, "the store is empty");
+  if (normalize && (int64_t)T * r.N < 2) return fail(s, PEDN_E_ARG, "advantage normalisation needs at least two entries per agent");
+  HIP_TRY(s, hipSetDevice(s->device));
+  gae_launch(r.rewards, r.values, r.done, T, r.N * r.A, r.A, gamma, lmbda, r.td_target, r.adv, s->stream);
+  if (normalize) {
+    const dim3 grid((unsigned)((r.A + PEDN_NORM_COLS - 1) / PEDN_NORM_COLS), (unsigned)T);
+    for (int pass = 0; pass < 3; ++pass)   // (a launch per pass: each needs every workgroup's row sums of the one before)
+      hipLaunchKernelGGL(rollout_advnorm_kernel, grid, dim3(1024), 0, s->stream, r.adv, r.adv_n, r.rowsum, T, r.N, r.A, pass);
+  }
+  HIP_TRY(s, hipGetLastError());
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  return PEDN_OK;
+}
+
+void* pedn_rollout_device_ptr(pedn_sim* s, int32_t which) {
+  if (!s || !s->ro_on) return nullptr;
+  const RolloutView& r = s->ro;
+  switch (which) {
+    case 0: return r.actions;
+    case 1: return r.values;
+    case 2: return r.rewards;
+    case 3: return r.done;
+    case 4: return r.obs;
+    case 5: return r.td_target;
+    case 6: return r.adv;
+    case 7: return r.adv_n;
+    case 8: return r.state;
+  }
+  return nullptr;
+}
+
+int pedn_gae(const float* rewards, const float* values, const float* dones, int32_t T, int32_t lanes, double gamma, double lmbda,
+             float* td_target, float* adv, void* stream) {
+  if (!rewards || !adv || (values && (!dones || !td_target))) return fail(nullptr, PEDN_E_ARG, "null argument");
+  if (T < 1 || lanes < 1) return fail(nullptr, PEDN_E_ARG, "T and lanes must be positive");
+  gae_launch(rewards, values, dones, T, lanes, 1, gamma, lmbda, td_target, adv, (hipStream_t)stream);
+  HIP_TRY(nullptr, hipGetLastError());
+  return PEDN_OK;
 }
 
 // ---- rule-based controllers on the device (pedn_ctrl.hpp) ----------------------------------------------------------------------

@@ -192,6 +192,14 @@ def _load():
         "pedn_rl_norm_set_stats": (C.c_int, [P, _F64P, _F64P, _F64P, _F64P]),
         "pedn_rl_norm_device_ptr": (C.c_void_p, [P, C.c_int32]),
         "pedn_rl_fetch_raw": (C.c_int, [P, C.c_void_p, C.c_void_p]),
+        "pedn_rollout_configure": (C.c_int, [P, C.c_int32, C.c_int32]),
+        "pedn_rollout_free": (C.c_int, [P]),
+        "pedn_rollout_begin": (C.c_int, [P]),
+        "pedn_rollout_record": (C.c_int, [P, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+        "pedn_rollout_finish": (C.c_int, [P, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "pedn_rollout_compute": (C.c_int, [P, C.c_double, C.c_double, C.c_int32]),
+        "pedn_rollout_device_ptr": (C.c_void_p, [P, C.c_int32]),
+        "pedn_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     }
     # the version first: a stale or alternate library (PEDN_HIP_LIB) must fail with this message, not with an AttributeError on a symbol
     lib.pedn_abi_version.restype, lib.pedn_abi_version.argtypes = C.c_int, []
@@ -224,7 +232,9 @@ EXPORTS = ["pedn_abi_version", "pedn_last_error", "pedn_create", "pedn_destroy",
            "pedn_metrics_begin", "pedn_metrics_accumulate", "pedn_metrics_read",
            "pedn_ctrl_configure", "pedn_ctrl_observe", "pedn_ctrl_step", "pedn_ctrl_read", "pedn_ctrl_device_ptr",
            "pedn_rl_norm_configure", "pedn_rl_norm_set_training", "pedn_rl_norm_get_stats", "pedn_rl_norm_set_stats", "pedn_rl_norm_device_ptr",
-           "pedn_rl_fetch_raw"]
+           "pedn_rl_fetch_raw",
+           "pedn_rollout_configure", "pedn_rollout_free", "pedn_rollout_begin", "pedn_rollout_record", "pedn_rollout_finish", "pedn_rollout_compute",
+           "pedn_rollout_device_ptr", "pedn_gae"]
 
 
 def _p(a, dtype=np.float64):
@@ -715,6 +725,42 @@ class Engine:
         rew = np.empty((self.n_replicas, self.rl_n_agents), dtype=np.float32)
         self._ck(self._lib.pedn_rl_fetch_raw(self._h, obs.ctypes.data_as(C.c_void_p), rew.ctypes.data_as(C.c_void_p)))
         return obs, rew
+
+    # -- rollout store (include/pedn.h: pedn_rollout_*; pednstream_amd.rollout.RolloutStore builds the arguments)
+    def _ck_arg(self, rc):
+        """A refused argument or call order (PEDN_E_ARG) is a ValueError."""
+        if rc == -1:
+            raise ValueError(self._lib.pedn_last_error(self._h).decode())
+        return self._ck(rc)
+
+    def rollout_configure(self, capacity, store_obs=True):
+        self._ck_arg(self._lib.pedn_rollout_configure(self._h, int(capacity), int(bool(store_obs))))
+
+    def rollout_free(self):
+        self._ck(self._lib.pedn_rollout_free(self._h))
+
+    def rollout_begin(self):
+        self._ck_arg(self._lib.pedn_rollout_begin(self._h))
+
+    def rollout_record(self, actions_ptr, values_ptr=0, terminated=False, stream_ptr=0):
+        """One launch on ``stream_ptr`` (0: the engine's stream); device pointers; safe under stream capture."""
+        p = lambda x: C.c_void_p(int(x)) if x else None
+        self._ck_arg(self._lib.pedn_rollout_record(self._h, p(actions_ptr), p(values_ptr), int(bool(terminated)), p(stream_ptr)))
+
+    def rollout_finish(self, last_values_ptr=0):
+        """(rows, overflow) after everything recorded so far has run."""
+        rows, over = C.c_int32(0), C.c_int32(0)
+        self._ck_arg(self._lib.pedn_rollout_finish(self._h, C.c_void_p(int(last_values_ptr)) if last_values_ptr else None, C.byref(rows), C.byref(over)))
+        return int(rows.value), bool(over.value)
+
+    def rollout_compute(self, gamma, lmbda, normalize=False):
+        self._ck_arg(self._lib.pedn_rollout_compute(self._h, float(gamma), float(lmbda), int(bool(normalize))))
+
+    def rollout_device_ptr(self, which):
+        return self._lib.pedn_rollout_device_ptr(self._h, int(which))
+
+    def ctrl_device_ptr(self, which):
+        return self._lib.pedn_ctrl_device_ptr(self._h, int(which))
 
     def device_ptr(self, field):
         cols, stride = C.c_int64(), C.c_int64()

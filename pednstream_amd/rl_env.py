@@ -204,6 +204,7 @@ class VecPedNetEnv:
         self._controllers = None       # set_controllers: {agent_id: agent or None}
         self._ctrl_reset = False
         self._norm = None              # set_running_norm: the configuration dict while the normalisation is on
+        self._rollout_store = None     # rollout_store: the engine holds one store at a time
 
     # ------------------------------------------------------------------------------------------------ API
     AUTO_VECTORISED_FROM = 65      # randomize(mode="auto"): batches of this many envs and more draw their scenarios on the device
@@ -656,7 +657,7 @@ class VecPedNetEnv:
     def capture(self, policy_fn, on_step=None, generators=(), steps_per_replay=1):
         """A graph-replayable rollout loop: ``policy_fn(obs) -> actions`` (torch ops only; obs is the engine's float32 observation buffer
         [n_envs, n_obs], actions a contiguous float64 CUDA tensor [n_envs, n_actions]) followed by one env step and ``on_step(obs, rewards)``
-        (optional, torch ops only: reward bookkeeping, storing the transition) captured ONCE as a ``torch.cuda.CUDAGraph`` and replayed
+        (optional, torch ops and ``RolloutStore.record`` only: reward bookkeeping, storing the transition) captured ONCE as a ``torch.cuda.CUDAGraph`` and replayed
         per policy step -- see ``GraphedRollout``.  ``generators``: every ``torch.Generator`` the two callables draw from other than the
         default one (torch must know them before the capture: ``CUDAGraph.register_generator_state``).  ``steps_per_replay`` > 1: that
         many consecutive iterations in ONE graph (``GraphedRollout.step`` then advances by that many policy steps; the tail of an episode
@@ -664,6 +665,17 @@ class VecPedNetEnv:
         if self.track_metrics:
             raise RuntimeError("capture() does not track metrics: construct the env with track_metrics=False")
         return GraphedRollout(self, policy_fn, on_step, generators, steps_per_replay)
+
+    def rollout_store(self, capacity=None, store_obs=True):
+        """A device-resident store of this env's transitions with the reference's GAE on top (``pednstream_amd.rollout.RolloutStore``):
+        ``capacity`` rows (default: the policy steps of an episode), ``store_obs``: keep the observations too.  The engine holds one
+        store at a time: a second call replaces the first one's arrays.  A rollout captured before is captured again."""
+        from .rollout import RolloutStore
+
+        self._rollout_store = None
+        store = RolloutStore(self, capacity, store_obs)
+        self._rollout_store = store
+        return store
 
     def _ordered_behind_engine(self):
         """The caller's current torch stream waits (on the device) for everything enqueued on the engine's stream so far."""
@@ -980,6 +992,10 @@ class MultiScenarioVecEnv:
             g.network.current_step = g.sim_step - 1
             g.network._widths_stale = True
         return obs, rew, (g0.sim_step - 1) >= g0.simulation_steps, False, {}
+
+    def rollout_store(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv steps separate engines: a rollout store belongs to one VecPedNetEnv (one per group: "
+                         "env.groups[i].rollout_store())")
 
     def set_running_norm(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv does not run the running normalisation: its groups are separate engines with statistics of "
