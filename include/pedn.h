@@ -481,6 +481,47 @@ void* pedn_rollout_device_ptr(pedn_sim* sim, int32_t which);
 int pedn_gae(const float* rewards, const float* values, const float* dones, int32_t T, int32_t lanes, double gamma, double lmbda,
              float* td_target, float* adv, void* stream);
 
+/* ---- replay store of the off-policy trainers on the device (rl/rl_utils.py:37-50 ReplayBuffer; rl/agents/SAC.py:127-225) ----------
+ * A device-resident ring of transitions of every env that keeps each observation ONCE, filled by ONE launch per policy step, and a
+ * gather of sampled minibatches as stacks of the last `stack_size` observations.  The contract (restated in numpy by
+ * tests/replay_model.py): every begin / push takes the next serial s = 0, 1, ... and writes slot s mod R of the ring, R = capacity +
+ * stack_size + ceil(capacity / episode_steps) + 1.  A RESET row (begin) holds the observation; a STEP row (push) the observation behind
+ * the step, the actions, the rewards, done and `first`, the serial of its episode's RESET row.  State of STEP row s = the frames
+ * max(s - stack_size + i, first), i = 0 .. stack_size - 1; next state = the frames max(s - stack_size + 1 + i, first).  Sampleable: the
+ * newest `capacity` STEP rows whose oldest frame max(s - stack_size, first) is still in the ring (>= head - R): size_rows of them, a
+ * suffix of the STEP rows.  Everything is copied bit for bit.
+ * Arrays: 0 frames f32 [R][envs][n_obs], 1 actions f64 [R][envs][n_actions], 2 rewards f32 [R][envs][n_agents], 3 done f32 [R],
+ * 4 first i64 [R] (-1: a RESET row), 5 step_serial i64 [capacity] (STEP count j mod capacity -> serial), 6 the stacked observation f32
+ * [envs][stack_size][n_obs] (the next state of the newest row, written by the begin / push launch itself), 7 state i64 [10] = head (the
+ * next serial), STEP rows so far, size_rows, first of the running episode, draw counter, error flag, two ticket counters, head mod R, STEP
+ * rows mod capacity.
+ * Observations and rewards are read from the buffers pedn_rl_fetch hands out (the normalised rows while the normalisation is on).
+ *   pedn_replay_configure    allocates the store (a previous one is freed); capacity in rows (one row = one policy step of all envs).
+ *                            pedn_rl_configure drops it; pedn_rl_clock_signature covers it.  It lives beside a rollout store.
+ *   pedn_replay_begin        a RESET row from the current observation; on pedn_stream()
+ *   pedn_replay_push         a STEP row: one launch on `stream` (NULL = pedn_stream()); actions f64 [envs][n_actions] is a device
+ *                            pointer.  done = term, or, inside a clocked section, whether the device clock stands at the horizon.  No
+ *                            allocation, no synchronisation, no event query, constant arguments: a captured push is replayed with the step.
+ *   pedn_replay_sample       one launch on `stream`, capturable like the push.  indices = NULL: `batch` (row, env) pairs drawn with
+ *                            replacement, draw d (the draw counter, advanced by the launch) and sample k from
+ *                            w = philox4x32_10((k, d & 0xffffffff, 0x71, d >> 32), (seed & 0xffffffff, seed >> 32)): STEP count
+ *                            j = (STEP rows so far) - 1 - ((w[0] * size_rows) >> 32), env (w[1] * envs) >> 32.  indices = device i64
+ *                            [batch][2] (serial, env): those pairs, the draw counter stays.  Outputs (device): states / next_states f32
+ *                            [batch][stack_size][obs_w], actions f64 [batch][act_w], rewards f32 [batch][rew_w], dones f32 [batch], idx
+ *                            i64 [batch][2] (NULL: not wanted) -- the observation columns [obs0, obs0 + obs_w) and so on.  A sample that
+ *                            is not sampleable (an empty store, an evicted or RESET serial, an env out of range) writes nothing, reads
+ *                            nothing outside the ring and raises the error flag.
+ *   pedn_replay_size         synchronises the device; state[6] = the first six state words; the error flag is cleared once reported */
+int pedn_replay_configure(pedn_sim* sim, int64_t capacity, int32_t stack_size, int32_t episode_steps, uint64_t seed);
+int pedn_replay_free(pedn_sim* sim);
+int pedn_replay_begin(pedn_sim* sim);
+int pedn_replay_push(pedn_sim* sim, const double* actions, int32_t term, void* stream);
+int pedn_replay_sample(pedn_sim* sim, int64_t batch, const int64_t* indices, int32_t obs0, int32_t obs_w, int32_t act0, int32_t act_w,
+                       int32_t rew0, int32_t rew_w, float* states, double* actions, float* rewards, float* next_states, float* dones,
+                       int64_t* idx, void* stream);
+int pedn_replay_size(pedn_sim* sim, int64_t* state);
+void* pedn_replay_device_ptr(pedn_sim* sim, int32_t which);
+
 /* ---- rule-based controllers on the device (rl/agents/rule_based.py, evaluated by rl/rl_utils.py:1513-1750) ----------------------
  * A controller per agent of the pedn_rl_configure agent set computes the agent's next action from the float32 observation the step has
  * just written, inside the observation part of the step's second launch (no extra launch, no host round trip between env steps):

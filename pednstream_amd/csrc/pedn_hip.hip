@@ -23,6 +23,7 @@
 #include "pedn_ctrl.hpp"
 #include "pedn_norm.hpp"
 #include "pedn_rollout.hpp"
+#include "pedn_replay.hpp"
 
 // ------------------------------------------------------------------------------------------------- host side
 static thread_local std::string g_last_error;
@@ -151,6 +152,10 @@ struct pedn_sim {
   bool ro_on = false, ro_begun = false, ro_finished = false;
   int ro_rows = 0;
   std::vector<void*> ro_allocs;
+  // replay store (pedn_replay_*, pedn_replay.hpp): the same for the off-policy ring; the two stores may live side by side
+  ReplayView rp = {};
+  bool rp_on = false, rp_begun = false;
+  std::vector<void*> rp_allocs;
 };
 static void metrics_free(pedn_sim* s);
 
@@ -527,6 +532,8 @@ static void norm_launch(pedn_sim* s, hipStream_t st, int rewards, int term);
 static int norm_reset_returns(pedn_sim* s);
 static void rollout_drop(pedn_sim* s);
 static void rollout_sources(pedn_sim* s);
+static void replay_drop(pedn_sim* s);
+static void replay_sources(pedn_sim* s);
 static void prewarm_chains(pedn_sim* s);
 static int fork_chains(pedn_sim* s, int n);
 
@@ -1123,6 +1130,7 @@ int pedn_destroy(pedn_sim* s) {
   if (s->stream) hipStreamSynchronize(s->stream);
   metrics_free(s);
   rollout_drop(s);
+  replay_drop(s);
   for (void* p : s->allocs) hipFree(p);
   if (s->rl_pin) hipHostFree(s->rl_pin);
   for (pedn_sim::Stage& st : s->stage) {
@@ -2318,6 +2326,7 @@ int pedn_rl_configure(pedn_sim* s, const pedn_rl_desc* d, int32_t* n_actions, in
   s->norm_on = s->norm_alloc = false;    // so does the running normalisation
   memset(&s->nv, 0, sizeof s->nv);
   rollout_drop(s);                       // and a rollout store (its rows have the agent set's widths)
+  replay_drop(s);                        // and a replay store
   if (n_actions) *n_actions = A;
   if (n_obs) *n_obs = O;
   return PEDN_OK;
@@ -2612,6 +2621,9 @@ uint64_t pedn_rl_clock_signature(pedn_sim* s) {
   const int64_t store = s->ro_on;   // a record launch captured with the step carries the store's view (zeroed while there is none)
   mix(&store, sizeof store);
   mix(&s->ro, sizeof s->ro);
+  const int64_t replay = s->rp_on;   // the same for a captured push launch of the replay store
+  mix(&replay, sizeof replay);
+  mix(&s->rp, sizeof s->rp);
   return h;
 }
 
@@ -2692,6 +2704,7 @@ int pedn_rl_norm_configure(pedn_sim* s, int32_t norm_obs, int32_t norm_reward, d
       s->nv.ret = keep.ret; s->nv.ret_stats = keep.ret_stats; s->nv.tracked = keep.tracked;
     }
     rollout_sources(s);
+    replay_sources(s);
     return PEDN_OK;
   }
   if (s->ctrl_ready) return fail(s, PEDN_E_ARG, "controllers and the running normalisation cannot be combined");
@@ -2734,6 +2747,7 @@ int pedn_rl_norm_configure(pedn_sim* s, int32_t norm_obs, int32_t norm_reward, d
   if ((rc = norm_init_stats(s)) != PEDN_OK) return rc;
   s->norm_on = true;
   rollout_sources(s);
+  replay_sources(s);
   return PEDN_OK;
 }
 
@@ -2965,6 +2979,154 @@ int pedn_gae(const float* rewards, const float* values, const float* dones, int3
   gae_launch(rewards, values, dones, T, lanes, 1, gamma, lmbda, td_target, adv, (hipStream_t)stream);
   HIP_TRY(nullptr, hipGetLastError());
   return PEDN_OK;
+}
+
+// ---- replay store of the off-policy trainers on the device (pedn_replay.hpp) ----------------------------------------
+static void replay_drop(pedn_sim* s) {
+  for (void* p : s->rp_allocs) hipFree(p);
+  s->rp_allocs.clear();
+  memset(&s->rp, 0, sizeof s->rp);
+  s->rp_on = s->rp_begun = false;
+}
+
+// the rows a push launch copies are the ones the fetches hand out
+static void replay_sources(pedn_sim* s) {
+  if (!s->rp_on) return;
+  s->rp.obs_src = s->norm_on ? s->nv.obs_n : s->rl.obs;
+  s->rp.rew_src = s->norm_on ? s->nv.rew_n : s->rl.rew;
+}
+
+int pedn_replay_free(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: a captured push launch is not replayed over freed rows, pedn_rl_clock_signature)
+  HIP_TRY(s, hipDeviceSynchronize());
+  replay_drop(s);
+  return PEDN_OK;
+}
+
+int pedn_replay_configure(pedn_sim* s, int64_t capacity, int32_t stack_size, int32_t episode_steps, uint64_t seed) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  if (capacity < 1) return fail(s, PEDN_E_ARG, "capacity < 1");
+  if (stack_size < 1) return fail(s, PEDN_E_ARG, "stack_size < 1");
+  if (episode_steps < 1) return fail(s, PEDN_E_ARG, "episode_steps < 1");
+  if (capacity > (int64_t)1 << 40) return fail(s, PEDN_E_ARG, "capacity too large");
+  if ((int64_t)s->v.R * stack_size * s->rl.O > 0x7fffffff) return fail(s, PEDN_E_ARG, "more than 2^31 entries in the stacked observation");
+  int rc = pedn_replay_free(s);
+  if (rc != PEDN_OK) return rc;
+  const RlView& q = s->rl;
+  ReplayView r;
+  memset(&r, 0, sizeof r);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
+  r.cap = capacity;
+  r.R = capacity + stack_size + (capacity + episode_steps - 1) / episode_steps + 1;
+  const size_t N = (size_t)s->v.R, R = (size_t)r.R;
+  auto take = [&](size_t bytes, void** out) -> int {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess) return fail(s, PEDN_E_NOMEM, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    s->rp_allocs.push_back(p);
+    const hipError_t z = hipMemset(p, 0, std::max<size_t>(bytes, 16));
+    if (z != hipSuccess) return fail(s, PEDN_E_DEVICE, std::string("hipMemset: ") + hipGetErrorString(z));
+    *out = p;
+    return PEDN_OK;
+  };
+  if ((rc = take(R * N * q.O * sizeof(float), (void**)&r.frames)) != PEDN_OK || (rc = take(R * N * q.A * sizeof(double), (void**)&r.actions)) != PEDN_OK ||
+      (rc = take(R * N * q.n_agents * sizeof(float), (void**)&r.rewards)) != PEDN_OK || (rc = take(R * sizeof(float), (void**)&r.done)) != PEDN_OK ||
+      (rc = take(N * stack_size * q.O * sizeof(float), (void**)&r.stacked)) != PEDN_OK || (rc = take(R * sizeof(int64_t), (void**)&r.first)) != PEDN_OK ||
+      (rc = take((size_t)capacity * sizeof(int64_t), (void**)&r.step_serial)) != PEDN_OK || (rc = take(16 * sizeof(int64_t), (void**)&r.state)) != PEDN_OK) {
+    const std::string keep = s->err;
+    replay_drop(s);
+    return fail(s, rc, keep);
+  }
+  const int64_t no_episode = -1;
+  HIP_TRY(s, hipMemcpy(r.state + 3, &no_episode, sizeof no_episode, hipMemcpyHostToDevice));
+  r.clock = s->d_clock;
+  r.k0 = (uint32_t)(seed & 0xffffffffu); r.k1 = (uint32_t)(seed >> 32);
+  r.N = s->v.R; r.A = q.n_agents; r.n_actions = q.A; r.n_obs = q.O; r.stack = stack_size; r.T = s->v.T1 - 1;
+  s->rp = r;
+  s->rp_on = true;
+  replay_sources(s);
+  return PEDN_OK;
+}
+
+// both roles of replay_push_kernel get the same number of workgroups: a lane takes about four 16-byte accesses of the wider role (few
+// workgroups: every one of them takes a ticket from one counter)
+static dim3 replay_push_grid(const ReplayView& r) {
+  const size_t row = (size_t)r.N * std::max(std::max(r.n_obs, 2 * r.n_actions), r.A) / 4 + 1;
+  const size_t stack = (size_t)r.N * r.stack * r.n_obs / ((r.n_obs & 3) ? 1 : 4);
+  return dim3((unsigned)std::min<size_t>((std::max(row, stack) + 1023) / 1024, 512), 2);
+}
+
+int pedn_replay_begin(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rp_on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: the RESET row takes the observation the eager reset left)
+  hipLaunchKernelGGL(replay_push_kernel, replay_push_grid(s->rp), dim3(256), 0, s->stream, s->rp, (const double*)nullptr, 1, 0);
+  HIP_TRY(s, hipGetLastError());
+  s->rp_begun = true;
+  return PEDN_OK;
+}
+
+// (no allocation, no synchronisation, no event query: safe under stream capture)
+int pedn_replay_push(pedn_sim* s, const double* actions, int32_t term, void* stream) {
+  if (!s || !actions) return fail(s, PEDN_E_ARG, "null argument");
+  if (!s->rp_on || !s->rp_begun) return fail(s, PEDN_E_ARG, "pedn_replay_begin has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  hipLaunchKernelGGL(replay_push_kernel, replay_push_grid(s->rp), dim3(256), 0, st, s->rp, actions, 0, s->clocked ? -1 : (term ? 1 : 0));
+  HIP_TRY(s, hipGetLastError());
+  return PEDN_OK;
+}
+
+// (the same: safe under stream capture)
+int pedn_replay_sample(pedn_sim* s, int64_t batch, const int64_t* indices, int32_t obs0, int32_t obs_w, int32_t act0, int32_t act_w,
+                       int32_t rew0, int32_t rew_w, float* states, double* actions, float* rewards, float* next_states, float* dones,
+                       int64_t* idx, void* stream) {
+  if (!s || !states || !actions || !rewards || !next_states || !dones) return fail(s, PEDN_E_ARG, "null argument");
+  if (!s->rp_on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
+  const ReplayView& r = s->rp;
+  if (batch < 1 || batch > 0x7fffffffll) return fail(s, PEDN_E_ARG, "batch size out of range");
+  if (obs0 < 0 || obs_w < 1 || obs0 + obs_w > r.n_obs || act0 < 0 || act_w < 1 || act0 + act_w > r.n_actions || rew0 < 0 || rew_w < 1 ||
+      rew0 + rew_w > r.A)
+    return fail(s, PEDN_E_ARG, "column range outside the row");
+  HIP_TRY(s, hipSetDevice(s->device));
+  ReplayOut o;
+  memset(&o, 0, sizeof o);
+  o.states = states; o.next_states = next_states; o.rewards = rewards; o.dones = dones; o.actions = actions; o.idx = idx;
+  o.obs0 = obs0; o.obs_w = obs_w; o.act0 = act0; o.act_w = act_w; o.rew0 = rew0; o.rew_w = rew_w;
+  const int64_t groups = (batch + PEDN_REPLAY_GROUP - 1) / PEDN_REPLAY_GROUP;
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  hipLaunchKernelGGL(replay_sample_kernel, dim3((unsigned)groups), dim3(256), 0, st, r, o, indices, (uint32_t)batch);
+  HIP_TRY(s, hipGetLastError());
+  return PEDN_OK;
+}
+
+int pedn_replay_size(pedn_sim* s, int64_t* state) {
+  if (!s || !state) return fail(s, PEDN_E_ARG, "null argument");
+  if (!s->rp_on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  HIP_TRY(s, hipDeviceSynchronize());   // pushes and samples may sit on a caller's stream
+  HIP_TRY(s, hipMemcpy(state, s->rp.state, 6 * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (state[5]) HIP_TRY(s, hipMemset(s->rp.state + 5, 0, sizeof(int64_t)));   // reported once
+  return PEDN_OK;
+}
+
+void* pedn_replay_device_ptr(pedn_sim* s, int32_t which) {
+  if (!s || !s->rp_on) return nullptr;
+  const ReplayView& r = s->rp;
+  switch (which) {
+    case 0: return r.frames;
+    case 1: return r.actions;
+    case 2: return r.rewards;
+    case 3: return r.done;
+    case 4: return r.first;
+    case 5: return r.step_serial;
+    case 6: return r.stacked;
+    case 7: return r.state;
+  }
+  return nullptr;
 }
 
 // ---- rule-based controllers on the device (pedn_ctrl.hpp) ----------------------------------------------------------------------

@@ -199,6 +199,13 @@ def _load():
         "pedn_rollout_finish": (C.c_int, [P, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "pedn_rollout_compute": (C.c_int, [P, C.c_double, C.c_double, C.c_int32]),
         "pedn_rollout_device_ptr": (C.c_void_p, [P, C.c_int32]),
+        "pedn_replay_configure": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int32, C.c_uint64]),
+        "pedn_replay_free": (C.c_int, [P]),
+        "pedn_replay_begin": (C.c_int, [P]),
+        "pedn_replay_push": (C.c_int, [P, C.c_void_p, C.c_int32, C.c_void_p]),
+        "pedn_replay_sample": (C.c_int, [P, C.c_int64, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] * 7),
+        "pedn_replay_size": (C.c_int, [P, C.POINTER(C.c_int64)]),
+        "pedn_replay_device_ptr": (C.c_void_p, [P, C.c_int32]),
         "pedn_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     }
     # the version first: a stale or alternate library (PEDN_HIP_LIB) must fail with this message, not with an AttributeError on a symbol
@@ -234,7 +241,9 @@ EXPORTS = ["pedn_abi_version", "pedn_last_error", "pedn_create", "pedn_destroy",
            "pedn_rl_norm_configure", "pedn_rl_norm_set_training", "pedn_rl_norm_get_stats", "pedn_rl_norm_set_stats", "pedn_rl_norm_device_ptr",
            "pedn_rl_fetch_raw",
            "pedn_rollout_configure", "pedn_rollout_free", "pedn_rollout_begin", "pedn_rollout_record", "pedn_rollout_finish", "pedn_rollout_compute",
-           "pedn_rollout_device_ptr", "pedn_gae"]
+           "pedn_rollout_device_ptr", "pedn_gae",
+           "pedn_replay_configure", "pedn_replay_free", "pedn_replay_begin", "pedn_replay_push", "pedn_replay_sample", "pedn_replay_size",
+           "pedn_replay_device_ptr"]
 
 
 def _p(a, dtype=np.float64):
@@ -758,6 +767,37 @@ class Engine:
 
     def rollout_device_ptr(self, which):
         return self._lib.pedn_rollout_device_ptr(self._h, int(which))
+
+    # -- replay store (include/pedn.h: pedn_replay_*; pednstream_amd.replay.ReplayStore builds the arguments)
+    def replay_configure(self, capacity, stack_size, episode_steps, seed=0):
+        self._ck_arg(self._lib.pedn_replay_configure(self._h, int(capacity), int(stack_size), int(episode_steps), int(seed) & (2 ** 64 - 1)))
+
+    def replay_free(self):
+        self._ck(self._lib.pedn_replay_free(self._h))
+
+    def replay_begin(self):
+        self._ck_arg(self._lib.pedn_replay_begin(self._h))
+
+    def replay_push(self, actions_ptr, terminated=False, stream_ptr=0):
+        """One launch on ``stream_ptr`` (0: the engine's stream); a device pointer; safe under stream capture."""
+        self._ck_arg(self._lib.pedn_replay_push(self._h, C.c_void_p(int(actions_ptr)), int(bool(terminated)),
+                                                C.c_void_p(int(stream_ptr)) if stream_ptr else None))
+
+    def replay_sample(self, batch, indices_ptr, obs, act, rew, out_ptrs, stream_ptr=0):
+        """One launch on ``stream_ptr``; ``obs`` / ``act`` / ``rew`` are (first column, width); ``out_ptrs`` the device pointers of
+        states, actions, rewards, next_states, dones, idx (0: not wanted); safe under stream capture."""
+        p = lambda x: C.c_void_p(int(x)) if x else None
+        self._ck_arg(self._lib.pedn_replay_sample(self._h, int(batch), p(indices_ptr), *[int(x) for x in (*obs, *act, *rew)],
+                                                  *[p(x) for x in out_ptrs], p(stream_ptr)))
+
+    def replay_state(self):
+        """Waits for the device; dict of head, steps, size_rows, first, draws, error (the error flag is cleared once reported)."""
+        st = (C.c_int64 * 6)()
+        self._ck_arg(self._lib.pedn_replay_size(self._h, st))
+        return dict(zip(("head", "steps", "size_rows", "first", "draws", "error"), [int(x) for x in st]))
+
+    def replay_device_ptr(self, which):
+        return self._lib.pedn_replay_device_ptr(self._h, int(which))
 
     def ctrl_device_ptr(self, which):
         return self._lib.pedn_ctrl_device_ptr(self._h, int(which))

@@ -205,6 +205,7 @@ class VecPedNetEnv:
         self._ctrl_reset = False
         self._norm = None              # set_running_norm: the configuration dict while the normalisation is on
         self._rollout_store = None     # rollout_store: the engine holds one store at a time
+        self._replay_store = None      # replay_store: and one replay store beside it
 
     # ------------------------------------------------------------------------------------------------ API
     AUTO_VECTORISED_FROM = 65      # randomize(mode="auto"): batches of this many envs and more draw their scenarios on the device
@@ -657,7 +658,7 @@ class VecPedNetEnv:
     def capture(self, policy_fn, on_step=None, generators=(), steps_per_replay=1):
         """A graph-replayable rollout loop: ``policy_fn(obs) -> actions`` (torch ops only; obs is the engine's float32 observation buffer
         [n_envs, n_obs], actions a contiguous float64 CUDA tensor [n_envs, n_actions]) followed by one env step and ``on_step(obs, rewards)``
-        (optional, torch ops and ``RolloutStore.record`` only: reward bookkeeping, storing the transition) captured ONCE as a ``torch.cuda.CUDAGraph`` and replayed
+        (optional, torch ops, ``RolloutStore.record`` and ``ReplayStore.push`` / ``sample`` only: reward bookkeeping, storing the transition) captured ONCE as a ``torch.cuda.CUDAGraph`` and replayed
         per policy step -- see ``GraphedRollout``.  ``generators``: every ``torch.Generator`` the two callables draw from other than the
         default one (torch must know them before the capture: ``CUDAGraph.register_generator_state``).  ``steps_per_replay`` > 1: that
         many consecutive iterations in ONE graph (``GraphedRollout.step`` then advances by that many policy steps; the tail of an episode
@@ -675,6 +676,18 @@ class VecPedNetEnv:
         self._rollout_store = None
         store = RolloutStore(self, capacity, store_obs)
         self._rollout_store = store
+        return store
+
+    def replay_store(self, capacity, stack_size=4, seed=0):
+        """A device-resident replay buffer for off-policy training (``pednstream_amd.replay.ReplayStore``): a ring of the newest
+        ``capacity`` policy steps of every env that keeps each observation once, the stack of the last ``stack_size`` observations for
+        the policy, and minibatches of stacked transitions drawn on the device (``seed``).  One replay store at a time, beside a
+        ``rollout_store``: a second call replaces the first one's arrays.  A rollout captured before is captured again."""
+        from .replay import ReplayStore
+
+        self._replay_store = None
+        store = ReplayStore(self, capacity, stack_size, seed)
+        self._replay_store = store
         return store
 
     def _ordered_behind_engine(self):
@@ -996,6 +1009,10 @@ class MultiScenarioVecEnv:
     def rollout_store(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv steps separate engines: a rollout store belongs to one VecPedNetEnv (one per group: "
                          "env.groups[i].rollout_store())")
+
+    def replay_store(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv steps separate engines: a replay store belongs to one VecPedNetEnv (one per group: "
+                         "env.groups[i].replay_store(...))")
 
     def set_running_norm(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv does not run the running normalisation: its groups are separate engines with statistics of "
