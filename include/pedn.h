@@ -481,6 +481,32 @@ void* pedn_rollout_device_ptr(pedn_sim* sim, int32_t which);
 int pedn_gae(const float* rewards, const float* values, const float* dones, int32_t T, int32_t lanes, double gamma, double lmbda,
              float* td_target, float* adv, void* stream);
 
+/* ---- the reference's stacked actors for all envs and agents in one launch (rl/agents/SAC.py:72-107,277-293; PPO_org.py:145-172,470-516) --
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 14 (tests/actor_model.py restates it in numpy).
+ *   stack    f32 [n_envs][stack_size][n_obs], oldest frame first (e.g. array 6 of pedn_replay_device_ptr); input i = f * stack_size + s of
+ *            an agent is stack[e][s][obs0 + f]
+ *   table    int32 [n_agents][6]: obs0, obs_w, act0, act_w, the offset of the agent's tensors in `params` (floats), 0.  The caller
+ *            guarantees obs0 + obs_w <= n_obs, act0 + act_w <= n_actions, 1 <= act_w <= 8, disjoint action columns, and with
+ *            delta_actions that act_w divides obs_w
+ *   low, high  f32 [n_actions]: the bounds of the absolute actions
+ *   params   f32: per agent, in nn.Linear's [out][in] layout, encoder.fc1 weight [64][stack_size * obs_w] and bias [64], encoder.fc2
+ *            [64][64] + [64], fc [64][64] + [64], for kind 1 ln weight [64] and bias [64], fc_mu [act_w][64] + [act_w], fc_std the same
+ *   noise    f32 [n_envs][n_actions], read with mode 1 (may be NULL otherwise)
+ *   mu, std, eps, raw  f32 [n_envs][n_actions], actions f64 [n_envs][n_actions]: written for every column some agent owns
+ *   state    int64 [2], zeroed by the caller once: 0 the draw counter d, 1 the ticket of the launch's workgroups
+ * kind 0 (SAC): std = softplus, raw = tanh(mu + std * eps) * max_delta.  kind 1 (PPO): LayerNorm behind fc, std clamped to
+ * [min_std, max_std], raw = mu + std * eps clamped to +-max_delta (delta_actions) or to [low, high].  actions = clip(width + raw, low,
+ * high) with delta_actions (width: the newest frame's column obs0 + (j + 1) * obs_w / act_w - 1), else raw.  mode 0: eps of (env, column
+ * c) is drawn from Philox4x32-10((replica_offset + env, d lo, 0x72 | c << 8, d hi), seed) and the launch's last workgroup advances d;
+ * mode 1: eps = noise; mode 2 (deterministic): eps = 0 and raw comes from mu alone.  hidden_size must be 64.
+ * One launch on `stream` (NULL = the default stream); no allocation, no synchronisation, no event query, constant arguments: safe under
+ * stream capture, and a captured launch is replayed with the step (the draw counter lives in device memory). */
+int pedn_actor_forward(const float* stack, const int32_t* table, const float* low, const float* high, const float* params,
+                       const float* noise, float* mu, float* std, float* eps, float* raw, double* actions, int64_t* state,
+                       int32_t n_envs, int32_t stack_size, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size,
+                       int32_t kind, int32_t delta_actions, int32_t mode, double max_delta, double min_std, double max_std, uint64_t seed,
+                       uint32_t replica_offset, void* stream);
+
 /* ---- replay store of the off-policy trainers on the device (rl/rl_utils.py:37-50 ReplayBuffer; rl/agents/SAC.py:127-225) ----------
  * A device-resident ring of transitions of every env that keeps each observation ONCE, filled by ONE launch per policy step, and a
  * gather of sampled minibatches as stacks of the last `stack_size` observations.  The contract (restated in numpy by

@@ -6,12 +6,14 @@ Public surface (mirrors the reference's for this path):
     load_config           YAML/JSON scenario -> config dict         (reference src/utils/config.py)
     RolloutStore, gae, compute_gae   on-policy rollouts and GAE on the device (reference rl/agents/PPO_org.py, rl/rl_utils.py)
     ReplayStore           off-policy replay ring with stacked observations on the device (reference rl/rl_utils.py ReplayBuffer, rl/agents/SAC.py)
+    StackedActors         the stacked SAC / PPO actors of all agents for all envs in one launch (reference rl/agents/SAC.py, PPO_org.py)
 """
 from .config import load_config
 from .env_loader import NetworkEnvGenerator
 from .network import Network
+from .policy import StackedActors
 from .replay import ReplayStore
 from .rollout import RolloutStore, compute_gae, gae
 
-__all__ = ["NetworkEnvGenerator", "Network", "load_config", "RolloutStore", "gae", "compute_gae", "ReplayStore"]
+__all__ = ["NetworkEnvGenerator", "Network", "load_config", "RolloutStore", "gae", "compute_gae", "ReplayStore", "StackedActors"]
 __version__ = "0.1.0"

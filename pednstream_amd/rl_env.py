@@ -690,6 +690,15 @@ class VecPedNetEnv:
         self._replay_store = store
         return store
 
+    def stacked_actors(self, kind="sac", stack_size=4, delta_actions=True, max_delta=2.5, min_std=1e-3, max_std=10.0, seed=0):
+        """The reference's stacked actors of every agent of this env, evaluated for all envs in ONE launch
+        (``pednstream_amd.policy.StackedActors``): ``kind`` "sac" (tanh-squashed) or "ppo" (LayerNorm, clamped), ``stack_size`` frames
+        per decision (the ``stack_size`` of ``replay_store``), ``delta_actions``: the action is added to the gate width of the newest
+        frame and clipped to the action bounds.  ``actors.act(buf.stacked_obs())`` is a ``policy_fn`` of ``capture``."""
+        from .policy import for_env
+
+        return for_env(self, kind, stack_size, delta_actions, max_delta, min_std, max_std, seed)
+
     def _ordered_behind_engine(self):
         """The caller's current torch stream waits (on the device) for everything enqueued on the engine's stream so far."""
         import torch
@@ -1013,6 +1022,10 @@ class MultiScenarioVecEnv:
     def replay_store(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv steps separate engines: a replay store belongs to one VecPedNetEnv (one per group: "
                          "env.groups[i].replay_store(...))")
+
+    def stacked_actors(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv steps separate engines: stacked actors belong to one VecPedNetEnv (one per group: "
+                         "env.groups[i].stacked_actors(...))")
 
     def set_running_norm(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv does not run the running normalisation: its groups are separate engines with statistics of "
