@@ -507,6 +507,33 @@ int pedn_actor_forward(const float* stack, const int32_t* table, const float* lo
                        int32_t kind, int32_t delta_actions, int32_t mode, double max_delta, double min_std, double max_std, uint64_t seed,
                        uint32_t replica_offset, void* stream);
 
+/* ---- SAC TD targets and Polyak updates of all agents (rl/agents/SAC.py:109-125 QValueNetContinuous, :296-318 calc_target, soft_update) ----
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 15 (tests/sac_target_model.py restates it in numpy).
+ *   next_states  f32 [batch][stack_size][n_obs], rewards f32 [batch][n_agents], dones f32 [batch]: a whole-row minibatch (pedn_replay_sample)
+ *   table        the int32 [n_agents][6] table of pedn_actor_forward, with the same guarantees; actor_params its SAC-kind pack
+ *   critic_table int32 [n_agents][2]: the offsets (floats, multiples of 4) of the agent's critic 1 and critic 2 in a critic pack
+ *   target_params  f32: per critic, in nn.Linear's [out][in] layout, encoder.fc1 [64][stack_size * obs_w] + [64], encoder.fc2 [64][64] +
+ *                [64], fc [64][64 + act_w + 1] + [64], fc_out [1][64] + [1]; its input row is the 64 encoder outputs, next_action and the
+ *                newest frame's column obs0 + obs_w - 1; no ReLU between fc and fc_out
+ *   log_alpha    f32 [n_agents]
+ *   noise        f32 [batch][n_actions] used as eps, or NULL: eps of (row b, column c) is drawn from Philox4x32-10((b, d lo, 0x73 | c << 8,
+ *                d hi), seed) and the launch's last workgroup advances d
+ *   out_actions  f32 [5][batch][n_actions]: mu, std, eps, logp, next_actions; out_agents f32 [4][batch][n_agents]: entropy, q1, q2,
+ *                td_target.  Written for every column some agent owns, for inspection; td_target is the result
+ *   state        int64 [2], zeroed by the caller once: 0 the draw counter d, 1 the ticket of the launch's workgroups
+ * next_action = tanh(mu + std * eps) * max_delta, logp = Normal(mu, std).log_prob(u) - log(1 - tanh(tanh(u))^2 + 1e-7) (the reference's
+ * second tanh is mirrored), entropy = -sum logp, q = min(q1, q2) with NaN winning, td_target = r + gamma * (q + exp(log_alpha) * entropy) *
+ * (1 - done).  hidden_size must be 64.  One launch on `stream` (NULL = the default stream); no allocation, no synchronisation, no event
+ * query, constant arguments: safe under stream capture. */
+int pedn_sac_td_target(const float* next_states, const float* rewards, const float* dones, const int32_t* table, const int32_t* critic_table,
+                       const float* actor_params, const float* target_params, const float* log_alpha, const float* noise,
+                       float* out_actions, float* out_agents, int64_t* state, int32_t batch, int32_t stack_size, int32_t n_obs,
+                       int32_t n_actions, int32_t n_agents, int32_t hidden_size, double max_delta, double gamma, uint64_t seed,
+                       void* stream);
+/* target[i] = target[i] * (float)(1 - tau) + online[i] * (float)tau for i < n_floats (a positive multiple of 4; both packs 16-byte aligned;
+ * 0 <= tau <= 1): the reference's soft_update of every target critic at once.  One launch on `stream`, capturable like the above. */
+int pedn_sac_soft_update(float* target, const float* online, int64_t n_floats, double tau, void* stream);
+
 /* ---- replay store of the off-policy trainers on the device (rl/rl_utils.py:37-50 ReplayBuffer; rl/agents/SAC.py:127-225) ----------
  * A device-resident ring of transitions of every env that keeps each observation ONCE, filled by ONE launch per policy step, and a
  * gather of sampled minibatches as stacks of the last `stack_size` observations.  The contract (restated in numpy by

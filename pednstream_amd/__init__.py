@@ -7,6 +7,7 @@ Public surface (mirrors the reference's for this path):
     RolloutStore, gae, compute_gae   on-policy rollouts and GAE on the device (reference rl/agents/PPO_org.py, rl/rl_utils.py)
     ReplayStore           off-policy replay ring with stacked observations on the device (reference rl/rl_utils.py ReplayBuffer, rl/agents/SAC.py)
     StackedActors         the stacked SAC / PPO actors of all agents for all envs in one launch (reference rl/agents/SAC.py, PPO_org.py)
+    SacTargets            SAC TD targets of a minibatch and the Polyak update of every target critic, one launch each (reference rl/agents/SAC.py)
 """
 from .config import load_config
 from .env_loader import NetworkEnvGenerator
@@ -14,6 +15,7 @@ from .network import Network
 from .policy import StackedActors
 from .replay import ReplayStore
 from .rollout import RolloutStore, compute_gae, gae
+from .sac import SacTargets
 
-__all__ = ["NetworkEnvGenerator", "Network", "load_config", "RolloutStore", "gae", "compute_gae", "ReplayStore", "StackedActors"]
+__all__ = ["NetworkEnvGenerator", "Network", "load_config", "RolloutStore", "gae", "compute_gae", "ReplayStore", "StackedActors", "SacTargets"]
 __version__ = "0.1.0"

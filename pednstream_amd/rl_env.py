@@ -699,6 +699,14 @@ class VecPedNetEnv:
 
         return for_env(self, kind, stack_size, delta_actions, max_delta, min_std, max_std, seed)
 
+    def sac_targets(self, actors, gamma=0.99, tau=0.005, seed=0):
+        """The gradient-free half of the reference's ``SACAgent.update`` for every agent of this env (``pednstream_amd.sac.SacTargets``):
+        ``td_target(rewards, next_states, dones)`` of a whole-row ``replay_store`` minibatch in ONE launch, ``soft_update()`` of every
+        target critic in ONE launch.  ``actors``: this env's ``stacked_actors("sac", stack_size)``."""
+        from .sac import for_env
+
+        return for_env(self, actors, gamma, tau, seed)
+
     def _ordered_behind_engine(self):
         """The caller's current torch stream waits (on the device) for everything enqueued on the engine's stream so far."""
         import torch
@@ -1026,6 +1034,10 @@ class MultiScenarioVecEnv:
     def stacked_actors(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv steps separate engines: stacked actors belong to one VecPedNetEnv (one per group: "
                          "env.groups[i].stacked_actors(...))")
+
+    def sac_targets(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv steps separate engines: SAC targets belong to one VecPedNetEnv (one per group: "
+                         "env.groups[i].sac_targets(...))")
 
     def set_running_norm(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv does not run the running normalisation: its groups are separate engines with statistics of "

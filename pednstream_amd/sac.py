@@ -1,0 +1,283 @@
+"""The gradient-free half of the reference's ``SACAgent.update`` on the device, for every agent at once: the TD targets of a whole-row
+minibatch in ONE launch (``calc_target``, rl/agents/SAC.py:296-312, with both target critics ``QValueNetContinuous`` :109-125) and the
+Polyak update of every target critic in ONE launch (``soft_update`` :314-318).  pednstream_amd/csrc/pedn_sac.hpp; the contract is DESIGN
+section 15, tests/sac_target_model.py restates it in numpy.
+
+    buf = env.replay_store(capacity, stack_size=5)
+    actors = env.stacked_actors(kind="sac", stack_size=5)
+    sac = env.sac_targets(actors)
+    for aid in env.possible_agents:
+        sac.bind(aid, critic_1[aid], critic_2[aid], target_1[aid], target_2[aid], log_alpha=log_alpha[aid])
+    s, a, r, ns, d, idx = buf.sample(256)
+    td = sac.td_target(r, ns, d)                  # [256, n_agents], detached by construction
+    ...                                           # critic / actor / alpha losses and optimiser steps in torch, on the bound modules
+    sac.soft_update()
+
+``SacTargets`` is the constructor on a ``StackedActors`` (no env).  Backward passes and the optimisers stay in torch.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import engine as _engine
+from .policy import HIDDEN, StackedActors
+
+WHICH = ("critic_1", "critic_2", "target_critic_1", "target_critic_2")
+ACTION_OUTPUTS = ("mu", "std", "eps", "logp", "next_actions")
+AGENT_OUTPUTS = ("entropy", "q1", "q2", "td_target")
+TILE = 8                        # rows per workgroup of sac_target_kernel (PEDN_SAC_TILE)
+
+
+def critic_shapes(obs_w, act_w, stack_size, hidden_size=HIDDEN):
+    """[(state_dict key, shape)] of one critic in the order of the pack."""
+    h = int(hidden_size)
+    return [("encoder.fc1.weight", (h, int(stack_size) * int(obs_w))), ("encoder.fc1.bias", (h,)), ("encoder.fc2.weight", (h, h)),
+            ("encoder.fc2.bias", (h,)), ("fc.weight", (h, h + int(act_w) + 1)), ("fc.bias", (h,)), ("fc_out.weight", (1, h)), ("fc_out.bias", (1,))]
+
+
+def critic_pack_layout(agents, stack_size, hidden_size=HIDDEN):
+    """(offsets, total): offsets[i][c] = {key: (offset in floats, shape)} of critic c + 1 of agent i = (obs0, obs_w, act0, act_w); per
+    agent critic 1 then critic 2, every critic on a multiple of 4 floats; total is a multiple of 4 (the padding is zero)."""
+    offsets, at = [], 0
+    for (_, obs_w, _, act_w) in agents:
+        pair = []
+        for _c in range(2):
+            at = -(-at // 4) * 4
+            cur = {}
+            for key, shape in critic_shapes(obs_w, act_w, stack_size, hidden_size):
+                cur[key] = (at, shape)
+                at += int(np.prod(shape))
+            pair.append(cur)
+        offsets.append(pair)
+    return offsets, -(-at // 4) * 4
+
+
+def make_critic_module(obs_w, act_w, stack_size):
+    """A torch module with the reference critic's layers, parameter names and forward (``forward(s [B, S, obs_w], a [B, act_w]) ->
+    [B, 1]``), for training beside the kernel: ``SacTargets.bind`` makes its parameters views of a pack."""
+    import torch
+    from torch import nn
+
+    class Encoder(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.fc1, self.fc2 = nn.Linear(int(stack_size) * int(obs_w), HIDDEN), nn.Linear(HIDDEN, HIDDEN)
+
+        def forward(self, x):
+            return torch.relu(self.fc2(torch.relu(self.fc1(x))))
+
+    class Critic(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.encoder, self.fc, self.fc_out = Encoder(), nn.Linear(HIDDEN + int(act_w) + 1, HIDDEN), nn.Linear(HIDDEN, 1)
+
+        def forward(self, s, a):
+            zs = self.encoder(s.transpose(1, 2).flatten(1))               # input f * S + s is s[b, s, f]
+            gate_widths = s[:, -1, -1].unsqueeze(1)                       # the newest frame's last column
+            return self.fc_out(self.fc(torch.cat([zs, a, gate_widths], dim=1)))      # (no ReLU behind fc, as in the reference)
+
+    return Critic()
+
+
+class SacTargets:
+    """``actors``: a ``StackedActors`` of kind "sac"; the agent table, ``max_delta``, the device and the stack size are its.  The actors'
+    pack is read in place; the critics live in two packs of one layout, ``online`` and ``target``."""
+
+    def __init__(self, actors, gamma=0.99, tau=0.005, seed=0):
+        if not isinstance(actors, StackedActors):
+            raise ValueError("actors must be a StackedActors")
+        if actors.kind != "sac":
+            raise ValueError(f"SAC targets need actors of kind 'sac', got {actors.kind!r}")
+        gamma, tau = float(gamma), float(tau)
+        if not math.isfinite(gamma):
+            raise ValueError(f"gamma must be finite, got {gamma}")
+        if not 0.0 <= tau <= 1.0:
+            raise ValueError(f"tau must be in [0, 1], got {tau}")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("the seed must fit 64 bits")
+        self.actors, self.gamma, self.tau, self.seed = actors, gamma, tau, int(seed)
+        self.agents, self.agent_ids, self.device = actors.agents, actors.agent_ids, actors.device
+        self.stack_size, self.n_obs, self.n_actions, self.max_delta = actors.stack_size, actors.n_obs, actors.n_actions, actors.max_delta
+        self.n_agents = len(self.agents)
+        self.offsets, self.pack_size = critic_pack_layout(self.agents, self.stack_size)
+        self.critic_table = np.array([[pair[0]["encoder.fc1.weight"][0], pair[1]["encoder.fc1.weight"][0]] for pair in self.offsets], dtype=np.int32)
+        self._loaded = set()            # (agent index, which)
+        self._dev = None                # the device tensors, allocated once (a captured graph owns their addresses)
+        self._out = {}                  # batch size -> (out_actions [5, B, n_actions], out_agents [4, B, n_agents])
+        self._last = None
+
+    # ------------------------------------------------------------------------------------------------ parameters
+    def _index(self, agent_id):
+        try:
+            return self.agent_ids.index(agent_id)
+        except ValueError:
+            raise ValueError(f"Unknown agent: {agent_id}") from None
+
+    @staticmethod
+    def _which(which):
+        if which not in WHICH:
+            raise ValueError(f"which must be one of {WHICH}, got {which!r}")
+        return ("target" if which.startswith("target_") else "online"), int(which[-1]) - 1
+
+    def _device(self):
+        if self._dev is None:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            self._dev = {"online": torch.zeros(self.pack_size, dtype=torch.float32, device=dev),
+                         "target": torch.zeros(self.pack_size, dtype=torch.float32, device=dev),
+                         "ctable": torch.as_tensor(self.critic_table, device=dev),
+                         "log_alpha": torch.full((self.n_agents,), math.log(0.01), dtype=torch.float32, device=dev),
+                         "state": torch.zeros(2, dtype=torch.int64, device=dev)}
+        return self._dev
+
+    def parameters(self, agent_id, which):
+        """{key: float32 CUDA tensor} in ``nn.Linear`` shapes; the tensors ALIAS the pack the kernels read and write."""
+        i = self._index(agent_id)
+        pack_name, c = self._which(which)
+        pack = self._device()[pack_name]
+        return {k: pack[at:at + int(np.prod(shape))].view(*shape) for k, (at, shape) in self.offsets[i][c].items()}
+
+    def load_state_dict(self, agent_id, which, state_dict):
+        """Copy a critic's tensors (the reference's keys, ``nn.Linear`` layout; torch tensors or arrays) into its pack."""
+        import torch
+
+        i = self._index(agent_id)
+        pack_name, c = self._which(which)
+        keys = {k: v for k, v in state_dict.items()}
+        want = self.offsets[i][c]
+        if set(keys) != set(want):
+            raise ValueError(f"state dict keys {sorted(keys)} do not match {sorted(want)}")
+        for k, (_, shape) in want.items():
+            if tuple(keys[k].shape) != tuple(shape):
+                raise ValueError(f"{k}: expected shape {tuple(shape)}, got {tuple(keys[k].shape)}")
+        views = self.parameters(agent_id, which)
+        with torch.no_grad():
+            for k, v in keys.items():
+                views[k].copy_(torch.as_tensor(np.asarray(v, dtype=np.float32)) if not isinstance(v, torch.Tensor) else v.detach().to(torch.float32))
+        self._loaded.add((i, which))
+
+    @property
+    def log_alpha(self):
+        """float32 [n_agents] CUDA tensor the kernel reads (default log 0.01)."""
+        return self._device()["log_alpha"]
+
+    def bind(self, agent_id, critic_1, critic_2, target_critic_1, target_critic_2, log_alpha=None):
+        """Copy the four modules' parameters into the packs and point every ``param.data`` at its view there: an optimiser that steps
+        the online critics updates what ``soft_update`` reads, and ``soft_update`` updates the target modules, with no copy.  A
+        ``log_alpha`` leaf tensor's value is copied into its element of ``self.log_alpha`` and its ``.data`` becomes a view of it."""
+        import torch
+
+        i = self._index(agent_id)
+        if log_alpha is not None and (not isinstance(log_alpha, torch.Tensor) or log_alpha.numel() != 1):
+            raise ValueError("log_alpha must be a torch tensor of one element")
+        modules = dict(zip(WHICH, (critic_1, critic_2, target_critic_1, target_critic_2)))
+        for which, m in modules.items():
+            params = dict(m.named_parameters())
+            if set(params) != set(self.offsets[i][0]):
+                raise ValueError(f"{which}: the module's parameters {sorted(params)} do not match {sorted(self.offsets[i][0])}")
+        for which, m in modules.items():
+            self.load_state_dict(agent_id, which, {k: v for k, v in m.state_dict().items()})
+            views = self.parameters(agent_id, which)
+            for k, p in m.named_parameters():
+                p.data = views[k]
+        if log_alpha is not None:
+            view = self.log_alpha[i:i + 1].view(log_alpha.shape)
+            with torch.no_grad():
+                view.copy_(log_alpha.detach().to(torch.float32))
+            log_alpha.data = view
+        return modules
+
+    # ------------------------------------------------------------------------------------------------ the two launches
+    def _check(self, name, t, shape):
+        import torch
+
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{name} must be on cuda:{self.device}")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+    def td_target(self, rewards, next_states, dones, noise=None):
+        """``td_target`` float32 [B, n_agents] (one tensor per batch size, written again by the next call of that size) for a whole-row
+        minibatch as ``ReplayStore.sample(B)`` hands it out: ``rewards`` [B, n_agents], ``next_states`` [B, stack_size, n_obs], ``dones``
+        [B], float32 contiguous CUDA.  ``noise`` [B, n_actions] float32: use it as eps in place of a draw.  One launch on the current
+        torch stream; no allocation after the first call of a batch size, no synchronisation: capturable.  A draw advances ``draws()``."""
+        import torch
+
+        if not isinstance(dones, torch.Tensor) or dones.dim() != 1 or dones.shape[0] < 1:
+            raise ValueError("dones must be a torch tensor of shape [B]")
+        B = int(dones.shape[0])
+        self._check("dones", dones, (B,))
+        self._check("rewards", rewards, (B, self.n_agents))
+        self._check("next_states", next_states, (B, self.stack_size, self.n_obs))
+        if noise is not None:
+            self._check("noise", noise, (B, self.n_actions))
+        missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self.actors._loaded]
+        if missing:
+            raise ValueError(f"no actor parameters were loaded for {missing}: StackedActors.load_state_dict() or bind() first")
+        missing = [(self.agent_ids[i], w) for i in range(self.n_agents) for w in WHICH[2:] if (i, w) not in self._loaded]
+        if missing:
+            raise ValueError(f"no critics were loaded for {missing}: load_state_dict() or bind() first")
+        d = self._device()
+        out = self._out.get(B)
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = self._out[B] = (torch.zeros(len(ACTION_OUTPUTS), B, self.n_actions, dtype=torch.float32, device=dev),
+                                  torch.zeros(len(AGENT_OUTPUTS), B, self.n_agents, dtype=torch.float32, device=dev))
+        self._last = out
+        ad = self.actors._device()
+        p = lambda t: C.c_void_p(t.data_ptr())
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        lib = _engine.lib()
+        with torch.cuda.device(self.device):
+            rc = lib.pedn_sac_td_target(p(next_states), p(rewards), p(dones), p(ad["table"]), p(d["ctable"]), p(ad["pack"]), p(d["target"]),
+                                        p(d["log_alpha"]), p(noise) if noise is not None else None, p(out[0]), p(out[1]), p(d["state"]),
+                                        B, self.stack_size, self.n_obs, self.n_actions, self.n_agents, HIDDEN, self.max_delta, self.gamma,
+                                        self.seed, C.c_void_p(int(stream)) if stream else None)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"pedn_sac_td_target failed ({rc}): {lib.pedn_last_error(None).decode()}")
+        return out[1][3]
+
+    @property
+    def outputs(self):
+        """What the last ``td_target`` wrote, float32: ``mu``, ``std``, ``eps``, ``logp``, ``next_actions`` [B, n_actions] and ``entropy``,
+        ``q1``, ``q2``, ``td_target`` [B, n_agents]."""
+        if self._last is None:
+            raise ValueError("td_target() has not run")
+        out = {k: self._last[0][i] for i, k in enumerate(ACTION_OUTPUTS)}
+        out.update({k: self._last[1][i] for i, k in enumerate(AGENT_OUTPUTS)})
+        return out
+
+    def soft_update(self):
+        """target = target * (1 - tau) + online * tau over every target critic: one launch on the current torch stream, capturable."""
+        import torch
+
+        missing = [(self.agent_ids[i], w) for i in range(self.n_agents) for w in WHICH if (i, w) not in self._loaded]
+        if missing:
+            raise ValueError(f"no critics were loaded for {missing}: load_state_dict() or bind() first")
+        d = self._device()
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        lib = _engine.lib()
+        with torch.cuda.device(self.device):
+            rc = lib.pedn_sac_soft_update(C.c_void_p(d["target"].data_ptr()), C.c_void_p(d["online"].data_ptr()), self.pack_size, self.tau,
+                                          C.c_void_p(int(stream)) if stream else None)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"pedn_sac_soft_update failed ({rc}): {lib.pedn_last_error(None).decode()}")
+
+    def draws(self):
+        """How many launches have drawn noise (the device counter; waits for the device)."""
+        return int(self._device()["state"][0].item())
+
+
+def for_env(env, actors, gamma=0.99, tau=0.005, seed=0):
+    """``SacTargets`` over the stacked actors of a ``VecPedNetEnv``."""
+    if not hasattr(env, "network") or not hasattr(env, "possible_agents") or hasattr(env, "groups"):
+        raise ValueError("SAC targets belong to one VecPedNetEnv (MultiScenarioVecEnv steps separate engines)")
+    if isinstance(actors, StackedActors) and (actors.agent_ids != list(env.possible_agents) or actors.n_obs != env.n_obs or actors.n_actions != env.n_actions):
+        raise ValueError("the actors were not made for this env (env.stacked_actors('sac', stack_size))")
+    return SacTargets(actors, gamma=gamma, tau=tau, seed=seed)
