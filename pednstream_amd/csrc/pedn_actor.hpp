@@ -204,3 +204,30 @@ __global__ __launch_bounds__(256) void actor_forward_kernel(ActorArgs a) {
     }
   }
 }
+
+// ---- host side: pedn_actor_forward of include/pedn.h; no state in the engine's handle
+int pedn_actor_forward(const float* stack, const int32_t* table, const float* low, const float* high, const float* params,
+                       const float* noise, float* mu, float* std, float* eps, float* raw, double* actions, int64_t* state,
+                       int32_t n_envs, int32_t stack_size, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size,
+                       int32_t kind, int32_t delta_actions, int32_t mode, double max_delta, double min_std, double max_std, uint64_t seed,
+                       uint32_t replica_offset, void* stream) {
+  if (!stack || !table || !low || !high || !params || !mu || !std || !eps || !raw || !actions || !state)
+    return fail(nullptr, PEDN_E_ARG, "null argument");
+  if (hidden_size != PEDN_ACTOR_HIDDEN) return fail(nullptr, PEDN_E_ARG, "the actor kernel is built for hidden_size 64");
+  if (n_envs < 1 || stack_size < 1 || n_obs < 1 || n_actions < 1 || n_agents < 1 || n_agents > 65535)
+    return fail(nullptr, PEDN_E_ARG, "n_envs, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)");
+  if (kind < 0 || kind > 1 || mode < 0 || mode > 2) return fail(nullptr, PEDN_E_ARG, "kind is 0 (SAC) or 1 (PPO), mode 0, 1 or 2");
+  if (mode == 1 && !noise) return fail(nullptr, PEDN_E_ARG, "mode 1 needs the noise");
+  ActorArgs a{};
+  a.stack = stack; a.table = table; a.low = low; a.high = high; a.params = params; a.noise = noise;
+  a.mu = mu; a.std = std; a.eps = eps; a.raw = raw; a.actions = actions; a.state = state;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
+  a.replica_offset = replica_offset;
+  a.n_envs = n_envs; a.S = stack_size; a.n_obs = n_obs; a.n_actions = n_actions;
+  a.kind = kind; a.delta = delta_actions != 0; a.mode = mode;
+  a.max_delta = (float)max_delta; a.min_std = (float)min_std; a.max_std = (float)max_std;
+  const dim3 grid((unsigned)((n_envs + PEDN_ACTOR_TILE - 1) / PEDN_ACTOR_TILE), (unsigned)n_agents);
+  hipLaunchKernelGGL(actor_forward_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(nullptr, hipGetLastError());
+  return PEDN_OK;
+}

@@ -1,6 +1,10 @@
-// pedn_hip.hip -- host side of the MI355X (gfx950) engine for PedNStream's network_loading hot path: the C-ABI of
-// include/pedn.h (handle, device buffers, launches, host<->device transfers).  The kernels live in pedn_kernels.hpp, the
-// device data structures in pedn_types.hpp, the bit-exact arithmetic primitives in pedn_math.hpp.
+// pedn_hip.hip -- the core of the host side of the MI355X (gfx950) engine for PedNStream's network_loading hot path: model compilation
+// and plan choice (pedn_create), the setters and reads, the step path (launch_step, pedn_step, pedn_run, rl_step and the clocked step) and
+// the agent set (pedn_rl_configure) of the C-ABI of include/pedn.h.  The kernels live in pedn_kernels.hpp, the device data structures in
+// pedn_types.hpp, the bit-exact arithmetic primitives in pedn_math.hpp, the handle and the shared host helpers in pedn_host.hpp.
+// Every training-side feature (controllers, running normalisation, rollout and replay stores, stacked actors, SAC targets, evaluation
+// metrics) lives entirely in its own header, kernels first and host section behind them; this file knows them by a few named functions
+// (norm_launch, norm_reset_returns, store_drop, metrics_free), they know it by the services declared at the end of pedn_host.hpp.
 //
 // Data layout in HBM: every history field is one array [T+1][columns][RS] with the replica index
 // fastest (RS = replicas rounded up to a multiple of 128).  A wavefront owns 64 consecutive replicas of ONE link or node:
@@ -8,254 +12,15 @@
 // segment, and the data-dependent look-backs gather between rows of the same column.
 //
 // Compile with -ffp-contract=off: results must match the reference bit for bit.
-#include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "../../include/pedn.h"
 #include "pedn_kernels.hpp"
+#include "pedn_host.hpp"
 #include "pedn_ctrl.hpp"
 #include "pedn_norm.hpp"
 #include "pedn_rollout.hpp"
 #include "pedn_replay.hpp"
 #include "pedn_actor.hpp"
 #include "pedn_sac.hpp"
-
-// ------------------------------------------------------------------------------------------------- host side
-static thread_local std::string g_last_error;
-
-struct pedn_sim {
-  DevView v{};
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int device = 0;
-  int n_nodes = 0, n_turns = 0, n_demand = 0, n_od = 0, n_blocks = 0, n_ent = 0;
-  int link_owner = 0;  // pedn_run: node_kernel(t + 1)'s slot waves perform the link update of t (one launch per step), PEDN_LINK_OWNER
-  int packed_by = 1;   // how nodes were binned into node_kernel's blocks: 0 by degree, 1 by the static load estimate, 2 by measured cost
-  // Single-launch plan of small batches with dynamic turning fractions (inline_tf): every device-computed row is short enough for ONE
-  // wave and its probabilities fit PEDN_TF_INL_ROWS LDS rows (inline_tf_ok), and the whole node_kernel grid is one generation at 4 waves
-  // per SIMD: the slot waves of node_kernel<LU, TF> compute their own rows, a step is one launch.
-  bool inline_tf_ok = false;
-  int inline_tf = 0;
-  int inline_help = 0;      // ... with helper waves: node_kernel_h, sixteen waves per workgroup (PEDN_INLINE_TF=2)
-  // A caller that looks at the state after EVERY step (a controller reading densities, an output handler) makes every pending link
-  // update a launch of its own and every next step start from stand-alone turning fractions: three launches per step where the plain plan
-  // has two.  pedn_step notices (touched: something settled the pending state since the last step) and steps such a caller under the
-  // plain plan until two steps in a row go untouched (nine_intersections, step + two reads: 76.0 -> 71 us per step).
-  int touched = 0, touch_streak = 0;
-  int step_streak = 0;   // consecutive pedn_step(t), pedn_step(t + 1), ... calls with nothing looking at the state in between (see pedn_step)
-  size_t node_lds_tf = 0;   // dynamic LDS of node_kernel<.., TF>
-  std::vector<int32_t> h_slot_trow;
-  int rl_chains = 0;   // pedn_rl_step steps the two halves of the envs as two chains that stay forked ACROSS calls (PEDN_RL_CHAINS)
-  int forked = 0;      // stream2 holds work of such a chain that the engine's stream does not order yet (join_forked)
-  // Device-resident step clock (DevView.clock; pedn_rl_clock_begin .. pedn_rl_clock_end): while `clocked`, env steps are enqueued with
-  // constant arguments (pedn_rl_step_clocked) and the host does not know the step the device is at -- every other entry point that
-  // steps, reads or changes state first ends the clocked section (clock_end: synchronises and takes the bookkeeping back).
-  int32_t* d_clock = nullptr;
-  bool clocked = false;
-  int clock_t0 = 0;   // step the clock was set to by pedn_rl_clock_begin
-  int valid_hi = 0x7fffffff;   // lazy reset: history rows above this index are neither written nor cleared (DevView.valid_hi)
-  int link_pending = -1;  // owner-wave plan: step whose link update has not been performed yet, -1 none
-  // Quiet corridors (DevView.quiet): node_kernel<LU> launches store the words (PEDN_QUIET=0|1, default wherever link_owner is chosen);
-  // quiet_valid = the step whose words every replica group has, from a node_kernel<LU> launch on each chain with no change of a history
-  // row since -- the next LU launch may use them; -1 none.  Cleared by everything that could break that (no_quiet).
-  int quiet = 0;
-  int quiet_valid = -1;
-  int quiet_lean = 1;   // PEDN_QUIET_LEAN=0|1 (default on): those launches skip the node work that all-zero flows fix (DevView.quiet_lean)
-  uint32_t* d_quiet = nullptr;
-  // Zero elision (DevView.zg64 / zg32; PEDN_ZERO_ELIDE=0|1, default on): zhw64 = the highest row of inflow / outflow / cumulative_inflow /
-  // cumulative_outflow, zhw32 = of num_pedestrians / density / link_flow, that may hold anything but +0.0 -- -1 after a full reset (which
-  // leaves every row at +0.0), kept by the lazy reset (the old episode's rows stay), INT_MAX when something the host does not follow may write them
-  // (a zero-copy pointer, the clocked steps) until the next full reset.  A launch that writes row x of a group gets the gate iff
-  // x > the group's mark; the mark is raised to x once the step is enqueued (both chains of a step decide from the marks before it).
-  // Only zeros are ever written below the marks' back (clear_rows, catch_up), so they need not raise them.
-  int zero_elide = 1;
-  int zhw64 = 0x7fffffff, zhw32 = 0x7fffffff;
-  int zgated = 0;   // node-kernel launches with a gate open since the last reset of either kind (pedn_plan_info info[7])
-  int fuse_obs = 1;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
-  // (The link update as a launch of its own runs one replica per lane -- link_kernel_1r: 42-47 VGPRs, 8 waves per SIMD; melbourne x 1024
-  // 12.3-12.6 against 12.7-13.1 us with two replicas per lane, profiles/r03_link_kernel_variants.txt; inside link_turn_kernel, whose
-  // budget is set by the turning fractions, it keeps two replicas per lane: half the workgroups.)
-  int max_degree = 0;     // largest number of incident corridors of a node
-  size_t node_lds = 0;    // dynamic LDS bytes of node_kernel
-  hipStream_t stream2 = nullptr;   // second half of the replicas in pedn_run (two_streams)
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int warmed_chains = 1;  // chains whose streams exist and were probed to overlap
-  int chains = 1;         // plan of pedn_run for long ranges: 1 or 2 chains of launches (two_streams = chains > 1)
-  int run_chains = 1;     // chains of the range being launched (launch_step / flush_links: the last chain does the bookkeeping)
-  int stream_probe_attempts = 0;   // warm_chain_streams: probes run until the chains' streams were seen to overlap
-  float stream_probe_ms = 0.0f;
-  int two_streams = 0;    // pedn_run launches the two halves of the batch on two streams (replicas are independent)
-  int second_launch = 0;  // launch_step: a launch followed node_kernel
-  int fuse_tp = 0;     // the link update and the next step's turn probabilities share one launch (launch_step)
-  int tp_ran = 0;      // launch_step launched the stand-alone turn_frac_kernel (pedn_profile_step)
-  int tp_ready = -1;   // step whose turning fractions are in tfd[step & 1] (written by link_turn_kernel of the step before), -1: none
-  std::vector<int32_t> node_turn_ptr, node_demand_row;
-  std::vector<int32_t> h_up_od_ptr, h_upod_od, h_pair_upod;  // route-choice tables needed to re-tabulate P(od | up)
-  std::vector<double> h_od_w;
-  std::vector<int32_t> h_turn_pair_ptr, h_pair_const, h_turn_mode;
-  double* d_pair_pod = nullptr;
-  double* d_turn_tab = nullptr;
-  RlView rl{};
-  // rule-based controllers (pedn_ctrl_*, pedn_ctrl.hpp): device rows of next actions and episode sums, moving-average buffers
-  CtrlView ctrl{};
-  bool ctrl_ready = false;
-  bool ctrl_any = false;   // some agent has a controller (else a controlled step applies no actions at all)
-  int ctrl_rows = 0;       // moving-average rows allocated in ctrl.ring
-  bool rl_ready = false;
-  bool node_lp = false;   // PEDN_NODE_OPTIMAL: the node LP instead of the classic rule
-  bool rl_fold = false;   // gater-only agent set: pedn_rl_step lets node_kernel apply the actions (no launch of rl_apply_kernel)
-  std::vector<SlotRec> h_slot_rec;
-  SlotRec* d_slot_rec = nullptr;
-  std::vector<double> h_front_u, h_back_u, h_tf_u;
-  double *d_front_u = nullptr, *d_back_u = nullptr, *d_tf_u = nullptr;
-  std::vector<int32_t> h_node_dyn, h_slot_dyn;  // per node: dynamic; per slot: SlotRec.dyn (0 static, 1 turn_frac_kernel, 2 tabulated)
-  std::vector<int32_t> h_node_slot_ptr;
-  std::vector<double> h_ttab, h_ttab_r;         // host copies of turn_tab [T+1][n_turns] / turn_tab_r [n_turns][R] (tabulated rows: final values)
-  std::vector<char> h_rl_link;
-  LinkPR* d_prm = nullptr;           // per-replica link parameters [L][RS] (pedn_set_link_params, pedn_randomize_scenarios)
-  LinkPR* d_prm_draw = nullptr;      // recent-history mode: where pedn_randomize_scenarios draws before the result is accepted
-  double *d_pair_pod_r = nullptr, *d_turn_tab_r = nullptr;
-  // per-replica OD weights and the tables derived from them on the device (scenario_pod_tables)
-  double *d_od_w_r = nullptr, *d_pod_tot = nullptr;     // [n_od][RS], [n_up][RS]
-  const int32_t *d_up_od_ptr = nullptr, *d_upod_od = nullptr, *d_upod_up = nullptr, *d_pair_upod = nullptr, *d_turn_pair_ptr = nullptr,
-                *d_turn_mode = nullptr, *d_tab_rows = nullptr;
-  int n_tab_rows = 0, n_upod = 0;
-  bool pod_tables_uploaded = false, ttab_r_stale = false;   // h_ttab_r is older than turn_tab_r on the device
-  int* d_max_tau = nullptr;
-  int n_pair = 0, n_up = 0, n_over = 0;
-  int n_tf_heavy_quads = 0;  // leading workgroups of turn_frac_body with long chains (more than PEDN_TF_HEAVY_GROUPS softmax groups in a row)
-  long step_epoch = 1;  // counts launched steps; h_tf_set_epoch[node] == step_epoch: fractions imposed since the last step
-  std::vector<long> h_tf_set_epoch;
-  int rows64[7], rows32[6];  // history rows of every field (T+1, or the size of its ring in recent-history mode)
-  int last_t = -1;     // last step launched (pedn_get_turning_fractions: which buffer holds a dynamic node's fractions)
-  std::vector<void*> allocs;
-  // host <-> device staging: two slots used in turn, each a pinned host buffer + a device buffer + the event recorded behind
-  // the slot's last consumer, so that an upload neither waits for the stream nor borrows caller memory beyond the call
-  struct Stage { void* pin = nullptr; void* dev = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
-  Stage stage[2];
-  int stage_next = 0;
-  void* rl_pin = nullptr;      // pinned landing buffer of the RL step's observations + rewards (rl_fetch)
-  size_t rl_pin_bytes = 0;
-  std::string err;
-  struct MetricsState* metrics = nullptr;   // evaluation metrics (pedn_metrics.hpp)
-  // running normalisation (pedn_rl_norm_*, pedn_norm.hpp): the view its launch carries; buffers belong to the agent set
-  NormView nv = {};
-  bool norm_on = false, norm_alloc = false;
-  std::vector<int32_t> h_norm_tracked, h_norm_agent;   // [O]: tracked mask, agent of every column
-  // rollout store (pedn_rollout_*, pedn_rollout.hpp): the view its launches carry (zeroed while there is none) and its own allocations
-  RolloutView ro = {};
-  bool ro_on = false, ro_begun = false, ro_finished = false;
-  int ro_rows = 0;
-  std::vector<void*> ro_allocs;
-  // replay store (pedn_replay_*, pedn_replay.hpp): the same for the off-policy ring; the two stores may live side by side
-  ReplayView rp = {};
-  bool rp_on = false, rp_begun = false;
-  std::vector<void*> rp_allocs;
-};
-static void metrics_free(pedn_sim* s);
-
-// the quiet words of the last step may not be used by the next launch (pedn_sim.quiet_valid)
-static inline void no_quiet(pedn_sim* s) { s->quiet_valid = -1; }
-
-// zero elision: may a launch that writes row `row` of a group whose mark is `hw` skip its +0.0 stores (pedn_sim.zhw64 / zhw32)?
-// (recent-history mode: ring rows are reused, never)
-static inline int32_t zero_gate(const pedn_sim* s, int hw, int row) { return s->zero_elide && !s->v.hist && row > hw ? 1 : 0; }
-
-static int fail(pedn_sim* s, int code, const std::string& msg) {
-  g_last_error = msg;
-  if (s) s->err = msg;
-  return code;
-}
-
-#define HIP_TRY(sim, expr)                                                                     \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      return fail(sim, PEDN_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));      \
-  } while (0)
-
-template <typename T>
-static int upload(pedn_sim* s, const T* src, size_t n, const T** dst) {
-  void* p = nullptr;
-  size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  HIP_TRY(s, hipMalloc(&p, bytes));
-  s->allocs.push_back(p);
-  if (n) HIP_TRY(s, hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-  *dst = (const T*)p;
-  return PEDN_OK;
-}
-
-template <typename T>
-static int dalloc(pedn_sim* s, size_t n, T** dst) {
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-  if (e != hipSuccess) return fail(s, PEDN_E_NOMEM, std::string("hipMalloc of ") + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e));
-  s->allocs.push_back(p);
-  *dst = (T*)p;
-  return PEDN_OK;
-}
-
-// A staging slot of at least `bytes` whose previous use has completed (the other slot may still be in flight).
-#define PEDN_DIRECT_READ_BYTES 65536     // pedn_read_block: up to this size the gather kernel writes into the pinned buffer itself
-#define PEDN_IN_PLACE_BYTES (4u << 20)   // host rows up to this size are read in place by their consuming kernel (stage_in_place; measured up to 256 KB)
-static int stage_acquire(pedn_sim* s, size_t bytes, pedn_sim::Stage** out) {
-  pedn_sim::Stage& st = s->stage[s->stage_next];
-  s->stage_next ^= 1;
-  if (!st.done) HIP_TRY(s, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-  else HIP_TRY(s, hipEventSynchronize(st.done));
-  if (bytes > st.bytes) {
-    if (st.dev) HIP_TRY(s, hipFree(st.dev));
-    if (st.pin) HIP_TRY(s, hipHostFree(st.pin));
-    st.dev = st.pin = nullptr;
-    st.bytes = 0;
-    const size_t want = std::max<size_t>(bytes, 1 << 20);
-    HIP_TRY(s, hipMalloc(&st.dev, want));
-    HIP_TRY(s, hipHostMalloc(&st.pin, want, hipHostMallocDefault));
-    st.bytes = want;
-  }
-  *out = &st;
-  return PEDN_OK;
-}
-
-// host values -> the slot's device buffer (through its pinned buffer: the caller's memory is not touched after the return)
-static int stage_upload(pedn_sim* s, pedn_sim::Stage* st, const void* src, size_t bytes, size_t offset = 0) {
-  memcpy((char*)st->pin + offset, src, bytes);
-  HIP_TRY(s, hipMemcpyAsync((char*)st->dev + offset, (char*)st->pin + offset, bytes, hipMemcpyHostToDevice, s->stream));
-  return PEDN_OK;
-}
-
-// call after the last launch that reads or writes the slot
-static int stage_commit(pedn_sim* s, pedn_sim::Stage* st) {
-  HIP_TRY(s, hipEventRecord(st->done, s->stream));
-  return PEDN_OK;
-}
-
-// Host rows that ONE kernel reads once (the action rows of a host-driven env step): copied into a pinned slot and read by the kernel IN
-// PLACE over the bus -- no copy command in front of the launch (a DMA costs ~20 us of stream latency, a copy from pageable memory waits
-// for the stream; the consuming wave's bus read costs it ~2 us).  The caller records the slot's event behind the consuming launch
-// (stage_commit).  2048 envs: 93-96 -> 81 us per host-driven step, 48 -> 29 without a fetch.
-static int stage_in_place(pedn_sim* s, const void* src, size_t bytes, pedn_sim::Stage** out) {
-  int rc = stage_acquire(s, bytes, out);
-  if (rc != PEDN_OK) return rc;
-  memcpy((*out)->pin, src, bytes);
-  return PEDN_OK;
-}
-
-// host bytes -> a device buffer of the engine; the caller's memory is borrowed for the call only, so the copy is waited for (rows beyond
-// PEDN_IN_PLACE_BYTES; what was measured instead for smaller ones -- a copy COMMAND from a pinned slot, a copy KERNEL from it -- lost to
-// reading them in place, profiles/r05_host_step_time.txt)
-static int upload_through_stage(pedn_sim* s, void* dst, const void* src, size_t bytes) {
-  HIP_TRY(s, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  return PEDN_OK;
-}
+#include "pedn_metrics.hpp"
 
 // The first launch on a stream and the first cross-stream wait cost the runtime ~0.2 ms (queue creation, signal set-up): pay
 // that when the two-chain plan is chosen, not inside the first pedn_run that uses it.
@@ -521,21 +286,11 @@ static int scenario_pod_tables(pedn_sim* s) {
   return PEDN_OK;
 }
 
-extern "C" {
-
+// (the entry points below have C linkage from their declarations in include/pedn.h)
 static int push_rows(pedn_sim* s, double* dst, const double* values, int n_rows, size_t row0, size_t row_stride, int replica);
 static void flush_links(pedn_sim* s, int half, hipEvent_t* ev);
-static inline void pending_links_first(pedn_sim* s);
-static inline void join_forked(pedn_sim* s);
-typedef void (*node_kernel_fn)(DevView, int);
-static node_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf);
-static int clock_end(pedn_sim* s);
-static void norm_launch(pedn_sim* s, hipStream_t st, int rewards, int term);
-static int norm_reset_returns(pedn_sim* s);
-static void rollout_drop(pedn_sim* s);
-static void rollout_sources(pedn_sim* s);
-static void replay_drop(pedn_sim* s);
-static void replay_sources(pedn_sim* s);
+typedef void (*step_kernel_fn)(DevView, int);   // node_kernel, turn_frac_kernel, link_kernel_1r
+static step_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf);
 static void prewarm_chains(pedn_sim* s);
 static int fork_chains(pedn_sim* s, int n);
 
@@ -1131,8 +886,8 @@ int pedn_destroy(pedn_sim* s) {
   if (s->stream2) hipStreamSynchronize(s->stream2);
   if (s->stream) hipStreamSynchronize(s->stream);
   metrics_free(s);
-  rollout_drop(s);
-  replay_drop(s);
+  store_drop(s->ro);
+  store_drop(s->rp);
   for (void* p : s->allocs) hipFree(p);
   if (s->rl_pin) hipHostFree(s->rl_pin);
   for (pedn_sim::Stage& st : s->stage) {
@@ -1150,7 +905,8 @@ int pedn_destroy(pedn_sim* s) {
   return PEDN_OK;
 }
 
-int pedn_reset(pedn_sim* s) {
+// what both resets do in front of clearing the state: the host's bookkeeping back to "nothing has run"
+static int reset_bookkeeping(pedn_sim* s) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   HIP_TRY(s, hipSetDevice(s->device));
   join_forked(s);
@@ -1158,22 +914,16 @@ int pedn_reset(pedn_sim* s) {
   s->last_t = -1;
   s->link_pending = -1;   // discarded: the state it would complete is being cleared
   no_quiet(s);
-  int rc = norm_reset_returns(s);
-  if (rc != PEDN_OK) return rc;
-  return reset_state(s);
+  return norm_reset_returns(s);
 }
 
+int pedn_reset(pedn_sim* s) {
+  const int rc = reset_bookkeeping(s);
+  return rc != PEDN_OK ? rc : reset_state(s);
+}
 int pedn_reset_lazy(pedn_sim* s) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  HIP_TRY(s, hipSetDevice(s->device));
-  join_forked(s);
-  s->tp_ready = -1;
-  s->last_t = -1;
-  s->link_pending = -1;
-  no_quiet(s);
-  int rc = norm_reset_returns(s);
-  if (rc != PEDN_OK) return rc;
-  return reset_state_lazy(s);
+  const int rc = reset_bookkeeping(s);
+  return rc != PEDN_OK ? rc : reset_state_lazy(s);
 }
 
 // values (host) -> rows of a [rows][RS] device array, one replica or all
@@ -1473,7 +1223,7 @@ static void row_bases(DevView& vn, int t) {
 
 // lu: the instantiation whose slot waves perform the link update of step t-1 themselves (node_kernel<..., LU = true>)
 // tf: ... and compute their own rows of turning fractions (node_kernel<.., TF> / with helper waves node_kernel_h)
-static node_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf) {
+static step_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf) {
   const bool h = s->v.hist != 0;  // recent-history mode: the instantiations that mask the history rows
   const bool d6 = s->max_degree <= 6;  // loops and the row of turning fractions unrolled for 6 instead of 8 corridors per node
 #define PEDN_NK(PR_, LP_, LU_, TF_) (h ? (d6 ? node_kernel<PR_, LP_, true, 6, LU_, TF_> : node_kernel<PR_, LP_, true, 8, LU_, TF_>) \
@@ -1490,13 +1240,43 @@ static node_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf) {
 }
 
 // the node kernel of a clocked env step (pedn_rl_step_clocked): the step index comes from DevView.clock
-static node_kernel_fn clocked_node_kernel_for(const pedn_sim* s) {
+static step_kernel_fn clocked_node_kernel_for(const pedn_sim* s) {
   const bool h = s->v.hist != 0, d6 = s->max_degree <= 6;
 #define PEDN_NKC(PR_) (h ? (d6 ? node_kernel<PR_, false, true, 6, false, false, true> : node_kernel<PR_, false, true, 8, false, false, true>) \
                          : (d6 ? node_kernel<PR_, false, false, 6, false, false, true> : node_kernel<PR_, false, false, 8, false, false, true>))
   return s->v.pr ? PEDN_NKC(true) : PEDN_NKC(false);   // (not built for the node LP: pedn_rl_clock_begin refuses)
 #undef PEDN_NKC
 }
+
+// the other step kernels, by the view's per-replica link parameters (pr) and recent-history mode (hist)
+static step_kernel_fn turn_frac_kernel_for(const DevView& v) {
+  if (v.pr) return v.hist ? turn_frac_kernel<true, true> : turn_frac_kernel<true, false>;
+  return v.hist ? turn_frac_kernel<false, true> : turn_frac_kernel<false, false>;
+}
+static step_kernel_fn link_kernel_1r_for(const DevView& v) {
+  if (v.pr) return v.hist ? link_kernel_1r<true, true> : link_kernel_1r<true, false>;
+  return v.hist ? link_kernel_1r<false, true> : link_kernel_1r<false, false>;
+}
+// obs: the observations ride in the launch; clk: the launch of a clocked env step (it always observes)
+typedef void (*link_turn_kernel_fn)(DevView, int, unsigned, unsigned, unsigned, RlView, int);
+static link_turn_kernel_fn link_turn_kernel_for(const DevView& v, bool obs, bool clk) {
+#define PEDN_LTK(OBS_, CLK_) (v.pr ? (v.hist ? link_turn_kernel<true, OBS_, true, CLK_> : link_turn_kernel<true, OBS_, false, CLK_>) \
+                                   : (v.hist ? link_turn_kernel<false, OBS_, true, CLK_> : link_turn_kernel<false, OBS_, false, CLK_>))
+  if (clk) return PEDN_LTK(true, true);
+  return obs ? PEDN_LTK(true, false) : PEDN_LTK(false, false);
+#undef PEDN_LTK
+}
+// the controller twins (pedn_ctrl.hpp)
+typedef void (*ctrl_link_turn_kernel_fn)(DevView, int, unsigned, unsigned, unsigned, RlView, int, CtrlView);
+static ctrl_link_turn_kernel_fn ctrl_link_turn_kernel_for(const DevView& v) {
+  if (v.pr) return v.hist ? ctrl_link_turn_kernel<true, true> : ctrl_link_turn_kernel<true, false>;
+  return v.hist ? ctrl_link_turn_kernel<false, true> : ctrl_link_turn_kernel<false, false>;
+}
+// (the observations as a launch of their own: the plain kernel and its twin differ in their arguments, so a selector each)
+typedef void (*rl_observe_kernel_fn)(DevView, RlView, int, int);
+static rl_observe_kernel_fn rl_observe_kernel_for(const DevView& v) { return v.hist ? rl_observe_kernel<true> : rl_observe_kernel<false>; }
+typedef void (*ctrl_observe_kernel_fn)(DevView, RlView, int, int, CtrlView);
+static ctrl_observe_kernel_fn ctrl_observe_kernel_for(const DevView& v) { return v.hist ? ctrl_observe_kernel<true> : ctrl_observe_kernel<false>; }
 
 // The link update of step t as a launch of its own (the second launch of a step of a model without dynamic turning fractions, and
 // the flush of a pending update under the owner-wave plan): one replica per lane.  e >= 0: start / stop events ev[e], ev[e + 1].
@@ -1510,9 +1290,20 @@ static void launch_link_update(pedn_sim* s, const DevView& v, hipStream_t stream
   };
   const unsigned nlb = link_blocks(v, true);
   if (nlb == 0) return;
-  if (v.pr) { if (v.hist) launch(link_kernel_1r<true, true>, dim3(nlb), dim3(256), v, t); else launch(link_kernel_1r<true, false>, dim3(nlb), dim3(256), v, t); }
-  else { if (v.hist) launch(link_kernel_1r<false, true>, dim3(nlb), dim3(256), v, t); else launch(link_kernel_1r<false, false>, dim3(nlb), dim3(256), v, t); }
+  launch(link_kernel_1r_for(v), dim3(nlb), dim3(256), v, t);
 }
+
+// Workgroups of a step's launches for the share of the batch that v is (view_of): rgroups groups of 64 replicas; tf_blocks: a wave per (row
+// of a dynamic node, 64 replicas), four to a workgroup.  The second launch (link_turn_kernel and its twins) is nlb workgroups of link update,
+// ntb of the turning fractions of t + 1 (fused; nth of them heavy rows, run in front of the link update), nob of observations (one per agent).
+struct StepGrid {
+  unsigned rgroups, nlb, ntb, nth, nob;
+  StepGrid(const pedn_sim* s, const DevView& v, unsigned link_blocks_, bool fused, bool obs)
+      : rgroups((unsigned)(v.subRS / 64)), nlb(link_blocks_), ntb(fused ? tf_blocks(v) : 0u),
+        nth(fused ? (unsigned)s->n_tf_heavy_quads * rgroups : 0u), nob(obs ? (unsigned)s->rl.n_agents * rgroups : 0u) {}
+  unsigned tf_blocks(const DevView& v) const { return (unsigned)((v.n_trow + 3) / 4) * rgroups; }
+  dim3 second() const { return dim3(nlb + ntb + nob); }
+};
 
 // this launch's share of the batch: the whole of it on the engine's stream (half = -1) or one half of the replicas per stream
 // (half = index of the chain, 0 or 1: each steps its share of the replicas on its own stream)
@@ -1580,14 +1371,14 @@ static void prewarm_chains(pedn_sim* s) {
   vl.n_pairs_corr = 0;
   vl.n_trow = 0;
   RlView q{};
+  DevView sel = vl;
+  sel.pr = 0;   // (what is warmed are the instantiations without per-replica parameters, whatever the engine holds)
   for (int c = 0; c < s->chains; ++c) {
     hipStream_t st = chain_stream(s, c);
     for (int lu = 0; lu < 2; ++lu) hipLaunchKernelGGL(node_kernel_for(s, lu != 0, false), dim3(1, 1), dim3(512), s->node_lds, st, v, 2);
     if (s->inline_tf) hipLaunchKernelGGL(node_kernel_for(s, true, true), dim3(1, 1), dim3(s->inline_help ? 1024 : 512), s->node_lds_tf, st, v, 2);
-    if (vl.hist) { hipLaunchKernelGGL((link_turn_kernel<false, false, true>), dim3(1), dim3(256), 0, st, vl, 1, 0u, 0u, 0u, q, 0);
-                   hipLaunchKernelGGL((link_kernel_1r<false, true>), dim3(1), dim3(256), 0, st, vl, 1); }
-    else { hipLaunchKernelGGL((link_turn_kernel<false, false, false>), dim3(1), dim3(256), 0, st, vl, 1, 0u, 0u, 0u, q, 0);
-           hipLaunchKernelGGL((link_kernel_1r<false, false>), dim3(1), dim3(256), 0, st, vl, 1); }
+    hipLaunchKernelGGL(link_turn_kernel_for(sel, false, false), dim3(1), dim3(256), 0, st, vl, 1, 0u, 0u, 0u, q, 0);
+    hipLaunchKernelGGL(link_kernel_1r_for(sel), dim3(1), dim3(256), 0, st, vl, 1);
   }
   for (int c = s->chains - 1; c >= 0; --c) hipStreamSynchronize(chain_stream(s, c));
 }
@@ -1634,7 +1425,6 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   vn.zg32 = lu ? zero_gate(s, zhw32, t - 1) : 0;
   if (vn.zg64 || vn.zg32) ++s->zgated;
   row_bases(vn, t);
-  const unsigned rgroups = (unsigned)(v.subRS / 64);
   // the turning fractions of t + 1 ride in the launch behind node_kernel(t) -- except behind the last step of the horizon, where
   // pair_pod / turn_tab have no row T + 1 to read (they hold T + 1 rows, 0..T) and nothing would consume the result
   // (and not under the single-launch plan, where the next step computes its own rows)
@@ -1644,54 +1434,36 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
     if (ev) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ev[e], ev[e + 1], 0, args...);
     else hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
   };
+  // link update: one replica per lane as a launch of its own and with per-replica parameters, two inside link_turn_kernel (link_body)
+  const bool one_r = v.pr || (!fused && !obs_fused);
+  // (lazy: no link-update workgroups in this step's second launch)
+  const StepGrid g(s, v, lazy ? 0u : link_blocks(v, one_r), fused, obs_fused);
   if (tf_alone) {  // first step of an episode, a repeated or an out-of-order step
-    const unsigned nb = (unsigned)((v.n_trow + 3) / 4) * rgroups;  // one wave per (row of a dynamic node, 64 replicas)
-    if (v.pr) { if (v.hist) launch(turn_frac_kernel<true, true>, dim3(nb), dim3(256), 0, v, t); else launch(turn_frac_kernel<true, false>, dim3(nb), dim3(256), 0, v, t); }
-    else { if (v.hist) launch(turn_frac_kernel<false, true>, dim3(nb), dim3(256), 0, v, t); else launch(turn_frac_kernel<false, false>, dim3(nb), dim3(256), 0, v, t); }
+    launch(turn_frac_kernel_for(v), dim3(g.tf_blocks(v)), dim3(256), 0, v, t);
     s->tp_ran = 1;
   }
   const size_t nlds = inl ? s->node_lds_tf : s->node_lds;
   const dim3 nblock(inl && s->inline_help ? 1024 : 512);   // helper waves: sixteen per workgroup
-  if (ev) hipExtLaunchKernelGGL(node_kernel_for(s, lu, inl), dim3(rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, ev[2], ev[3], 0, vn, t);
-  else hipLaunchKernelGGL(node_kernel_for(s, lu, inl), dim3(rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, vn, t);
+  if (ev) hipExtLaunchKernelGGL(node_kernel_for(s, lu, inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, ev[2], ev[3], 0, vn, t);
+  else hipLaunchKernelGGL(node_kernel_for(s, lu, inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, vn, t);
   if (inl && last_chain(s, half)) s->tp_ready = t;   // the fractions of t are in tfd[t & 1] (a following step that cannot inline computes its own)
-  // link update: one replica per lane as a launch of its own and with per-replica parameters, two inside link_turn_kernel (link_body)
-  const bool one_r = v.pr || (!fused && !obs_fused);
-  const unsigned nlb = lazy ? 0u : link_blocks(v, one_r);   // lazy: no link-update workgroups in this step's second launch
   if (last_chain(s, half)) {
     s->link_pending = lazy ? t : -1;
     s->quiet_valid = quiet ? t : -1;
     s->zhw64 = std::max(s->zhw64, t);
     if (lu) s->zhw32 = std::max(s->zhw32, t - 1);
-    if (nlb > 0) s->zhw32 = std::max(s->zhw32, t);   // the link update of t below
+    if (g.nlb > 0) s->zhw32 = std::max(s->zhw32, t);   // the link update of t below
   }
   s->second_launch = 1;
   if (fused || obs_fused) {
-    const unsigned ntb = fused ? (unsigned)((v.n_trow + 3) / 4) * rgroups : 0u;
-    const unsigned nth = fused ? (unsigned)s->n_tf_heavy_quads * rgroups : 0u;  // of which in front of the link update
-    const unsigned nob = obs_fused ? (unsigned)s->rl.n_agents * rgroups : 0u;  // one block per (agent, 64 replicas)
     RlView q = s->rl;
     if (!obs_fused) q.n_agents = 0;
     const int acc = observe > 0 ? 1 : 0;
-    const dim3 grid(nlb + ntb + nob), block(256);
-    // instantiation by (per-replica parameters, observations in the launch, recent-history mode)
-#define PEDN_LT(PR_, OBS_) do { if (v.hist) launch(link_turn_kernel<PR_, OBS_, true>, grid, block, 4, v, t, nlb, ntb, nth, q, acc); \
-                                else launch(link_turn_kernel<PR_, OBS_, false>, grid, block, 4, v, t, nlb, ntb, nth, q, acc); } while (0)
-    if (obs_fused && cv) {
-      if (v.pr) { if (v.hist) launch(ctrl_link_turn_kernel<true, true>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv);
-                  else launch(ctrl_link_turn_kernel<true, false>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv); }
-      else { if (v.hist) launch(ctrl_link_turn_kernel<false, true>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv);
-             else launch(ctrl_link_turn_kernel<false, false>, grid, block, 4, v, t, nlb, ntb, nth, q, acc, *cv); }
-    } else if (obs_fused) {
-      if (v.pr) PEDN_LT(true, true);
-      else PEDN_LT(false, true);
-    } else {
-      if (v.pr) PEDN_LT(true, false);
-      else PEDN_LT(false, false);
-    }
-#undef PEDN_LT
+    const dim3 block(256);
+    if (obs_fused && cv) launch(ctrl_link_turn_kernel_for(v), g.second(), block, 4, v, t, g.nlb, g.ntb, g.nth, q, acc, *cv);
+    else launch(link_turn_kernel_for(v, obs_fused, false), g.second(), block, 4, v, t, g.nlb, g.ntb, g.nth, q, acc);
     if (fused && last_chain(s, half)) s->tp_ready = t + 1;   // the other chains of this step still have to see the old value
-  } else if (nlb > 0) {
+  } else if (g.nlb > 0) {
     launch_link_update(s, v, stream, t, ev, 4);
   }
   else s->second_launch = 0;
@@ -2324,11 +2096,11 @@ int pedn_rl_configure(pedn_sim* s, const pedn_rl_desc* d, int32_t* n_actions, in
     v.rl_actions = nullptr;
   }
   s->rl_ready = true;
-  s->ctrl_ready = s->ctrl_any = false;   // controllers belong to an agent set: configure them again
-  s->norm_on = s->norm_alloc = false;    // so does the running normalisation
-  memset(&s->nv, 0, sizeof s->nv);
-  rollout_drop(s);                       // and a rollout store (its rows have the agent set's widths)
-  replay_drop(s);                        // and a replay store
+  s->ctrl.ready = s->ctrl.any = false;   // controllers belong to an agent set: configure them again
+  s->norm.on = s->norm.alloc = false;    // so does the running normalisation
+  memset(&s->norm.view, 0, sizeof s->norm.view);
+  store_drop(s->ro);                     // and a rollout store (its rows have the agent set's widths)
+  store_drop(s->rp);                     // and a replay store
   if (n_actions) *n_actions = A;
   if (n_obs) *n_obs = O;
   return PEDN_OK;
@@ -2363,8 +2135,8 @@ int pedn_rl_apply_actions(pedn_sim* s, const double* actions, int32_t on_device)
 // pageable memory each copy is staged and waited for by the runtime on its own)
 static int rl_fetch(pedn_sim* s, float* obs, float* rewards, bool raw = false) {
   if (!obs && !rewards) return PEDN_OK;
-  RlView q = s->rl;
-  if (s->norm_on && !raw) { q.obs = s->nv.obs_n; q.rew = s->nv.rew_n; }   // (contiguous like the raw pair)
+  const RlView& q = s->rl;
+  const FetchRows rows = fetch_rows(s, raw);
   const size_t nb_obs = (size_t)s->v.R * q.O * sizeof(float), nb_rew = (size_t)s->v.R * q.n_agents * sizeof(float);
   if (s->rl_pin_bytes < nb_obs + nb_rew) {
     if (s->rl_pin) HIP_TRY(s, hipHostFree(s->rl_pin));
@@ -2374,9 +2146,9 @@ static int rl_fetch(pedn_sim* s, float* obs, float* rewards, bool raw = false) {
     s->rl_pin_bytes = nb_obs + nb_rew;
   }
   char* pin = (char*)s->rl_pin;
-  if (obs && rewards) HIP_TRY(s, hipMemcpyAsync(pin, q.obs, nb_obs + nb_rew, hipMemcpyDeviceToHost, s->stream));   // (contiguous: pedn_rl_configure)
-  else if (obs) HIP_TRY(s, hipMemcpyAsync(pin, q.obs, nb_obs, hipMemcpyDeviceToHost, s->stream));
-  else HIP_TRY(s, hipMemcpyAsync(pin + nb_obs, q.rew, nb_rew, hipMemcpyDeviceToHost, s->stream));
+  if (obs && rewards) HIP_TRY(s, hipMemcpyAsync(pin, rows.obs, nb_obs + nb_rew, hipMemcpyDeviceToHost, s->stream));   // (contiguous: pedn_rl_configure)
+  else if (obs) HIP_TRY(s, hipMemcpyAsync(pin, rows.obs, nb_obs, hipMemcpyDeviceToHost, s->stream));
+  else HIP_TRY(s, hipMemcpyAsync(pin + nb_obs, rows.rew, nb_rew, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (obs) memcpy(obs, pin, nb_obs);
   if (rewards) memcpy(rewards, pin + nb_obs, nb_rew);
@@ -2385,7 +2157,7 @@ static int rl_fetch(pedn_sim* s, float* obs, float* rewards, bool raw = false) {
 
 // (cv: the controller twin, see launch_step)
 // norm: 0 no normalisation launch (a sub-step inside an env step), 1 behind an observation alone, 2 behind an env step (term: its terminated flag)
-static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards, const CtrlView* cv, int norm = 0, int term = 0) {
+static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards, const CtrlView* cv, int norm, int term) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
   if (t < 0 || t > s->v.T1 - 1) return fail(s, PEDN_E_ARG, "time step outside 0..T");
@@ -2395,11 +2167,8 @@ static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, fl
   DevView& v = s->v;
   RlView& q = s->rl;
   const dim3 grid((unsigned)q.n_agents * (unsigned)(v.RS / 64));
-  if (cv) {
-    if (v.hist) hipLaunchKernelGGL(ctrl_observe_kernel<true>, grid, dim3(256), 0, s->stream, v, q, t, accumulate, *cv);
-    else hipLaunchKernelGGL(ctrl_observe_kernel<false>, grid, dim3(256), 0, s->stream, v, q, t, accumulate, *cv);
-  } else if (v.hist) hipLaunchKernelGGL(rl_observe_kernel<true>, grid, dim3(256), 0, s->stream, v, q, t, accumulate);
-  else hipLaunchKernelGGL(rl_observe_kernel<false>, grid, dim3(256), 0, s->stream, v, q, t, accumulate);
+  if (cv) hipLaunchKernelGGL(ctrl_observe_kernel_for(v), grid, dim3(256), 0, s->stream, v, q, t, accumulate, *cv);
+  else hipLaunchKernelGGL(rl_observe_kernel_for(v), grid, dim3(256), 0, s->stream, v, q, t, accumulate);
   if (norm) norm_launch(s, s->stream, norm == 2, term);
   HIP_TRY(s, hipGetLastError());
   return rl_fetch(s, obs, rewards);
@@ -2409,30 +2178,22 @@ int pedn_rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, floa
   return rl_observe(s, t, accumulate, obs, rewards, nullptr, 1);
 }
 
-int pedn_rl_fetch(pedn_sim* s, float* obs, float* rewards) {
+static int fetch_entry(pedn_sim* s, float* obs, float* rewards, bool raw) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
   HIP_TRY(s, hipSetDevice(s->device));
   join_forked(s);   // (ends a clocked section; both chains' work in front of the copies)
-  return rl_fetch(s, obs, rewards);
+  return rl_fetch(s, obs, rewards, raw);
 }
 
-int pedn_rl_fetch_raw(pedn_sim* s, float* obs, float* rewards) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  join_forked(s);
-  return rl_fetch(s, obs, rewards, true);
-}
-
-// cv: a controlled env step (pedn_ctrl_step) -- its last sub-step observes through the controller twins
-static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t t, int32_t action_gap, float* obs, float* rewards,
-                   const CtrlView* cv);
+int pedn_rl_fetch(pedn_sim* s, float* obs, float* rewards) { return fetch_entry(s, obs, rewards, false); }
+int pedn_rl_fetch_raw(pedn_sim* s, float* obs, float* rewards) { return fetch_entry(s, obs, rewards, true); }
 
 int pedn_rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t t, int32_t action_gap, float* obs, float* rewards) {
   return rl_step(s, actions, on_device, t, action_gap, obs, rewards, nullptr);
 }
 
+// cv: a controlled env step (pedn_ctrl_step) -- its last sub-step observes through the controller twins
 static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t t, int32_t action_gap, float* obs, float* rewards,
                    const CtrlView* cv) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
@@ -2480,7 +2241,7 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
   // on_device == 2: the caller chains this call between its own streams and pedn_stream() with events (no host synchronisation):
   // everything must then be ordered by the engine's stream alone
   const int term = t + action_gap - 1 >= s->v.T1 - 1 ? 1 : 0;   // pz_pednet_env.py:592
-  const bool two = !s->norm_on && on_device != 2 && (s->rl_chains == 2 || (s->rl_chains == 0 && by_batch)) && s->warmed_chains >= 2 && s->v.RS >= 256 && s->fuse_obs && (!actions || (fold != nullptr && on_device)) && !obs && !rewards &&
+  const bool two = !s->norm.on && on_device != 2 && (s->rl_chains == 2 || (s->rl_chains == 0 && by_batch)) && s->warmed_chains >= 2 && s->v.RS >= 256 && s->fuse_obs && (!actions || (fold != nullptr && on_device)) && !obs && !rewards &&
                    s->link_pending < 0 && !(s->v.n_trow > 0 && !s->fuse_tp);
   if (!two) join_forked(s);
   else if (!s->forked) {
@@ -2498,9 +2259,10 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
       for (int c = 0; c < 2; ++c) launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, c, false, ck);
       s->run_chains = 1;
       if ((last && (obs || rewards)) || !observed) join_forked(s);
-    } else
+    } else {
       if ((rc = launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, -1, false, ck)) != PEDN_OK) return rc;
-      if (k == 0 && fold_stage && (rc = stage_commit(s, fold_stage)) != PEDN_OK) return rc;   // its only reader has been launched
+    }
+    if (k == 0 && fold_stage && (rc = stage_commit(s, fold_stage)) != PEDN_OK) return rc;   // its only reader has been launched
     HIP_TRY(s, hipGetLastError());
     if (!observed) {
       if ((rc = rl_observe(s, t + k, k > 0, last ? obs : nullptr, last ? rewards : nullptr, ck, last ? 2 : 0, term)) != PEDN_OK) return rc;
@@ -2574,21 +2336,14 @@ int pedn_rl_step_clocked(pedn_sim* s, const double* actions, int32_t action_gap,
       hipLaunchKernelGGL(rl_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, v, qq);
     }
   }
-  const unsigned rgroups = (unsigned)(v.RS / 64);
-  const bool fused = v.n_trow > 0;   // the fractions of t + 1 ride in the second launch (its workgroups idle behind the last step)
-  const unsigned nlb = link_blocks(v, v.pr != 0);
-  const unsigned ntb = fused ? (unsigned)((v.n_trow + 3) / 4) * rgroups : 0u, nth = fused ? (unsigned)s->n_tf_heavy_quads * rgroups : 0u;
-  const unsigned nob = (unsigned)q.n_agents * rgroups;
+  // the fractions of t + 1 ride in the second launch (its workgroups idle behind the last step); it always observes
+  const StepGrid g(s, v, link_blocks(v, v.pr != 0), v.n_trow > 0, true);
   for (int k = 0; k < action_gap; ++k) {
     DevView vn = v;
     vn.rl_actions = k == 0 ? fold : nullptr;
-    hipLaunchKernelGGL(clocked_node_kernel_for(s), dim3(rgroups, (unsigned)s->n_blocks), dim3(512), s->node_lds, st, vn, -1);
-    const dim3 grid(nlb + ntb + nob), block(256);
+    hipLaunchKernelGGL(clocked_node_kernel_for(s), dim3(g.rgroups, (unsigned)s->n_blocks), dim3(512), s->node_lds, st, vn, -1);
     const int acc = k > 0 ? 1 : 0;
-    if (v.pr) { if (v.hist) hipLaunchKernelGGL((link_turn_kernel<true, true, true, true>), grid, block, 0, st, v, -1, nlb, ntb, nth, q, acc);
-                else hipLaunchKernelGGL((link_turn_kernel<true, true, false, true>), grid, block, 0, st, v, -1, nlb, ntb, nth, q, acc); }
-    else { if (v.hist) hipLaunchKernelGGL((link_turn_kernel<false, true, true, true>), grid, block, 0, st, v, -1, nlb, ntb, nth, q, acc);
-           else hipLaunchKernelGGL((link_turn_kernel<false, true, false, true>), grid, block, 0, st, v, -1, nlb, ntb, nth, q, acc); }
+    hipLaunchKernelGGL(link_turn_kernel_for(v, true, true), g.second(), dim3(256), 0, st, v, -1, g.nlb, g.ntb, g.nth, q, acc);
   }
   norm_launch(s, st, 1, -1);   // (constant arguments: `terminated` comes from the clock)
   HIP_TRY(s, hipGetLastError());
@@ -2617,15 +2372,15 @@ uint64_t pedn_rl_clock_signature(pedn_sim* s) {
   mix(&s->rl, sizeof s->rl);
   const int64_t sel[8] = {s->rl_fold, s->n_tf_heavy_quads, s->n_blocks, (int64_t)s->node_lds, s->max_degree, s->node_lp, s->fuse_tp, s->fuse_obs};
   mix(sel, sizeof sel);
-  const int64_t on = s->norm_on;   // the normalisation launch and its view (zeroed while off; configure fills every byte it hashes)
+  const int64_t on = s->norm.on;   // the normalisation launch and its view (zeroed while off; configure fills every byte it hashes)
   mix(&on, sizeof on);
-  mix(&s->nv, sizeof s->nv);
-  const int64_t store = s->ro_on;   // a record launch captured with the step carries the store's view (zeroed while there is none)
+  mix(&s->norm.view, sizeof s->norm.view);
+  const int64_t store = s->ro.on;   // a record launch captured with the step carries the store's view (zeroed while there is none)
   mix(&store, sizeof store);
-  mix(&s->ro, sizeof s->ro);
-  const int64_t replay = s->rp_on;   // the same for a captured push launch of the replay store
+  mix(&s->ro.view, sizeof s->ro.view);
+  const int64_t replay = s->rp.on;   // the same for a captured push launch of the replay store
   mix(&replay, sizeof replay);
-  mix(&s->rp, sizeof s->rp);
+  mix(&s->rp.view, sizeof s->rp.view);
   return h;
 }
 
@@ -2643,7 +2398,7 @@ int pedn_rl_step_many(pedn_sim** sims, int32_t n, const double* actions, int32_t
   for (int k = 0; k < n; ++k)
     if (!sims[k] || !sims[k]->rl_ready) return fail(sims[k], PEDN_E_ARG, "null handle or pedn_rl_configure has not been called");
   for (int k = 0; k < n; ++k)
-    if (sims[k]->norm_on) return fail(sims[k], PEDN_E_ARG, "pedn_rl_step_many does not run the running normalisation (statistics are per engine)");
+    if (sims[k]->norm.on) return fail(sims[k], PEDN_E_ARG, "pedn_rl_step_many does not run the running normalisation (statistics are per engine)");
   size_t row = 0;
   for (int k = 0; k < n; ++k) {   // every engine's launches first (own stream each: they overlap) ...
     pedn_sim* s = sims[k];
@@ -2664,644 +2419,6 @@ int pedn_rl_step_many(pedn_sim** sims, int32_t n, const double* actions, int32_t
 void* pedn_rl_device_ptr(pedn_sim* s, int32_t which) {
   if (!s || !s->rl_ready) return nullptr;
   return which == 0 ? (void*)s->rl.actions : which == 1 ? (void*)s->rl.obs : which == 2 ? (void*)s->rl.rew : nullptr;
-}
-
-
-// ---- running observation / reward normalisation on the device (pedn_norm.hpp) --------------------------------------------------
-static void norm_launch(pedn_sim* s, hipStream_t st, int rewards, int term) {
-  if (!s->norm_on) return;
-  const unsigned blocks = (unsigned)((s->nv.O + PEDN_NORM_COLS - 1) / PEDN_NORM_COLS) + 1u;   // + the reward workgroup
-  hipLaunchKernelGGL(norm_kernel, dim3(blocks), dim3(1024), 0, st, s->nv, rewards, term);
-}
-
-static int norm_reset_returns(pedn_sim* s) {   // a new episode: the discounted returns start again, the statistics stay
-  if (!s->norm_alloc) return PEDN_OK;
-  HIP_TRY(s, hipMemsetAsync(s->nv.ret, 0, (size_t)s->v.R * s->rl.n_agents * sizeof(double), s->stream));
-  return PEDN_OK;
-}
-
-static int norm_init_stats(pedn_sim* s) {
-  const int O = s->rl.O;
-  std::vector<double> h((size_t)3 * O + 3);
-  for (int c = 0; c < O; ++c) { h[c] = 0.0; h[(size_t)O + c] = 1.0; h[(size_t)2 * O + c] = 1e-4; }
-  h[(size_t)3 * O] = 0.0; h[(size_t)3 * O + 1] = 1.0; h[(size_t)3 * O + 2] = 1e-4;
-  HIP_TRY(s, hipMemcpy(s->nv.mean, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  return PEDN_OK;
-}
-
-int pedn_rl_norm_configure(pedn_sim* s, int32_t norm_obs, int32_t norm_reward, double clip_obs, double clip_reward, double gamma,
-                           const int32_t* tracked_mask, const int32_t* agent_of_column) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  pending_links_first(s);   // (ends a clocked section: a captured graph is checked against the signature before its next replay)
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  const RlView& q = s->rl;
-  if (!norm_obs && !norm_reward) {   // off: the fetches hand out the raw rows again; the statistics are discarded
-    s->norm_on = false;
-    const NormView keep = s->nv;
-    memset(&s->nv, 0, sizeof s->nv);
-    if (s->norm_alloc) {   // (the buffers stay with the agent set)
-      s->nv.obs_n = keep.obs_n; s->nv.rew_n = keep.rew_n; s->nv.mean = keep.mean; s->nv.var = keep.var; s->nv.count = keep.count;
-      s->nv.ret = keep.ret; s->nv.ret_stats = keep.ret_stats; s->nv.tracked = keep.tracked;
-    }
-    rollout_sources(s);
-    replay_sources(s);
-    return PEDN_OK;
-  }
-  if (s->ctrl_ready) return fail(s, PEDN_E_ARG, "controllers and the running normalisation cannot be combined");
-  if (!tracked_mask || !agent_of_column) return fail(s, PEDN_E_ARG, "null argument");
-  if (!(clip_obs > 0.0) || !(clip_reward > 0.0)) return fail(s, PEDN_E_ARG, "clip_obs and clip_reward must be positive");
-  if (q.n_agents > PEDN_NORM_MAX_AGENTS) return fail(s, PEDN_E_ARG, "more than 1024 agents");
-  if ((int64_t)s->v.R * std::max(q.O, q.n_agents) > 0x7fffffff) return fail(s, PEDN_E_ARG, "observation buffer too large for the normalisation kernel");
-  for (int c = 0; c < q.O; ++c)
-    if (agent_of_column[c] < 0 || agent_of_column[c] >= q.n_agents) return fail(s, PEDN_E_ARG, "agent_of_column out of range");
-  int rc;
-  NormView n;
-  memset(&n, 0, sizeof n);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
-  if (!s->norm_alloc) {
-    double* d = nullptr;
-    float* f = nullptr;
-    int32_t* m = nullptr;
-    const size_t n_ret = (size_t)s->v.R * q.n_agents;
-    if ((rc = dalloc(s, (size_t)3 * q.O + 3 + n_ret, &d)) != PEDN_OK) return rc;
-    if ((rc = dalloc(s, (size_t)s->v.R * q.O + n_ret, &f)) != PEDN_OK) return rc;
-    if ((rc = dalloc(s, (size_t)q.O, &m)) != PEDN_OK) return rc;
-    n.mean = d; n.var = d + q.O; n.count = d + 2 * (size_t)q.O; n.ret_stats = d + 3 * (size_t)q.O; n.ret = n.ret_stats + 3;
-    n.obs_n = f; n.rew_n = f + (size_t)s->v.R * q.O;
-    n.tracked = m;
-    HIP_TRY(s, hipMemset(f, 0, ((size_t)s->v.R * q.O + n_ret) * sizeof(float)));
-  } else {
-    const NormView& o = s->nv;
-    n.mean = o.mean; n.var = o.var; n.count = o.count; n.ret_stats = o.ret_stats; n.ret = o.ret; n.obs_n = o.obs_n; n.rew_n = o.rew_n; n.tracked = o.tracked;
-  }
-  n.obs = q.obs; n.rew = q.rew; n.clock = s->d_clock;
-  n.R = s->v.R; n.O = q.O; n.n_agents = q.n_agents; n.T = s->v.T1 - 1;
-  n.norm_obs = norm_obs ? 1 : 0; n.norm_reward = norm_reward ? 1 : 0; n.training = 1;
-  n.clip_obs = clip_obs; n.clip_reward = clip_reward; n.gamma = gamma;
-  s->nv = n;
-  s->norm_alloc = true;
-  s->h_norm_tracked.assign(tracked_mask, tracked_mask + q.O);
-  for (int32_t& t : s->h_norm_tracked) t = t ? 1 : 0;
-  s->h_norm_agent.assign(agent_of_column, agent_of_column + q.O);
-  HIP_TRY(s, hipMemcpy(const_cast<int32_t*>(n.tracked), s->h_norm_tracked.data(), (size_t)q.O * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(s, hipMemset(n.ret, 0, (size_t)s->v.R * q.n_agents * sizeof(double)));
-  if ((rc = norm_init_stats(s)) != PEDN_OK) return rc;
-  s->norm_on = true;
-  rollout_sources(s);
-  replay_sources(s);
-  return PEDN_OK;
-}
-
-int pedn_rl_norm_set_training(pedn_sim* s, int32_t training) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->norm_on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
-  HIP_TRY(s, hipSetDevice(s->device));
-  join_forked(s);   // (the flag travels in the launch's arguments: a clocked section ends, a captured graph is captured again)
-  s->nv.training = training ? 1 : 0;
-  return PEDN_OK;
-}
-
-int pedn_rl_norm_get_stats(pedn_sim* s, double* mean, double* var, double* count, double* ret_stats) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->norm_on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
-  HIP_TRY(s, hipSetDevice(s->device));
-  join_forked(s);
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  const int O = s->nv.O;
-  std::vector<double> h((size_t)3 * O + 3);
-  HIP_TRY(s, hipMemcpy(h.data(), s->nv.mean, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  if (mean) memcpy(mean, h.data(), (size_t)O * sizeof(double));
-  if (var) memcpy(var, h.data() + O, (size_t)O * sizeof(double));
-  if (count) {   // per agent: the count of its tracked columns (they all carry the same one)
-    for (int a = 0; a < s->nv.n_agents; ++a) count[a] = 1e-4;
-    for (int c = O - 1; c >= 0; --c)
-      if (s->h_norm_tracked[c]) count[s->h_norm_agent[c]] = h[(size_t)2 * O + c];
-  }
-  if (ret_stats) memcpy(ret_stats, h.data() + (size_t)3 * O, 3 * sizeof(double));
-  return PEDN_OK;
-}
-
-int pedn_rl_norm_set_stats(pedn_sim* s, const double* mean, const double* var, const double* count, const double* ret_stats) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->norm_on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
-  HIP_TRY(s, hipSetDevice(s->device));
-  join_forked(s);
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  const int O = s->nv.O;
-  std::vector<double> h((size_t)3 * O + 3);
-  HIP_TRY(s, hipMemcpy(h.data(), s->nv.mean, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  if (mean) memcpy(h.data(), mean, (size_t)O * sizeof(double));
-  if (var) memcpy(h.data() + O, var, (size_t)O * sizeof(double));
-  if (count)
-    for (int c = 0; c < O; ++c) h[(size_t)2 * O + c] = count[s->h_norm_agent[c]];
-  if (ret_stats) memcpy(h.data() + (size_t)3 * O, ret_stats, 3 * sizeof(double));
-  HIP_TRY(s, hipMemcpy(s->nv.mean, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  return PEDN_OK;
-}
-
-void* pedn_rl_norm_device_ptr(pedn_sim* s, int32_t which) {
-  if (!s || !s->norm_on) return nullptr;
-  const NormView& n = s->nv;
-  switch (which) {
-    case 0: return n.obs_n;
-    case 1: return n.rew_n;
-    case 2: return n.mean;
-    case 3: return n.var;
-    case 4: return n.count;
-    case 5: return n.ret;
-    case 6: return n.ret_stats;
-  }
-  return nullptr;
-}
-
-// ---- rollout store and advantage estimates on the device (pedn_rollout.hpp) ----------------------------------------
-static void rollout_drop(pedn_sim* s) {
-  for (void* p : s->ro_allocs) hipFree(p);
-  s->ro_allocs.clear();
-  memset(&s->ro, 0, sizeof s->ro);
-  s->ro_on = s->ro_begun = s->ro_finished = false;
-  s->ro_rows = 0;
-}
-
-// the rows a record launch copies are the ones the fetches hand out
-static void rollout_sources(pedn_sim* s) {
-  if (!s->ro_on) return;
-  s->ro.obs_src = s->norm_on ? s->nv.obs_n : s->rl.obs;
-  s->ro.rew_src = s->norm_on ? s->nv.rew_n : s->rl.rew;
-}
-
-static unsigned rollout_blocks(size_t elems) { return (unsigned)std::min<size_t>(std::max<size_t>((elems + 1023) / 1024, 1), 2048); }
-
-int pedn_rollout_free(pedn_sim* s) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  HIP_TRY(s, hipSetDevice(s->device));
-  pending_links_first(s);   // (ends a clocked section: a captured record launch is not replayed over freed rows, pedn_rl_clock_signature)
-  HIP_TRY(s, hipDeviceSynchronize());
-  rollout_drop(s);
-  return PEDN_OK;
-}
-
-int pedn_rollout_configure(pedn_sim* s, int32_t capacity, int32_t store_obs) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
-  if (capacity < 1) return fail(s, PEDN_E_ARG, "capacity < 1");
-  int rc = pedn_rollout_free(s);
-  if (rc != PEDN_OK) return rc;
-  const RlView& q = s->rl;
-  const size_t N = (size_t)s->v.R, cap = (size_t)capacity, nv = N * q.n_agents;
-  if (nv > 0x7fffffffull) return fail(s, PEDN_E_ARG, "more than 2^31 trajectories");   // (a lane index is an int; rows are addressed in 64 bits)
-  RolloutView r;
-  memset(&r, 0, sizeof r);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
-  auto take = [&](size_t bytes, void** out) -> int {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) return fail(s, PEDN_E_NOMEM, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-    s->ro_allocs.push_back(p);
-    const hipError_t z = hipMemset(p, 0, std::max<size_t>(bytes, 16));
-    if (z != hipSuccess) return fail(s, PEDN_E_DEVICE, std::string("hipMemset: ") + hipGetErrorString(z));
-    *out = p;
-    return PEDN_OK;
-  };
-  if ((rc = take(cap * N * q.A * sizeof(double), (void**)&r.actions)) != PEDN_OK || (rc = take((cap + 1) * nv * sizeof(float), (void**)&r.values)) != PEDN_OK ||
-      (rc = take(cap * nv * sizeof(float), (void**)&r.rewards)) != PEDN_OK || (rc = take(cap * N * sizeof(float), (void**)&r.done)) != PEDN_OK ||
-      (rc = take(cap * nv * sizeof(float), (void**)&r.td_target)) != PEDN_OK || (rc = take(cap * nv * sizeof(float), (void**)&r.adv)) != PEDN_OK ||
-      (rc = take(cap * nv * sizeof(float), (void**)&r.adv_n)) != PEDN_OK || (rc = take(2 * cap * q.n_agents * sizeof(double), (void**)&r.rowsum)) != PEDN_OK ||
-      (rc = take(4 * sizeof(int32_t), (void**)&r.state)) != PEDN_OK ||
-      (store_obs && (rc = take((cap + 1) * N * q.O * sizeof(float), (void**)&r.obs)) != PEDN_OK)) {
-    const std::string keep = s->err;
-    rollout_drop(s);
-    return fail(s, rc, keep);
-  }
-  r.clock = s->d_clock;
-  r.cap = capacity; r.N = s->v.R; r.A = q.n_agents; r.n_actions = q.A; r.n_obs = q.O; r.T = s->v.T1 - 1;
-  s->ro = r;
-  s->ro_on = true;
-  rollout_sources(s);
-  return PEDN_OK;
-}
-
-int pedn_rollout_begin(pedn_sim* s) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->ro_on) return fail(s, PEDN_E_ARG, "pedn_rollout_configure has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  pending_links_first(s);   // (ends a clocked section: the cursor goes back behind everything recorded so far)
-  const RolloutView& r = s->ro;
-  hipLaunchKernelGGL(rollout_begin_kernel, dim3(rollout_blocks(r.obs ? (size_t)r.N * r.n_obs : 1)), dim3(256), 0, s->stream, r);
-  HIP_TRY(s, hipGetLastError());
-  s->ro_begun = true;
-  s->ro_finished = false;
-  s->ro_rows = 0;
-  return PEDN_OK;
-}
-
-// (no allocation, no synchronisation, no event query: safe under stream capture)
-int pedn_rollout_record(pedn_sim* s, const double* actions, const float* values, int32_t term, void* stream) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->ro_on || !s->ro_begun) return fail(s, PEDN_E_ARG, "pedn_rollout_begin has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  const RolloutView& r = s->ro;
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  const size_t widest = (size_t)r.N * std::max(std::max(r.obs ? r.n_obs : 0, 2 * r.n_actions), r.A);
-  hipLaunchKernelGGL(rollout_record_kernel, dim3(rollout_blocks(widest)), dim3(256), 0, st, r, actions, values, s->clocked ? -1 : (term ? 1 : 0));
-  HIP_TRY(s, hipGetLastError());
-  s->ro_finished = false;
-  return PEDN_OK;
-}
-
-int pedn_rollout_finish(pedn_sim* s, const float* last_values, int32_t* rows, int32_t* overflow) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->ro_on || !s->ro_begun) return fail(s, PEDN_E_ARG, "pedn_rollout_begin has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  join_forked(s);   // (ends a clocked section)
-  HIP_TRY(s, hipDeviceSynchronize());   // records may sit on a caller's stream
-  const RolloutView& r = s->ro;
-  int32_t h[4] = {0, 0, 0, 0};
-  HIP_TRY(s, hipMemcpy(h, r.state, sizeof h, hipMemcpyDeviceToHost));
-  const int n = std::min(h[0], r.cap);
-  const size_t nv = (size_t)r.N * r.A;
-  if (last_values) HIP_TRY(s, hipMemcpy(r.values + (size_t)n * nv, last_values, nv * sizeof(float), hipMemcpyDeviceToDevice));
-  else HIP_TRY(s, hipMemset(r.values + (size_t)n * nv, 0, nv * sizeof(float)));
-  HIP_TRY(s, hipDeviceSynchronize());
-  s->ro_rows = n;
-  s->ro_finished = true;
-  if (rows) *rows = n;
-  if (overflow) *overflow = h[2];
-  return PEDN_OK;
-}
-
-static void gae_launch(const float* rew, const float* val, const float* done, int T, int lanes, int done_div, double gamma, double lmbda,
-                       float* td, float* adv, hipStream_t st) {
-  const float g = (float)gamma, c = (float)(gamma * lmbda);   // (the product in binary64, rounded once)
-  const dim3 grid((unsigned)((lanes + 255) / 256));
-  if (val) hipLaunchKernelGGL(rollout_gae_kernel<false>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
-  else hipLaunchKernelGGL(rollout_gae_kernel<true>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
-}
-
-int pedn_rollout_compute(pedn_sim* s, double gamma, double lmbda, int32_t normalize) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->ro_on || !s->ro_finished) return fail(s, PEDN_E_ARG, "pedn_rollout_finish has not been called");
-  const RolloutView& r = s->ro;
-  const int T = s->ro_rows;
-  if (T < 1) return fail(s, PEDN_E_ARG, "the store is empty");
-  if (normalize && (int64_t)T * r.N < 2) return fail(s, PEDN_E_ARG, "advantage normalisation needs at least two entries per agent");
-  HIP_TRY(s, hipSetDevice(s->device));
-  gae_launch(r.rewards, r.values, r.done, T, r.N * r.A, r.A, gamma, lmbda, r.td_target, r.adv, s->stream);
-  if (normalize) {
-    const dim3 grid((unsigned)((r.A + PEDN_NORM_COLS - 1) / PEDN_NORM_COLS), (unsigned)T);
-    for (int pass = 0; pass < 3; ++pass)   // (a launch per pass: each needs every workgroup's row sums of the one before)
-      hipLaunchKernelGGL(rollout_advnorm_kernel, grid, dim3(1024), 0, s->stream, r.adv, r.adv_n, r.rowsum, T, r.N, r.A, pass);
-  }
-  HIP_TRY(s, hipGetLastError());
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  return PEDN_OK;
-}
-
-void* pedn_rollout_device_ptr(pedn_sim* s, int32_t which) {
-  if (!s || !s->ro_on) return nullptr;
-  const RolloutView& r = s->ro;
-  switch (which) {
-    case 0: return r.actions;
-    case 1: return r.values;
-    case 2: return r.rewards;
-    case 3: return r.done;
-    case 4: return r.obs;
-    case 5: return r.td_target;
-    case 6: return r.adv;
-    case 7: return r.adv_n;
-    case 8: return r.state;
-  }
-  return nullptr;
-}
-
-int pedn_gae(const float* rewards, const float* values, const float* dones, int32_t T, int32_t lanes, double gamma, double lmbda,
-             float* td_target, float* adv, void* stream) {
-  if (!rewards || !adv || (values && (!dones || !td_target))) return fail(nullptr, PEDN_E_ARG, "null argument");
-  if (T < 1 || lanes < 1) return fail(nullptr, PEDN_E_ARG, "T and lanes must be positive");
-  gae_launch(rewards, values, dones, T, lanes, 1, gamma, lmbda, td_target, adv, (hipStream_t)stream);
-  HIP_TRY(nullptr, hipGetLastError());
-  return PEDN_OK;
-}
-
-// ---- the reference's stacked actors for all envs and agents in one launch (pedn_actor.hpp) ----------------------------
-int pedn_actor_forward(const float* stack, const int32_t* table, const float* low, const float* high, const float* params,
-                       const float* noise, float* mu, float* std, float* eps, float* raw, double* actions, int64_t* state,
-                       int32_t n_envs, int32_t stack_size, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size,
-                       int32_t kind, int32_t delta_actions, int32_t mode, double max_delta, double min_std, double max_std, uint64_t seed,
-                       uint32_t replica_offset, void* stream) {
-  if (!stack || !table || !low || !high || !params || !mu || !std || !eps || !raw || !actions || !state)
-    return fail(nullptr, PEDN_E_ARG, "null argument");
-  if (hidden_size != PEDN_ACTOR_HIDDEN) return fail(nullptr, PEDN_E_ARG, "the actor kernel is built for hidden_size 64");
-  if (n_envs < 1 || stack_size < 1 || n_obs < 1 || n_actions < 1 || n_agents < 1 || n_agents > 65535)
-    return fail(nullptr, PEDN_E_ARG, "n_envs, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)");
-  if (kind < 0 || kind > 1 || mode < 0 || mode > 2) return fail(nullptr, PEDN_E_ARG, "kind is 0 (SAC) or 1 (PPO), mode 0, 1 or 2");
-  if (mode == 1 && !noise) return fail(nullptr, PEDN_E_ARG, "mode 1 needs the noise");
-  ActorArgs a{};
-  a.stack = stack; a.table = table; a.low = low; a.high = high; a.params = params; a.noise = noise;
-  a.mu = mu; a.std = std; a.eps = eps; a.raw = raw; a.actions = actions; a.state = state;
-  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
-  a.replica_offset = replica_offset;
-  a.n_envs = n_envs; a.S = stack_size; a.n_obs = n_obs; a.n_actions = n_actions;
-  a.kind = kind; a.delta = delta_actions != 0; a.mode = mode;
-  a.max_delta = (float)max_delta; a.min_std = (float)min_std; a.max_std = (float)max_std;
-  const dim3 grid((unsigned)((n_envs + PEDN_ACTOR_TILE - 1) / PEDN_ACTOR_TILE), (unsigned)n_agents);
-  hipLaunchKernelGGL(actor_forward_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-  HIP_TRY(nullptr, hipGetLastError());
-  return PEDN_OK;
-}
-
-// ---- SAC TD targets and Polyak updates of all agents (pedn_sac.hpp) ---------------------------------------------------
-int pedn_sac_td_target(const float* next_states, const float* rewards, const float* dones, const int32_t* table, const int32_t* critic_table,
-                       const float* actor_params, const float* target_params, const float* log_alpha, const float* noise,
-                       float* out_actions, float* out_agents, int64_t* state, int32_t batch, int32_t stack_size, int32_t n_obs,
-                       int32_t n_actions, int32_t n_agents, int32_t hidden_size, double max_delta, double gamma, uint64_t seed,
-                       void* stream) {
-  if (!next_states || !rewards || !dones || !table || !critic_table || !actor_params || !target_params || !log_alpha || !out_actions ||
-      !out_agents || !state)
-    return fail(nullptr, PEDN_E_ARG, "null argument");
-  if (hidden_size != PEDN_ACTOR_HIDDEN) return fail(nullptr, PEDN_E_ARG, "the SAC target kernel is built for hidden_size 64");
-  if (batch < 1 || stack_size < 1 || n_obs < 1 || n_actions < 1 || n_agents < 1 || n_agents > 65535)
-    return fail(nullptr, PEDN_E_ARG, "batch, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)");
-  SacTargetArgs a{};
-  a.ns = next_states; a.rewards = rewards; a.dones = dones; a.table = table; a.ctable = critic_table;
-  a.actor = actor_params; a.critic = target_params; a.log_alpha = log_alpha; a.noise = noise;
-  a.out_actions = out_actions; a.out_agents = out_agents; a.state = state;
-  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
-  a.B = batch; a.S = stack_size; a.n_obs = n_obs; a.n_actions = n_actions; a.n_agents = n_agents;
-  a.max_delta = (float)max_delta; a.gamma = (float)gamma;
-  const dim3 grid((unsigned)((batch + PEDN_SAC_TILE - 1) / PEDN_SAC_TILE), (unsigned)n_agents);
-  hipLaunchKernelGGL(sac_target_kernel, grid, dim3(192), 0, (hipStream_t)stream, a);
-  HIP_TRY(nullptr, hipGetLastError());
-  return PEDN_OK;
-}
-
-int pedn_sac_soft_update(float* target, const float* online, int64_t n_floats, double tau, void* stream) {
-  if (!target || !online) return fail(nullptr, PEDN_E_ARG, "null argument");
-  if (n_floats < 4 || n_floats % 4) return fail(nullptr, PEDN_E_ARG, "the packs' length must be a positive multiple of 4 floats");
-  if (((uintptr_t)target | (uintptr_t)online) & 15) return fail(nullptr, PEDN_E_ARG, "the packs must be 16-byte aligned");
-  if (!(tau >= 0.0 && tau <= 1.0)) return fail(nullptr, PEDN_E_ARG, "tau must be in [0, 1]");
-  const int64_t n4 = n_floats / 4;
-  const int64_t blocks = (n4 + 255) / 256;
-  hipLaunchKernelGGL(sac_polyak_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<float4*>(target), reinterpret_cast<const float4*>(online), n4, (float)(1.0 - tau), (float)tau);
-  HIP_TRY(nullptr, hipGetLastError());
-  return PEDN_OK;
-}
-
-// ---- replay store of the off-policy trainers on the device (pedn_replay.hpp) ----------------------------------------
-static void replay_drop(pedn_sim* s) {
-  for (void* p : s->rp_allocs) hipFree(p);
-  s->rp_allocs.clear();
-  memset(&s->rp, 0, sizeof s->rp);
-  s->rp_on = s->rp_begun = false;
-}
-
-// the rows a push launch copies are the ones the fetches hand out
-static void replay_sources(pedn_sim* s) {
-  if (!s->rp_on) return;
-  s->rp.obs_src = s->norm_on ? s->nv.obs_n : s->rl.obs;
-  s->rp.rew_src = s->norm_on ? s->nv.rew_n : s->rl.rew;
-}
-
-int pedn_replay_free(pedn_sim* s) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  HIP_TRY(s, hipSetDevice(s->device));
-  pending_links_first(s);   // (ends a clocked section: a captured push launch is not replayed over freed rows, pedn_rl_clock_signature)
-  HIP_TRY(s, hipDeviceSynchronize());
-  replay_drop(s);
-  return PEDN_OK;
-}
-
-int pedn_replay_configure(pedn_sim* s, int64_t capacity, int32_t stack_size, int32_t episode_steps, uint64_t seed) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
-  if (capacity < 1) return fail(s, PEDN_E_ARG, "capacity < 1");
-  if (stack_size < 1) return fail(s, PEDN_E_ARG, "stack_size < 1");
-  if (episode_steps < 1) return fail(s, PEDN_E_ARG, "episode_steps < 1");
-  if (capacity > (int64_t)1 << 40) return fail(s, PEDN_E_ARG, "capacity too large");
-  if ((int64_t)s->v.R * stack_size * s->rl.O > 0x7fffffff) return fail(s, PEDN_E_ARG, "more than 2^31 entries in the stacked observation");
-  int rc = pedn_replay_free(s);
-  if (rc != PEDN_OK) return rc;
-  const RlView& q = s->rl;
-  ReplayView r;
-  memset(&r, 0, sizeof r);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
-  r.cap = capacity;
-  r.R = capacity + stack_size + (capacity + episode_steps - 1) / episode_steps + 1;
-  const size_t N = (size_t)s->v.R, R = (size_t)r.R;
-  auto take = [&](size_t bytes, void** out) -> int {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) return fail(s, PEDN_E_NOMEM, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-    s->rp_allocs.push_back(p);
-    const hipError_t z = hipMemset(p, 0, std::max<size_t>(bytes, 16));
-    if (z != hipSuccess) return fail(s, PEDN_E_DEVICE, std::string("hipMemset: ") + hipGetErrorString(z));
-    *out = p;
-    return PEDN_OK;
-  };
-  if ((rc = take(R * N * q.O * sizeof(float), (void**)&r.frames)) != PEDN_OK || (rc = take(R * N * q.A * sizeof(double), (void**)&r.actions)) != PEDN_OK ||
-      (rc = take(R * N * q.n_agents * sizeof(float), (void**)&r.rewards)) != PEDN_OK || (rc = take(R * sizeof(float), (void**)&r.done)) != PEDN_OK ||
-      (rc = take(N * stack_size * q.O * sizeof(float), (void**)&r.stacked)) != PEDN_OK || (rc = take(R * sizeof(int64_t), (void**)&r.first)) != PEDN_OK ||
-      (rc = take((size_t)capacity * sizeof(int64_t), (void**)&r.step_serial)) != PEDN_OK || (rc = take(16 * sizeof(int64_t), (void**)&r.state)) != PEDN_OK) {
-    const std::string keep = s->err;
-    replay_drop(s);
-    return fail(s, rc, keep);
-  }
-  const int64_t no_episode = -1;
-  HIP_TRY(s, hipMemcpy(r.state + 3, &no_episode, sizeof no_episode, hipMemcpyHostToDevice));
-  r.clock = s->d_clock;
-  r.k0 = (uint32_t)(seed & 0xffffffffu); r.k1 = (uint32_t)(seed >> 32);
-  r.N = s->v.R; r.A = q.n_agents; r.n_actions = q.A; r.n_obs = q.O; r.stack = stack_size; r.T = s->v.T1 - 1;
-  s->rp = r;
-  s->rp_on = true;
-  replay_sources(s);
-  return PEDN_OK;
-}
-
-// both roles of replay_push_kernel get the same number of workgroups: a lane takes about four 16-byte accesses of the wider role (few
-// workgroups: every one of them takes a ticket from one counter)
-static dim3 replay_push_grid(const ReplayView& r) {
-  const size_t row = (size_t)r.N * std::max(std::max(r.n_obs, 2 * r.n_actions), r.A) / 4 + 1;
-  const size_t stack = (size_t)r.N * r.stack * r.n_obs / ((r.n_obs & 3) ? 1 : 4);
-  return dim3((unsigned)std::min<size_t>((std::max(row, stack) + 1023) / 1024, 512), 2);
-}
-
-int pedn_replay_begin(pedn_sim* s) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->rp_on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  pending_links_first(s);   // (ends a clocked section: the RESET row takes the observation the eager reset left)
-  hipLaunchKernelGGL(replay_push_kernel, replay_push_grid(s->rp), dim3(256), 0, s->stream, s->rp, (const double*)nullptr, 1, 0);
-  HIP_TRY(s, hipGetLastError());
-  s->rp_begun = true;
-  return PEDN_OK;
-}
-
-// (no allocation, no synchronisation, no event query: safe under stream capture)
-int pedn_replay_push(pedn_sim* s, const double* actions, int32_t term, void* stream) {
-  if (!s || !actions) return fail(s, PEDN_E_ARG, "null argument");
-  if (!s->rp_on || !s->rp_begun) return fail(s, PEDN_E_ARG, "pedn_replay_begin has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  hipLaunchKernelGGL(replay_push_kernel, replay_push_grid(s->rp), dim3(256), 0, st, s->rp, actions, 0, s->clocked ? -1 : (term ? 1 : 0));
-  HIP_TRY(s, hipGetLastError());
-  return PEDN_OK;
-}
-
-// (the same: safe under stream capture)
-int pedn_replay_sample(pedn_sim* s, int64_t batch, const int64_t* indices, int32_t obs0, int32_t obs_w, int32_t act0, int32_t act_w,
-                       int32_t rew0, int32_t rew_w, float* states, double* actions, float* rewards, float* next_states, float* dones,
-                       int64_t* idx, void* stream) {
-  if (!s || !states || !actions || !rewards || !next_states || !dones) return fail(s, PEDN_E_ARG, "null argument");
-  if (!s->rp_on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
-  const ReplayView& r = s->rp;
-  if (batch < 1 || batch > 0x7fffffffll) return fail(s, PEDN_E_ARG, "batch size out of range");
-  if (obs0 < 0 || obs_w < 1 || obs0 + obs_w > r.n_obs || act0 < 0 || act_w < 1 || act0 + act_w > r.n_actions || rew0 < 0 || rew_w < 1 ||
-      rew0 + rew_w > r.A)
-    return fail(s, PEDN_E_ARG, "column range outside the row");
-  HIP_TRY(s, hipSetDevice(s->device));
-  ReplayOut o;
-  memset(&o, 0, sizeof o);
-  o.states = states; o.next_states = next_states; o.rewards = rewards; o.dones = dones; o.actions = actions; o.idx = idx;
-  o.obs0 = obs0; o.obs_w = obs_w; o.act0 = act0; o.act_w = act_w; o.rew0 = rew0; o.rew_w = rew_w;
-  const int64_t groups = (batch + PEDN_REPLAY_GROUP - 1) / PEDN_REPLAY_GROUP;
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  hipLaunchKernelGGL(replay_sample_kernel, dim3((unsigned)groups), dim3(256), 0, st, r, o, indices, (uint32_t)batch);
-  HIP_TRY(s, hipGetLastError());
-  return PEDN_OK;
-}
-
-int pedn_replay_size(pedn_sim* s, int64_t* state) {
-  if (!s || !state) return fail(s, PEDN_E_ARG, "null argument");
-  if (!s->rp_on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  HIP_TRY(s, hipDeviceSynchronize());   // pushes and samples may sit on a caller's stream
-  HIP_TRY(s, hipMemcpy(state, s->rp.state, 6 * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (state[5]) HIP_TRY(s, hipMemset(s->rp.state + 5, 0, sizeof(int64_t)));   // reported once
-  return PEDN_OK;
-}
-
-void* pedn_replay_device_ptr(pedn_sim* s, int32_t which) {
-  if (!s || !s->rp_on) return nullptr;
-  const ReplayView& r = s->rp;
-  switch (which) {
-    case 0: return r.frames;
-    case 1: return r.actions;
-    case 2: return r.rewards;
-    case 3: return r.done;
-    case 4: return r.first;
-    case 5: return r.step_serial;
-    case 6: return r.stacked;
-    case 7: return r.state;
-  }
-  return nullptr;
-}
-
-// ---- rule-based controllers on the device (pedn_ctrl.hpp) ----------------------------------------------------------------------
-int pedn_ctrl_configure(pedn_sim* s, const int32_t* kind, const int32_t* window, const int32_t* wide, const float* threshold,
-                        const double* width, const float* open) {
-  if (!s || !kind || !window || !wide || !threshold || !width || !open) return fail(s, PEDN_E_ARG, "null argument");
-  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
-  if (s->norm_on) return fail(s, PEDN_E_ARG, "controllers and the running normalisation cannot be combined: switch the normalisation off first");
-  HIP_TRY(s, hipSetDevice(s->device));
-  pending_links_first(s);
-  const RlView& q = s->rl;
-  std::vector<int32_t> type((size_t)q.n_agents);
-  HIP_TRY(s, hipMemcpy(type.data(), q.agent_type, type.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  std::vector<CtrlAgent> ag((size_t)q.n_agents);
-  int rows = 0;
-  bool any = false;
-  for (int a = 0; a < q.n_agents; ++a) {
-    CtrlAgent& c = ag[a];
-    c.kind = kind[a];
-    if (c.kind < 0 || c.kind > 2) return fail(s, PEDN_E_ARG, "controller kind must be 0 (none), 1 (gater rule) or 2 (separator rule)");
-    if (c.kind == 1 && type[a] != 1) return fail(s, PEDN_E_ARG, "agent " + std::to_string(a) + " is not a gater");
-    if (c.kind == 1 && q.obs_mode != 2) return fail(s, PEDN_E_ARG, "the gater rule reads densities: obs_mode must be option2");
-    if (c.kind == 2 && type[a] != 0) return fail(s, PEDN_E_ARG, "agent " + std::to_string(a) + " is not a separator");
-    c.window = c.kind == 2 ? window[a] : 0;
-    if (c.window < 0 || c.window > PEDN_CTRL_MAX_WINDOW)
-      return fail(s, PEDN_E_ARG, "moving-average window outside 0.." + std::to_string(PEDN_CTRL_MAX_WINDOW));
-    c.wide = wide[a] != 0;
-    c.ring = rows;
-    rows += c.window;
-    c.thr = threshold[a];
-    c.w64 = width[a];
-    c.w32 = (float)width[a];
-    any = any || c.kind != 0;
-  }
-  const DevView& v = s->v;
-  CtrlView& cv = s->ctrl;
-  int rc;
-  // (sizes depend only on the agent set: allocated once per pedn_rl_configure, the moving-average rows grow when a call needs more)
-  static_assert(sizeof(CtrlAgent) == 32, "CtrlAgent is uploaded as bytes");
-  if (!cv.actions || s->ctrl_ready == false) {
-    CtrlAgent* d_ag;
-    float* d_open;
-    if ((rc = dalloc(s, (size_t)q.n_agents, &d_ag)) != PEDN_OK) return rc;
-    if ((rc = dalloc(s, (size_t)q.A, &d_open)) != PEDN_OK) return rc;
-    if ((rc = dalloc(s, (size_t)v.R * q.A, &cv.actions)) != PEDN_OK) return rc;
-    if ((rc = dalloc(s, (size_t)v.R * q.n_agents, &cv.ep)) != PEDN_OK) return rc;
-    if ((rc = dalloc(s, (size_t)q.n_agents * v.RS, &cv.count)) != PEDN_OK) return rc;
-    cv.agent = d_ag;
-    cv.open = d_open;
-    cv.ring = nullptr;
-    s->ctrl_rows = 0;
-  }
-  if (rows > s->ctrl_rows) {
-    if ((rc = dalloc(s, (size_t)rows * v.RS, &cv.ring)) != PEDN_OK) return rc;
-    s->ctrl_rows = rows;
-  }
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  HIP_TRY(s, hipMemcpy(const_cast<CtrlAgent*>(cv.agent), ag.data(), ag.size() * sizeof(CtrlAgent), hipMemcpyHostToDevice));
-  HIP_TRY(s, hipMemcpy(const_cast<float*>(cv.open), open, (size_t)q.A * sizeof(float), hipMemcpyHostToDevice));
-  std::vector<double> nan((size_t)v.R * q.A, __builtin_nan(""));   // no action until the first observation decides one
-  HIP_TRY(s, hipMemcpy(cv.actions, nan.data(), nan.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(s, hipMemset(cv.ep, 0, (size_t)v.R * q.n_agents * sizeof(float)));
-  HIP_TRY(s, hipMemset(cv.count, 0, (size_t)q.n_agents * v.RS * sizeof(int32_t)));   // every moving-average buffer empty
-  cv.RS = v.RS;
-  cv.ep_mode = 1;
-  s->ctrl_ready = true;
-  s->ctrl_any = any;
-  return PEDN_OK;
-}
-
-int pedn_ctrl_observe(pedn_sim* s, int32_t t) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->ctrl_ready) return fail(s, PEDN_E_ARG, "pedn_ctrl_configure has not been called");
-  CtrlView cv = s->ctrl;
-  cv.ep_mode = 2;
-  return rl_observe(s, t, 0, nullptr, nullptr, &cv);
-}
-
-int pedn_ctrl_step(pedn_sim* s, int32_t t, int32_t action_gap, int32_t n_steps) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->ctrl_ready) return fail(s, PEDN_E_ARG, "pedn_ctrl_configure has not been called");
-  if (n_steps < 0 || action_gap < 1 || t < 1 || t + (int64_t)n_steps * action_gap - 1 > s->v.T1 - 1)
-    return fail(s, PEDN_E_ARG, "step range outside 1..T");
-  CtrlView cv = s->ctrl;
-  cv.ep_mode = 1;
-  for (int i = 0; i < n_steps; ++i) {
-    const int rc = rl_step(s, s->ctrl_any ? s->ctrl.actions : nullptr, 1, t + i * action_gap, action_gap, nullptr, nullptr, &cv);
-    if (rc != PEDN_OK) return rc;
-  }
-  return PEDN_OK;
-}
-
-int pedn_ctrl_read(pedn_sim* s, double* actions, float* episode_rewards) {
-  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  if (!s->ctrl_ready) return fail(s, PEDN_E_ARG, "pedn_ctrl_configure has not been called");
-  HIP_TRY(s, hipSetDevice(s->device));
-  join_forked(s);
-  const size_t R = (size_t)s->v.R;
-  if (actions) HIP_TRY(s, hipMemcpyAsync(actions, s->ctrl.actions, R * s->rl.A * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  if (episode_rewards)
-    HIP_TRY(s, hipMemcpyAsync(episode_rewards, s->ctrl.ep, R * s->rl.n_agents * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  return PEDN_OK;
-}
-
-void* pedn_ctrl_device_ptr(pedn_sim* s, int32_t which) {
-  if (!s || !s->ctrl_ready) return nullptr;
-  return which == 0 ? (void*)s->ctrl.actions : which == 1 ? (void*)s->ctrl.ep : nullptr;
 }
 
 int pedn_device_math(int32_t device, int32_t op, int32_t n, const double* a, const double* b, uint64_t seed, double* out) {
@@ -3325,8 +2442,6 @@ int pedn_device_math(int32_t device, int32_t op, int32_t n, const double* a, con
   HIP_TRY(nullptr, hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   return PEDN_OK;
 }
-
-}  // extern "C"
 
 #ifdef PEDN_PHASE_PROFILE
 // profiling build only (make phase-profile): read (zero = 0) or clear (zero = 1) the 16 phase accumulators of node_kernel
@@ -3370,5 +2485,3 @@ extern "C" int pedn_debug_phases(unsigned long long* out, int zero) {
   return 0;
 }
 #endif
-
-#include "pedn_metrics.hpp"

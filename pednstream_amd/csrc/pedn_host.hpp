@@ -1,0 +1,296 @@
+// pedn_host.hpp -- the engine's handle (pedn_sim) and the host helpers that the core (pedn_hip.hip) and the host sections of the subsystem
+// headers share: error reporting, device allocations, host <-> device staging, and the declarations of the core services a subsystem may
+// call.  Included by pedn_hip.hip behind pedn_kernels.hpp and in front of the subsystem headers.
+#pragma once
+#include <hip/hip_ext.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "pedn_kernels.hpp"
+
+static thread_local std::string g_last_error;
+
+struct pedn_sim;
+// Device allocations with an owner of their own (a store that is freed while the engine lives on); what lives as long as the engine goes
+// into pedn_sim::allocs (upload / dalloc).
+namespace {   // (internal to the library's one translation unit, like the static helpers)
+struct DevicePool : std::vector<void*> {
+  int take(pedn_sim* s, size_t bytes, void** out);   // hipMalloc + hipMemset to 0 of max(bytes, 16), registered here
+  void drop();                                       // hipFree of everything taken
+};
+}  // namespace
+
+// Per-subsystem state of the handle: the view the subsystem's launches carry by value (zeroed while there is none; hashed as bytes by
+// pedn_rl_clock_signature) and the host's flags.
+// rule-based controllers (pedn_ctrl.hpp); any: some agent has a controller (else a controlled step applies no actions at all), rows: the
+// moving-average rows allocated in view.ring
+struct CtrlState { CtrlView view{}; bool ready = false, any = false; int rows = 0; };
+// running normalisation (pedn_norm.hpp): its buffers belong to the agent set (pedn_sim::allocs); [O] tracked mask, agent of every column
+struct NormState { NormView view = {}; bool on = false, alloc = false; std::vector<int32_t> tracked, agent; };
+// rollout store (pedn_rollout.hpp) and replay store (pedn_replay.hpp), each with its own allocations; the two may live side by side
+struct RolloutState { RolloutView view = {}; bool on = false, begun = false, finished = false; int rows = 0; DevicePool mem; };
+struct ReplayState { ReplayView view = {}; bool on = false, begun = false; DevicePool mem; };
+
+struct pedn_sim {
+  DevView v{};
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int device = 0;
+  int n_nodes = 0, n_turns = 0, n_demand = 0, n_od = 0, n_blocks = 0, n_ent = 0;
+  int link_owner = 0;  // pedn_run: node_kernel(t + 1)'s slot waves perform the link update of t (one launch per step), PEDN_LINK_OWNER
+  int packed_by = 1;   // how nodes were binned into node_kernel's blocks: 0 by degree, 1 by the static load estimate, 2 by measured cost
+  // Single-launch plan of small batches with dynamic turning fractions (inline_tf): every device-computed row is short enough for ONE
+  // wave and its probabilities fit PEDN_TF_INL_ROWS LDS rows (inline_tf_ok), and the whole node_kernel grid is one generation at 4 waves
+  // per SIMD: the slot waves of node_kernel<LU, TF> compute their own rows, a step is one launch.
+  bool inline_tf_ok = false;
+  int inline_tf = 0;
+  int inline_help = 0;      // ... with helper waves: node_kernel_h, sixteen waves per workgroup (PEDN_INLINE_TF=2)
+  // A caller that looks at the state after EVERY step (a controller reading densities, an output handler) makes every pending link
+  // update a launch of its own and every next step start from stand-alone turning fractions: three launches per step where the plain plan
+  // has two.  pedn_step notices (touched: something settled the pending state since the last step) and steps such a caller under the
+  // plain plan until two steps in a row go untouched (nine_intersections, step + two reads: 76.0 -> 71 us per step).
+  int touched = 0, touch_streak = 0;
+  int step_streak = 0;   // consecutive pedn_step(t), pedn_step(t + 1), ... calls with nothing looking at the state in between (see pedn_step)
+  size_t node_lds_tf = 0;   // dynamic LDS of node_kernel<.., TF>
+  std::vector<int32_t> h_slot_trow;
+  int rl_chains = 0;   // pedn_rl_step steps the two halves of the envs as two chains that stay forked ACROSS calls (PEDN_RL_CHAINS)
+  int forked = 0;      // stream2 holds work of such a chain that the engine's stream does not order yet (join_forked)
+  // Device-resident step clock (DevView.clock; pedn_rl_clock_begin .. pedn_rl_clock_end): while `clocked`, env steps are enqueued with
+  // constant arguments (pedn_rl_step_clocked) and the host does not know the step the device is at -- every other entry point that
+  // steps, reads or changes state first ends the clocked section (clock_end: synchronises and takes the bookkeeping back).
+  int32_t* d_clock = nullptr;
+  bool clocked = false;
+  int clock_t0 = 0;   // step the clock was set to by pedn_rl_clock_begin
+  int valid_hi = 0x7fffffff;   // lazy reset: history rows above this index are neither written nor cleared (DevView.valid_hi)
+  int link_pending = -1;  // owner-wave plan: step whose link update has not been performed yet, -1 none
+  // Quiet corridors (DevView.quiet): node_kernel<LU> launches store the words (PEDN_QUIET=0|1, default wherever link_owner is chosen);
+  // quiet_valid = the step whose words every replica group has, from a node_kernel<LU> launch on each chain with no change of a history
+  // row since -- the next LU launch may use them; -1 none.  Cleared by everything that could break that (no_quiet).
+  int quiet = 0;
+  int quiet_valid = -1;
+  int quiet_lean = 1;   // PEDN_QUIET_LEAN=0|1 (default on): those launches skip the node work that all-zero flows fix (DevView.quiet_lean)
+  uint32_t* d_quiet = nullptr;
+  // Zero elision (DevView.zg64 / zg32; PEDN_ZERO_ELIDE=0|1, default on): zhw64 = the highest row of inflow / outflow / cumulative_inflow /
+  // cumulative_outflow, zhw32 = of num_pedestrians / density / link_flow, that may hold anything but +0.0 -- -1 after a full reset (which
+  // leaves every row at +0.0), kept by the lazy reset (the old episode's rows stay), INT_MAX when something the host does not follow may write them
+  // (a zero-copy pointer, the clocked steps) until the next full reset.  A launch that writes row x of a group gets the gate iff
+  // x > the group's mark; the mark is raised to x once the step is enqueued (both chains of a step decide from the marks before it).
+  // Only zeros are ever written below the marks' back (clear_rows, catch_up), so they need not raise them.
+  int zero_elide = 1;
+  int zhw64 = 0x7fffffff, zhw32 = 0x7fffffff;
+  int zgated = 0;   // node-kernel launches with a gate open since the last reset of either kind (pedn_plan_info info[7])
+  int fuse_obs = 1;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
+  // (The link update as a launch of its own runs one replica per lane -- link_kernel_1r: 42-47 VGPRs, 8 waves per SIMD; melbourne x 1024
+  // 12.3-12.6 against 12.7-13.1 us with two replicas per lane, profiles/r03_link_kernel_variants.txt; inside link_turn_kernel, whose
+  // budget is set by the turning fractions, it keeps two replicas per lane: half the workgroups.)
+  int max_degree = 0;     // largest number of incident corridors of a node
+  size_t node_lds = 0;    // dynamic LDS bytes of node_kernel
+  hipStream_t stream2 = nullptr;   // second half of the replicas in pedn_run (two_streams)
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  int warmed_chains = 1;  // chains whose streams exist and were probed to overlap
+  int chains = 1;         // plan of pedn_run for long ranges: 1 or 2 chains of launches (two_streams = chains > 1)
+  int run_chains = 1;     // chains of the range being launched (launch_step / flush_links: the last chain does the bookkeeping)
+  int stream_probe_attempts = 0;   // warm_chain_streams: probes run until the chains' streams were seen to overlap
+  float stream_probe_ms = 0.0f;
+  int two_streams = 0;    // pedn_run launches the two halves of the batch on two streams (replicas are independent)
+  int second_launch = 0;  // launch_step: a launch followed node_kernel
+  int fuse_tp = 0;     // the link update and the next step's turn probabilities share one launch (launch_step)
+  int tp_ran = 0;      // launch_step launched the stand-alone turn_frac_kernel (pedn_profile_step)
+  int tp_ready = -1;   // step whose turning fractions are in tfd[step & 1] (written by link_turn_kernel of the step before), -1: none
+  std::vector<int32_t> node_turn_ptr, node_demand_row;
+  std::vector<int32_t> h_up_od_ptr, h_upod_od, h_pair_upod;  // route-choice tables needed to re-tabulate P(od | up)
+  std::vector<double> h_od_w;
+  std::vector<int32_t> h_turn_pair_ptr, h_pair_const, h_turn_mode;
+  double* d_pair_pod = nullptr;
+  double* d_turn_tab = nullptr;
+  RlView rl{};
+  // rule-based controllers (pedn_ctrl_*, pedn_ctrl.hpp): device rows of next actions and episode sums, moving-average buffers
+  CtrlState ctrl;
+  bool rl_ready = false;
+  bool node_lp = false;   // PEDN_NODE_OPTIMAL: the node LP instead of the classic rule
+  bool rl_fold = false;   // gater-only agent set: pedn_rl_step lets node_kernel apply the actions (no launch of rl_apply_kernel)
+  std::vector<SlotRec> h_slot_rec;
+  SlotRec* d_slot_rec = nullptr;
+  std::vector<double> h_front_u, h_back_u, h_tf_u;
+  double *d_front_u = nullptr, *d_back_u = nullptr, *d_tf_u = nullptr;
+  std::vector<int32_t> h_node_dyn, h_slot_dyn;  // per node: dynamic; per slot: SlotRec.dyn (0 static, 1 turn_frac_kernel, 2 tabulated)
+  std::vector<int32_t> h_node_slot_ptr;
+  std::vector<double> h_ttab, h_ttab_r;         // host copies of turn_tab [T+1][n_turns] / turn_tab_r [n_turns][R] (tabulated rows: final values)
+  std::vector<char> h_rl_link;
+  LinkPR* d_prm = nullptr;           // per-replica link parameters [L][RS] (pedn_set_link_params, pedn_randomize_scenarios)
+  LinkPR* d_prm_draw = nullptr;      // recent-history mode: where pedn_randomize_scenarios draws before the result is accepted
+  double *d_pair_pod_r = nullptr, *d_turn_tab_r = nullptr;
+  // per-replica OD weights and the tables derived from them on the device (scenario_pod_tables)
+  double *d_od_w_r = nullptr, *d_pod_tot = nullptr;     // [n_od][RS], [n_up][RS]
+  const int32_t *d_up_od_ptr = nullptr, *d_upod_od = nullptr, *d_upod_up = nullptr, *d_pair_upod = nullptr, *d_turn_pair_ptr = nullptr,
+                *d_turn_mode = nullptr, *d_tab_rows = nullptr;
+  int n_tab_rows = 0, n_upod = 0;
+  bool pod_tables_uploaded = false, ttab_r_stale = false;   // h_ttab_r is older than turn_tab_r on the device
+  int* d_max_tau = nullptr;
+  int n_pair = 0, n_up = 0, n_over = 0;
+  int n_tf_heavy_quads = 0;  // leading workgroups of turn_frac_body with long chains (more than PEDN_TF_HEAVY_GROUPS softmax groups in a row)
+  long step_epoch = 1;  // counts launched steps; h_tf_set_epoch[node] == step_epoch: fractions imposed since the last step
+  std::vector<long> h_tf_set_epoch;
+  int rows64[7], rows32[6];  // history rows of every field (T+1, or the size of its ring in recent-history mode)
+  int last_t = -1;     // last step launched (pedn_get_turning_fractions: which buffer holds a dynamic node's fractions)
+  std::vector<void*> allocs;
+  // host <-> device staging: two slots used in turn, each a pinned host buffer + a device buffer + the event recorded behind
+  // the slot's last consumer, so that an upload neither waits for the stream nor borrows caller memory beyond the call
+  struct Stage { void* pin = nullptr; void* dev = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
+  Stage stage[2];
+  int stage_next = 0;
+  void* rl_pin = nullptr;      // pinned landing buffer of the RL step's observations + rewards (rl_fetch)
+  size_t rl_pin_bytes = 0;
+  std::string err;
+  struct MetricsState* metrics = nullptr;   // evaluation metrics (pedn_metrics.hpp)
+  NormState norm;
+  RolloutState ro;
+  ReplayState rp;
+};
+
+// the quiet words of the last step may not be used by the next launch (pedn_sim.quiet_valid)
+static inline void no_quiet(pedn_sim* s) { s->quiet_valid = -1; }
+
+// zero elision: may a launch that writes row `row` of a group whose mark is `hw` skip its +0.0 stores (pedn_sim.zhw64 / zhw32)?
+// (recent-history mode: ring rows are reused, never)
+static inline int32_t zero_gate(const pedn_sim* s, int hw, int row) { return s->zero_elide && !s->v.hist && row > hw ? 1 : 0; }
+
+static int fail(pedn_sim* s, int code, const std::string& msg) {
+  g_last_error = msg;
+  if (s) s->err = msg;
+  return code;
+}
+
+#define HIP_TRY(sim, expr)                                                                     \
+  do {                                                                                         \
+    hipError_t _e = (expr);                                                                    \
+    if (_e != hipSuccess)                                                                      \
+      return fail(sim, PEDN_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));      \
+  } while (0)
+
+template <typename T>
+static int upload(pedn_sim* s, const T* src, size_t n, const T** dst) {
+  void* p = nullptr;
+  size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+  HIP_TRY(s, hipMalloc(&p, bytes));
+  s->allocs.push_back(p);
+  if (n) HIP_TRY(s, hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+  *dst = (const T*)p;
+  return PEDN_OK;
+}
+
+template <typename T>
+static int dalloc(pedn_sim* s, size_t n, T** dst) {
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
+  if (e != hipSuccess) return fail(s, PEDN_E_NOMEM, std::string("hipMalloc of ") + std::to_string(n * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+  s->allocs.push_back(p);
+  *dst = (T*)p;
+  return PEDN_OK;
+}
+
+// A staging slot of at least `bytes` whose previous use has completed (the other slot may still be in flight).
+#define PEDN_DIRECT_READ_BYTES 65536     // pedn_read_block: up to this size the gather kernel writes into the pinned buffer itself
+#define PEDN_IN_PLACE_BYTES (4u << 20)   // host rows up to this size are read in place by their consuming kernel (stage_in_place; measured up to 256 KB)
+static int stage_acquire(pedn_sim* s, size_t bytes, pedn_sim::Stage** out) {
+  pedn_sim::Stage& st = s->stage[s->stage_next];
+  s->stage_next ^= 1;
+  if (!st.done) HIP_TRY(s, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+  else HIP_TRY(s, hipEventSynchronize(st.done));
+  if (bytes > st.bytes) {
+    if (st.dev) HIP_TRY(s, hipFree(st.dev));
+    if (st.pin) HIP_TRY(s, hipHostFree(st.pin));
+    st.dev = st.pin = nullptr;
+    st.bytes = 0;
+    const size_t want = std::max<size_t>(bytes, 1 << 20);
+    HIP_TRY(s, hipMalloc(&st.dev, want));
+    HIP_TRY(s, hipHostMalloc(&st.pin, want, hipHostMallocDefault));
+    st.bytes = want;
+  }
+  *out = &st;
+  return PEDN_OK;
+}
+
+// host values -> the slot's device buffer (through its pinned buffer: the caller's memory is not touched after the return)
+static int stage_upload(pedn_sim* s, pedn_sim::Stage* st, const void* src, size_t bytes, size_t offset = 0) {
+  memcpy((char*)st->pin + offset, src, bytes);
+  HIP_TRY(s, hipMemcpyAsync((char*)st->dev + offset, (char*)st->pin + offset, bytes, hipMemcpyHostToDevice, s->stream));
+  return PEDN_OK;
+}
+
+// call after the last launch that reads or writes the slot
+static int stage_commit(pedn_sim* s, pedn_sim::Stage* st) {
+  HIP_TRY(s, hipEventRecord(st->done, s->stream));
+  return PEDN_OK;
+}
+
+// Host rows that ONE kernel reads once (the action rows of a host-driven env step): copied into a pinned slot and read by the kernel IN
+// PLACE over the bus -- no copy command in front of the launch (a DMA costs ~20 us of stream latency, a copy from pageable memory waits
+// for the stream; the consuming wave's bus read costs it ~2 us).  The caller records the slot's event behind the consuming launch
+// (stage_commit).  2048 envs: 93-96 -> 81 us per host-driven step, 48 -> 29 without a fetch.
+static int stage_in_place(pedn_sim* s, const void* src, size_t bytes, pedn_sim::Stage** out) {
+  int rc = stage_acquire(s, bytes, out);
+  if (rc != PEDN_OK) return rc;
+  memcpy((*out)->pin, src, bytes);
+  return PEDN_OK;
+}
+
+// host bytes -> a device buffer of the engine; the caller's memory is borrowed for the call only, so the copy is waited for (rows beyond
+// PEDN_IN_PLACE_BYTES; what was measured instead for smaller ones -- a copy COMMAND from a pinned slot, a copy KERNEL from it -- lost to
+// reading them in place, profiles/r05_host_step_time.txt)
+static int upload_through_stage(pedn_sim* s, void* dst, const void* src, size_t bytes) {
+  HIP_TRY(s, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  return PEDN_OK;
+}
+
+inline int DevicePool::take(pedn_sim* s, size_t bytes, void** out) {
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16));
+  if (e != hipSuccess) return fail(s, PEDN_E_NOMEM, std::string("hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+  push_back(p);
+  const hipError_t z = hipMemset(p, 0, std::max<size_t>(bytes, 16));
+  if (z != hipSuccess) return fail(s, PEDN_E_DEVICE, std::string("hipMemset: ") + hipGetErrorString(z));
+  *out = p;
+  return PEDN_OK;
+}
+inline void DevicePool::drop() {
+  for (void* p : *this) (void)hipFree(p);
+  clear();
+}
+
+// a store (pedn_sim::ro / rp) goes: its arrays are freed, its view is zeroed (padding too: it is hashed as bytes), its flags are cleared
+template <typename Store>
+static void store_drop(Store& st) {
+  st.mem.drop();
+  st = Store();
+  memset(&st.view, 0, sizeof st.view);
+}
+
+// the rows the fetches hand out: the normalised pair while the running normalisation is on, else (or raw) the raw one; rew right behind
+// obs in both (pedn_rl_configure, pedn_rl_norm_configure)
+struct FetchRows { float *obs, *rew; };
+static inline FetchRows fetch_rows(const pedn_sim* s, bool raw = false) {
+  if (s->norm.on && !raw) return {s->norm.view.obs_n, s->norm.view.rew_n};
+  return {s->rl.obs, s->rl.rew};
+}
+
+// ... and they are the rows that a record launch of the rollout store and a push launch of the replay store copy
+static void store_sources(pedn_sim* s) {
+  const FetchRows f = fetch_rows(s);
+  if (s->ro.on) { s->ro.view.obs_src = f.obs; s->ro.view.rew_src = f.rew; }
+  if (s->rp.on) { s->rp.view.obs_src = f.obs; s->rp.view.rew_src = f.rew; }
+}
+
+// ---- core services, defined in pedn_hip.hip: what a subsystem's host section may call of the engine proper
+static inline void join_forked(pedn_sim* s);           // ends a clocked section, joins the chains pedn_rl_step left forked
+static inline void pending_links_first(pedn_sim* s);   // ... and performs a pending link update: in front of whatever reads or changes the state
+static int clock_end(pedn_sim* s);
+static int catch_up(pedn_sim* s, int upto);
+static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, float* rewards, const CtrlView* cv, int norm = 0, int term = 0);
+static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_t t, int32_t action_gap, float* obs, float* rewards,
+                   const CtrlView* cv);

@@ -1,6 +1,6 @@
 // pedn_metrics.hpp -- the reference's evaluation metrics (rl/rl_utils.py:770-1512) for every replica on the device: pedn_metrics_begin /
-// pedn_metrics_accumulate / pedn_metrics_read of include/pedn.h.  Included at the end of pedn_hip.hip (it uses the engine's handle and
-// its ordering helpers); nothing here is called by a step.
+// pedn_metrics_accumulate / pedn_metrics_read of include/pedn.h.  Like every subsystem header it is included behind pedn_host.hpp (it
+// uses the engine's handle and the core's ordering services); the core calls metrics_free, nothing here is called by a step.
 //
 // metrics_accumulate_kernel: one wave per (link, 64 replicas), lane = replica.  Each lane walks the rows of its window in order and adds
 // into its own f64 accumulators [MA_K][L][RS]: the three f32 fields are read once each, as coalesced 256-byte row segments, and nothing

@@ -27,19 +27,6 @@
 #define PEDN_NORM_STRANDS 64
 #define PEDN_NORM_MAX_AGENTS (PEDN_NORM_COLS * PEDN_NORM_STRANDS)   // batch moments of the returns sit in the strand arrays
 
-struct NormView {
-  const float *obs, *rew;        // the raw rows: [R][O], [R][n_agents]
-  float *obs_n, *rew_n;          // the normalised rows (rew_n right behind obs_n)
-  double *mean, *var, *count;    // [O] each
-  double *ret;                   // [R][n_agents] discounted returns
-  double *ret_stats;             // mean, var, count of the returns
-  const int32_t* tracked;        // [O] 1: normalised; 0: copied (a gater's gate width)
-  const int32_t* clock;          // the device-resident step clock (a clocked launch takes `terminated` from it)
-  int32_t R, O, n_agents, T;
-  int32_t norm_obs, norm_reward, training, pad_;
-  double clip_obs, clip_reward, gamma;
-};
-
 __device__ __forceinline__ double norm_clip(double x, double c) { return x < -c ? -c : (x > c ? c : x); }   // (NaN stays NaN, like np.clip)
 
 // RunningMeanStd._update_from_moments, operation for operation
@@ -184,4 +171,150 @@ __global__ __launch_bounds__(1024) void norm_kernel(NormView n, int rewards, int
   __shared__ double sQ[PEDN_NORM_STRANDS][PEDN_NORM_COLS];
   if (blockIdx.x + 1 == gridDim.x) norm_reward_block(n, rewards, term, &sP[0][0], &sQ[0][0]);
   else norm_obs_block(n, sP, sQ);
+}
+
+// ---- host side: pedn_rl_norm_* of include/pedn.h; the core calls norm_launch (behind whatever wrote the raw rows) and norm_reset_returns
+static void norm_launch(pedn_sim* s, hipStream_t st, int rewards, int term) {
+  if (!s->norm.on) return;
+  const unsigned blocks = (unsigned)((s->norm.view.O + PEDN_NORM_COLS - 1) / PEDN_NORM_COLS) + 1u;   // + the reward workgroup
+  hipLaunchKernelGGL(norm_kernel, dim3(blocks), dim3(1024), 0, st, s->norm.view, rewards, term);
+}
+
+static int norm_reset_returns(pedn_sim* s) {   // a new episode: the discounted returns start again, the statistics stay
+  if (!s->norm.alloc) return PEDN_OK;
+  HIP_TRY(s, hipMemsetAsync(s->norm.view.ret, 0, (size_t)s->v.R * s->rl.n_agents * sizeof(double), s->stream));
+  return PEDN_OK;
+}
+
+static int norm_init_stats(pedn_sim* s) {
+  const int O = s->rl.O;
+  std::vector<double> h((size_t)3 * O + 3);
+  for (int c = 0; c < O; ++c) { h[c] = 0.0; h[(size_t)O + c] = 1.0; h[(size_t)2 * O + c] = 1e-4; }
+  h[(size_t)3 * O] = 0.0; h[(size_t)3 * O + 1] = 1.0; h[(size_t)3 * O + 2] = 1e-4;
+  HIP_TRY(s, hipMemcpy(s->norm.view.mean, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_configure(pedn_sim* s, int32_t norm_obs, int32_t norm_reward, double clip_obs, double clip_reward, double gamma,
+                           const int32_t* tracked_mask, const int32_t* agent_of_column) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: a captured graph is checked against the signature before its next replay)
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  const RlView& q = s->rl;
+  if (!norm_obs && !norm_reward) {   // off: the fetches hand out the raw rows again; the statistics are discarded
+    s->norm.on = false;
+    const NormView keep = s->norm.view;
+    memset(&s->norm.view, 0, sizeof s->norm.view);
+    if (s->norm.alloc) {   // (the buffers stay with the agent set)
+      s->norm.view.obs_n = keep.obs_n; s->norm.view.rew_n = keep.rew_n; s->norm.view.mean = keep.mean; s->norm.view.var = keep.var; s->norm.view.count = keep.count;
+      s->norm.view.ret = keep.ret; s->norm.view.ret_stats = keep.ret_stats; s->norm.view.tracked = keep.tracked;
+    }
+    store_sources(s);
+    return PEDN_OK;
+  }
+  if (s->ctrl.ready) return fail(s, PEDN_E_ARG, "controllers and the running normalisation cannot be combined");
+  if (!tracked_mask || !agent_of_column) return fail(s, PEDN_E_ARG, "null argument");
+  if (!(clip_obs > 0.0) || !(clip_reward > 0.0)) return fail(s, PEDN_E_ARG, "clip_obs and clip_reward must be positive");
+  if (q.n_agents > PEDN_NORM_MAX_AGENTS) return fail(s, PEDN_E_ARG, "more than 1024 agents");
+  if ((int64_t)s->v.R * std::max(q.O, q.n_agents) > 0x7fffffff) return fail(s, PEDN_E_ARG, "observation buffer too large for the normalisation kernel");
+  for (int c = 0; c < q.O; ++c)
+    if (agent_of_column[c] < 0 || agent_of_column[c] >= q.n_agents) return fail(s, PEDN_E_ARG, "agent_of_column out of range");
+  int rc;
+  NormView n;
+  memset(&n, 0, sizeof n);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
+  if (!s->norm.alloc) {
+    double* d = nullptr;
+    float* f = nullptr;
+    int32_t* m = nullptr;
+    const size_t n_ret = (size_t)s->v.R * q.n_agents;
+    if ((rc = dalloc(s, (size_t)3 * q.O + 3 + n_ret, &d)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)s->v.R * q.O + n_ret, &f)) != PEDN_OK) return rc;
+    if ((rc = dalloc(s, (size_t)q.O, &m)) != PEDN_OK) return rc;
+    n.mean = d; n.var = d + q.O; n.count = d + 2 * (size_t)q.O; n.ret_stats = d + 3 * (size_t)q.O; n.ret = n.ret_stats + 3;
+    n.obs_n = f; n.rew_n = f + (size_t)s->v.R * q.O;
+    n.tracked = m;
+    HIP_TRY(s, hipMemset(f, 0, ((size_t)s->v.R * q.O + n_ret) * sizeof(float)));
+  } else {
+    const NormView& o = s->norm.view;
+    n.mean = o.mean; n.var = o.var; n.count = o.count; n.ret_stats = o.ret_stats; n.ret = o.ret; n.obs_n = o.obs_n; n.rew_n = o.rew_n; n.tracked = o.tracked;
+  }
+  n.obs = q.obs; n.rew = q.rew; n.clock = s->d_clock;
+  n.R = s->v.R; n.O = q.O; n.n_agents = q.n_agents; n.T = s->v.T1 - 1;
+  n.norm_obs = norm_obs ? 1 : 0; n.norm_reward = norm_reward ? 1 : 0; n.training = 1;
+  n.clip_obs = clip_obs; n.clip_reward = clip_reward; n.gamma = gamma;
+  s->norm.view = n;
+  s->norm.alloc = true;
+  s->norm.tracked.assign(tracked_mask, tracked_mask + q.O);
+  for (int32_t& t : s->norm.tracked) t = t ? 1 : 0;
+  s->norm.agent.assign(agent_of_column, agent_of_column + q.O);
+  HIP_TRY(s, hipMemcpy(const_cast<int32_t*>(n.tracked), s->norm.tracked.data(), (size_t)q.O * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(s, hipMemset(n.ret, 0, (size_t)s->v.R * q.n_agents * sizeof(double)));
+  if ((rc = norm_init_stats(s)) != PEDN_OK) return rc;
+  s->norm.on = true;
+  store_sources(s);
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_set_training(pedn_sim* s, int32_t training) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->norm.on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);   // (the flag travels in the launch's arguments: a clocked section ends, a captured graph is captured again)
+  s->norm.view.training = training ? 1 : 0;
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_get_stats(pedn_sim* s, double* mean, double* var, double* count, double* ret_stats) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->norm.on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  const int O = s->norm.view.O;
+  std::vector<double> h((size_t)3 * O + 3);
+  HIP_TRY(s, hipMemcpy(h.data(), s->norm.view.mean, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (mean) memcpy(mean, h.data(), (size_t)O * sizeof(double));
+  if (var) memcpy(var, h.data() + O, (size_t)O * sizeof(double));
+  if (count) {   // per agent: the count of its tracked columns (they all carry the same one)
+    for (int a = 0; a < s->norm.view.n_agents; ++a) count[a] = 1e-4;
+    for (int c = O - 1; c >= 0; --c)
+      if (s->norm.tracked[c]) count[s->norm.agent[c]] = h[(size_t)2 * O + c];
+  }
+  if (ret_stats) memcpy(ret_stats, h.data() + (size_t)3 * O, 3 * sizeof(double));
+  return PEDN_OK;
+}
+
+int pedn_rl_norm_set_stats(pedn_sim* s, const double* mean, const double* var, const double* count, const double* ret_stats) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->norm.on) return fail(s, PEDN_E_ARG, "pedn_rl_norm_configure has not switched the normalisation on");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  const int O = s->norm.view.O;
+  std::vector<double> h((size_t)3 * O + 3);
+  HIP_TRY(s, hipMemcpy(h.data(), s->norm.view.mean, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (mean) memcpy(h.data(), mean, (size_t)O * sizeof(double));
+  if (var) memcpy(h.data() + O, var, (size_t)O * sizeof(double));
+  if (count)
+    for (int c = 0; c < O; ++c) h[(size_t)2 * O + c] = count[s->norm.agent[c]];
+  if (ret_stats) memcpy(h.data() + (size_t)3 * O, ret_stats, 3 * sizeof(double));
+  HIP_TRY(s, hipMemcpy(s->norm.view.mean, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  return PEDN_OK;
+}
+
+void* pedn_rl_norm_device_ptr(pedn_sim* s, int32_t which) {
+  if (!s || !s->norm.on) return nullptr;
+  const NormView& n = s->norm.view;
+  switch (which) {
+    case 0: return n.obs_n;
+    case 1: return n.rew_n;
+    case 2: return n.mean;
+    case 3: return n.var;
+    case 4: return n.count;
+    case 5: return n.ret;
+    case 6: return n.ret_stats;
+  }
+  return nullptr;
 }

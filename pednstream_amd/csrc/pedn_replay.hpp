@@ -27,18 +27,6 @@
 
 #define PEDN_REPLAY_GROUP 8   // samples per workgroup pass (4 waves: two samples each)
 
-struct ReplayView {
-  const float *obs_src, *rew_src;   // what the fetches hand out: the normalised rows while the running normalisation is on
-  float* frames;
-  double* actions;
-  float *rewards, *done, *stacked;
-  int64_t *first, *step_serial, *state;
-  const int32_t* clock;             // the device-resident step clock
-  int64_t cap, R;
-  uint32_t k0, k1;                  // key(seed)
-  int32_t N, A, n_actions, n_obs, stack, T;
-};
-
 // n 4-byte words; 16-byte accesses when both ends allow (uniform over the caller's lanes)
 __device__ __forceinline__ void replay_copy_words(uint32_t* dst, const uint32_t* src, size_t n, size_t tid, size_t nth) {
   if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0 && (n & 3) == 0) {
@@ -232,4 +220,129 @@ __global__ __launch_bounds__(256) void replay_sample_kernel(ReplayView r, Replay
       __hip_atomic_store(r.state + 4, d + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+
+// ---- host side: pedn_replay_* of include/pedn.h.  State: pedn_sim::rp (store_drop, store_sources: pedn_host.hpp)
+int pedn_replay_free(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: a captured push launch is not replayed over freed rows, pedn_rl_clock_signature)
+  HIP_TRY(s, hipDeviceSynchronize());
+  store_drop(s->rp);
+  return PEDN_OK;
+}
+
+int pedn_replay_configure(pedn_sim* s, int64_t capacity, int32_t stack_size, int32_t episode_steps, uint64_t seed) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  if (capacity < 1) return fail(s, PEDN_E_ARG, "capacity < 1");
+  if (stack_size < 1) return fail(s, PEDN_E_ARG, "stack_size < 1");
+  if (episode_steps < 1) return fail(s, PEDN_E_ARG, "episode_steps < 1");
+  if (capacity > (int64_t)1 << 40) return fail(s, PEDN_E_ARG, "capacity too large");
+  if ((int64_t)s->v.R * stack_size * s->rl.O > 0x7fffffff) return fail(s, PEDN_E_ARG, "more than 2^31 entries in the stacked observation");
+  int rc = pedn_replay_free(s);
+  if (rc != PEDN_OK) return rc;
+  const RlView& q = s->rl;
+  ReplayView r;
+  memset(&r, 0, sizeof r);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
+  r.cap = capacity;
+  r.R = capacity + stack_size + (capacity + episode_steps - 1) / episode_steps + 1;
+  const size_t N = (size_t)s->v.R, R = (size_t)r.R;
+  DevicePool& mem = s->rp.mem;
+  if ((rc = mem.take(s, R * N * q.O * sizeof(float), (void**)&r.frames)) != PEDN_OK || (rc = mem.take(s, R * N * q.A * sizeof(double), (void**)&r.actions)) != PEDN_OK ||
+      (rc = mem.take(s, R * N * q.n_agents * sizeof(float), (void**)&r.rewards)) != PEDN_OK || (rc = mem.take(s, R * sizeof(float), (void**)&r.done)) != PEDN_OK ||
+      (rc = mem.take(s, N * stack_size * q.O * sizeof(float), (void**)&r.stacked)) != PEDN_OK || (rc = mem.take(s, R * sizeof(int64_t), (void**)&r.first)) != PEDN_OK ||
+      (rc = mem.take(s, (size_t)capacity * sizeof(int64_t), (void**)&r.step_serial)) != PEDN_OK || (rc = mem.take(s, 16 * sizeof(int64_t), (void**)&r.state)) != PEDN_OK) {
+    const std::string keep = s->err;
+    store_drop(s->rp);
+    return fail(s, rc, keep);
+  }
+  const int64_t no_episode = -1;
+  HIP_TRY(s, hipMemcpy(r.state + 3, &no_episode, sizeof no_episode, hipMemcpyHostToDevice));
+  r.clock = s->d_clock;
+  r.k0 = (uint32_t)(seed & 0xffffffffu); r.k1 = (uint32_t)(seed >> 32);
+  r.N = s->v.R; r.A = q.n_agents; r.n_actions = q.A; r.n_obs = q.O; r.stack = stack_size; r.T = s->v.T1 - 1;
+  s->rp.view = r;
+  s->rp.on = true;
+  store_sources(s);
+  return PEDN_OK;
+}
+
+// both roles of replay_push_kernel get the same number of workgroups: a lane takes about four 16-byte accesses of the wider role (few
+// workgroups: every one of them takes a ticket from one counter)
+static dim3 replay_push_grid(const ReplayView& r) {
+  const size_t row = (size_t)r.N * std::max(std::max(r.n_obs, 2 * r.n_actions), r.A) / 4 + 1;
+  const size_t stack = (size_t)r.N * r.stack * r.n_obs / ((r.n_obs & 3) ? 1 : 4);
+  return dim3((unsigned)std::min<size_t>((std::max(row, stack) + 1023) / 1024, 512), 2);
+}
+
+int pedn_replay_begin(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rp.on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: the RESET row takes the observation the eager reset left)
+  hipLaunchKernelGGL(replay_push_kernel, replay_push_grid(s->rp.view), dim3(256), 0, s->stream, s->rp.view, (const double*)nullptr, 1, 0);
+  HIP_TRY(s, hipGetLastError());
+  s->rp.begun = true;
+  return PEDN_OK;
+}
+
+// (no allocation, no synchronisation, no event query: safe under stream capture)
+int pedn_replay_push(pedn_sim* s, const double* actions, int32_t term, void* stream) {
+  if (!s || !actions) return fail(s, PEDN_E_ARG, "null argument");
+  if (!s->rp.on || !s->rp.begun) return fail(s, PEDN_E_ARG, "pedn_replay_begin has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  hipLaunchKernelGGL(replay_push_kernel, replay_push_grid(s->rp.view), dim3(256), 0, st, s->rp.view, actions, 0, s->clocked ? -1 : (term ? 1 : 0));
+  HIP_TRY(s, hipGetLastError());
+  return PEDN_OK;
+}
+
+// (the same: safe under stream capture)
+int pedn_replay_sample(pedn_sim* s, int64_t batch, const int64_t* indices, int32_t obs0, int32_t obs_w, int32_t act0, int32_t act_w,
+                       int32_t rew0, int32_t rew_w, float* states, double* actions, float* rewards, float* next_states, float* dones,
+                       int64_t* idx, void* stream) {
+  if (!s || !states || !actions || !rewards || !next_states || !dones) return fail(s, PEDN_E_ARG, "null argument");
+  if (!s->rp.on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
+  const ReplayView& r = s->rp.view;
+  if (batch < 1 || batch > 0x7fffffffll) return fail(s, PEDN_E_ARG, "batch size out of range");
+  if (obs0 < 0 || obs_w < 1 || obs0 + obs_w > r.n_obs || act0 < 0 || act_w < 1 || act0 + act_w > r.n_actions || rew0 < 0 || rew_w < 1 ||
+      rew0 + rew_w > r.A)
+    return fail(s, PEDN_E_ARG, "column range outside the row");
+  HIP_TRY(s, hipSetDevice(s->device));
+  ReplayOut o;
+  memset(&o, 0, sizeof o);
+  o.states = states; o.next_states = next_states; o.rewards = rewards; o.dones = dones; o.actions = actions; o.idx = idx;
+  o.obs0 = obs0; o.obs_w = obs_w; o.act0 = act0; o.act_w = act_w; o.rew0 = rew0; o.rew_w = rew_w;
+  const int64_t groups = (batch + PEDN_REPLAY_GROUP - 1) / PEDN_REPLAY_GROUP;
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  hipLaunchKernelGGL(replay_sample_kernel, dim3((unsigned)groups), dim3(256), 0, st, r, o, indices, (uint32_t)batch);
+  HIP_TRY(s, hipGetLastError());
+  return PEDN_OK;
+}
+
+int pedn_replay_size(pedn_sim* s, int64_t* state) {
+  if (!s || !state) return fail(s, PEDN_E_ARG, "null argument");
+  if (!s->rp.on) return fail(s, PEDN_E_ARG, "pedn_replay_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  HIP_TRY(s, hipDeviceSynchronize());   // pushes and samples may sit on a caller's stream
+  HIP_TRY(s, hipMemcpy(state, s->rp.view.state, 6 * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (state[5]) HIP_TRY(s, hipMemset(s->rp.view.state + 5, 0, sizeof(int64_t)));   // reported once
+  return PEDN_OK;
+}
+
+void* pedn_replay_device_ptr(pedn_sim* s, int32_t which) {
+  if (!s || !s->rp.on) return nullptr;
+  const ReplayView& r = s->rp.view;
+  switch (which) {
+    case 0: return r.frames;
+    case 1: return r.actions;
+    case 2: return r.rewards;
+    case 3: return r.done;
+    case 4: return r.first;
+    case 5: return r.step_serial;
+    case 6: return r.stacked;
+    case 7: return r.state;
+  }
+  return nullptr;
 }

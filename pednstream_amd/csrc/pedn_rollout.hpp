@@ -24,17 +24,6 @@
 
 #define PEDN_GAE_UNROLL 8
 
-struct RolloutView {
-  const float *obs_src, *rew_src;   // what the fetches hand out: the normalised rows while the running normalisation is on
-  double* actions;
-  float *values, *rewards, *done, *obs;   // obs: NULL when observations are not kept
-  float *td_target, *adv, *adv_n;         // [cap][N][A] each
-  double* rowsum;                         // [2][cap][A]: row sums of the two normalisation passes
-  int32_t* state;                         // cursor, ticket, overflow, (unused)
-  const int32_t* clock;                   // the device-resident step clock
-  int32_t cap, N, A, n_actions, n_obs, T, pad_[2];
-};
-
 __device__ __forceinline__ void rollout_copy_f32(float* dst, const float* src, size_t n, size_t tid, size_t nth) {
   if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0 && (n & 3) == 0) {   // (uniform over the launch)
     const float4* s4 = reinterpret_cast<const float4*>(src);
@@ -191,4 +180,148 @@ __global__ __launch_bounds__(1024) void rollout_advnorm_kernel(const float* x, f
   __syncthreads();
   const double sum = norm_tree_lds(sP, col, sub, cnt);
   if (cin && s == 0) rs[(size_t)pass * TA + (size_t)t * A + c] = sum;
+}
+
+// ---- host side: pedn_rollout_* and pedn_gae of include/pedn.h.  State: pedn_sim::ro (store_drop, store_sources: pedn_host.hpp)
+static unsigned rollout_blocks(size_t elems) { return (unsigned)std::min<size_t>(std::max<size_t>((elems + 1023) / 1024, 1), 2048); }
+
+int pedn_rollout_free(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: a captured record launch is not replayed over freed rows, pedn_rl_clock_signature)
+  HIP_TRY(s, hipDeviceSynchronize());
+  store_drop(s->ro);
+  return PEDN_OK;
+}
+
+int pedn_rollout_configure(pedn_sim* s, int32_t capacity, int32_t store_obs) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
+  if (capacity < 1) return fail(s, PEDN_E_ARG, "capacity < 1");
+  int rc = pedn_rollout_free(s);
+  if (rc != PEDN_OK) return rc;
+  const RlView& q = s->rl;
+  const size_t N = (size_t)s->v.R, cap = (size_t)capacity, nv = N * q.n_agents;
+  if (nv > 0x7fffffffull) return fail(s, PEDN_E_ARG, "more than 2^31 trajectories");   // (a lane index is an int; rows are addressed in 64 bits)
+  RolloutView r;
+  memset(&r, 0, sizeof r);   // (padding too: the view is hashed as bytes, pedn_rl_clock_signature)
+  DevicePool& mem = s->ro.mem;
+  if ((rc = mem.take(s, cap * N * q.A * sizeof(double), (void**)&r.actions)) != PEDN_OK || (rc = mem.take(s, (cap + 1) * nv * sizeof(float), (void**)&r.values)) != PEDN_OK ||
+      (rc = mem.take(s, cap * nv * sizeof(float), (void**)&r.rewards)) != PEDN_OK || (rc = mem.take(s, cap * N * sizeof(float), (void**)&r.done)) != PEDN_OK ||
+      (rc = mem.take(s, cap * nv * sizeof(float), (void**)&r.td_target)) != PEDN_OK || (rc = mem.take(s, cap * nv * sizeof(float), (void**)&r.adv)) != PEDN_OK ||
+      (rc = mem.take(s, cap * nv * sizeof(float), (void**)&r.adv_n)) != PEDN_OK || (rc = mem.take(s, 2 * cap * q.n_agents * sizeof(double), (void**)&r.rowsum)) != PEDN_OK ||
+      (rc = mem.take(s, 4 * sizeof(int32_t), (void**)&r.state)) != PEDN_OK ||
+      (store_obs && (rc = mem.take(s, (cap + 1) * N * q.O * sizeof(float), (void**)&r.obs)) != PEDN_OK)) {
+    const std::string keep = s->err;
+    store_drop(s->ro);
+    return fail(s, rc, keep);
+  }
+  r.clock = s->d_clock;
+  r.cap = capacity; r.N = s->v.R; r.A = q.n_agents; r.n_actions = q.A; r.n_obs = q.O; r.T = s->v.T1 - 1;
+  s->ro.view = r;
+  s->ro.on = true;
+  store_sources(s);
+  return PEDN_OK;
+}
+
+int pedn_rollout_begin(pedn_sim* s) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro.on) return fail(s, PEDN_E_ARG, "pedn_rollout_configure has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  pending_links_first(s);   // (ends a clocked section: the cursor goes back behind everything recorded so far)
+  const RolloutView& r = s->ro.view;
+  hipLaunchKernelGGL(rollout_begin_kernel, dim3(rollout_blocks(r.obs ? (size_t)r.N * r.n_obs : 1)), dim3(256), 0, s->stream, r);
+  HIP_TRY(s, hipGetLastError());
+  s->ro.begun = true;
+  s->ro.finished = false;
+  s->ro.rows = 0;
+  return PEDN_OK;
+}
+
+// (no allocation, no synchronisation, no event query: safe under stream capture)
+int pedn_rollout_record(pedn_sim* s, const double* actions, const float* values, int32_t term, void* stream) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro.on || !s->ro.begun) return fail(s, PEDN_E_ARG, "pedn_rollout_begin has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  const RolloutView& r = s->ro.view;
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  const size_t widest = (size_t)r.N * std::max(std::max(r.obs ? r.n_obs : 0, 2 * r.n_actions), r.A);
+  hipLaunchKernelGGL(rollout_record_kernel, dim3(rollout_blocks(widest)), dim3(256), 0, st, r, actions, values, s->clocked ? -1 : (term ? 1 : 0));
+  HIP_TRY(s, hipGetLastError());
+  s->ro.finished = false;
+  return PEDN_OK;
+}
+
+int pedn_rollout_finish(pedn_sim* s, const float* last_values, int32_t* rows, int32_t* overflow) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro.on || !s->ro.begun) return fail(s, PEDN_E_ARG, "pedn_rollout_begin has not been called");
+  HIP_TRY(s, hipSetDevice(s->device));
+  join_forked(s);   // (ends a clocked section)
+  HIP_TRY(s, hipDeviceSynchronize());   // records may sit on a caller's stream
+  const RolloutView& r = s->ro.view;
+  int32_t h[4] = {0, 0, 0, 0};
+  HIP_TRY(s, hipMemcpy(h, r.state, sizeof h, hipMemcpyDeviceToHost));
+  const int n = std::min(h[0], r.cap);
+  const size_t nv = (size_t)r.N * r.A;
+  if (last_values) HIP_TRY(s, hipMemcpy(r.values + (size_t)n * nv, last_values, nv * sizeof(float), hipMemcpyDeviceToDevice));
+  else HIP_TRY(s, hipMemset(r.values + (size_t)n * nv, 0, nv * sizeof(float)));
+  HIP_TRY(s, hipDeviceSynchronize());
+  s->ro.rows = n;
+  s->ro.finished = true;
+  if (rows) *rows = n;
+  if (overflow) *overflow = h[2];
+  return PEDN_OK;
+}
+
+static void gae_launch(const float* rew, const float* val, const float* done, int T, int lanes, int done_div, double gamma, double lmbda,
+                       float* td, float* adv, hipStream_t st) {
+  const float g = (float)gamma, c = (float)(gamma * lmbda);   // (the product in binary64, rounded once)
+  const dim3 grid((unsigned)((lanes + 255) / 256));
+  if (val) hipLaunchKernelGGL(rollout_gae_kernel<false>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
+  else hipLaunchKernelGGL(rollout_gae_kernel<true>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
+}
+
+int pedn_rollout_compute(pedn_sim* s, double gamma, double lmbda, int32_t normalize) {
+  if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
+  if (!s->ro.on || !s->ro.finished) return fail(s, PEDN_E_ARG, "pedn_rollout_finish has not been called");
+  const RolloutView& r = s->ro.view;
+  const int T = s->ro.rows;
+  if (T < 1) return fail(s, PEDN_E_ARG, "the store is empty");
+  if (normalize && (int64_t)T * r.N < 2) return fail(s, PEDN_E_ARG, "advantage normalisation needs at least two entries per agent");
+  HIP_TRY(s, hipSetDevice(s->device));
+  gae_launch(r.rewards, r.values, r.done, T, r.N * r.A, r.A, gamma, lmbda, r.td_target, r.adv, s->stream);
+  if (normalize) {
+    const dim3 grid((unsigned)((r.A + PEDN_NORM_COLS - 1) / PEDN_NORM_COLS), (unsigned)T);
+    for (int pass = 0; pass < 3; ++pass)   // (a launch per pass: each needs every workgroup's row sums of the one before)
+      hipLaunchKernelGGL(rollout_advnorm_kernel, grid, dim3(1024), 0, s->stream, r.adv, r.adv_n, r.rowsum, T, r.N, r.A, pass);
+  }
+  HIP_TRY(s, hipGetLastError());
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  return PEDN_OK;
+}
+
+void* pedn_rollout_device_ptr(pedn_sim* s, int32_t which) {
+  if (!s || !s->ro.on) return nullptr;
+  const RolloutView& r = s->ro.view;
+  switch (which) {
+    case 0: return r.actions;
+    case 1: return r.values;
+    case 2: return r.rewards;
+    case 3: return r.done;
+    case 4: return r.obs;
+    case 5: return r.td_target;
+    case 6: return r.adv;
+    case 7: return r.adv_n;
+    case 8: return r.state;
+  }
+  return nullptr;
+}
+
+int pedn_gae(const float* rewards, const float* values, const float* dones, int32_t T, int32_t lanes, double gamma, double lmbda,
+             float* td_target, float* adv, void* stream) {
+  if (!rewards || !adv || (values && (!dones || !td_target))) return fail(nullptr, PEDN_E_ARG, "null argument");
+  if (T < 1 || lanes < 1) return fail(nullptr, PEDN_E_ARG, "T and lanes must be positive");
+  gae_launch(rewards, values, dones, T, lanes, 1, gamma, lmbda, td_target, adv, (hipStream_t)stream);
+  HIP_TRY(nullptr, hipGetLastError());
+  return PEDN_OK;
 }

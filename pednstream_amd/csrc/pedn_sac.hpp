@@ -266,3 +266,41 @@ __global__ __launch_bounds__(256) void sac_polyak_kernel(float4* __restrict__ ta
     target[i] = t;
   }
 }
+
+// ---- host side: pedn_sac_td_target and pedn_sac_soft_update of include/pedn.h; no state in the engine's handle
+int pedn_sac_td_target(const float* next_states, const float* rewards, const float* dones, const int32_t* table, const int32_t* critic_table,
+                       const float* actor_params, const float* target_params, const float* log_alpha, const float* noise,
+                       float* out_actions, float* out_agents, int64_t* state, int32_t batch, int32_t stack_size, int32_t n_obs,
+                       int32_t n_actions, int32_t n_agents, int32_t hidden_size, double max_delta, double gamma, uint64_t seed,
+                       void* stream) {
+  if (!next_states || !rewards || !dones || !table || !critic_table || !actor_params || !target_params || !log_alpha || !out_actions ||
+      !out_agents || !state)
+    return fail(nullptr, PEDN_E_ARG, "null argument");
+  if (hidden_size != PEDN_ACTOR_HIDDEN) return fail(nullptr, PEDN_E_ARG, "the SAC target kernel is built for hidden_size 64");
+  if (batch < 1 || stack_size < 1 || n_obs < 1 || n_actions < 1 || n_agents < 1 || n_agents > 65535)
+    return fail(nullptr, PEDN_E_ARG, "batch, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)");
+  SacTargetArgs a{};
+  a.ns = next_states; a.rewards = rewards; a.dones = dones; a.table = table; a.ctable = critic_table;
+  a.actor = actor_params; a.critic = target_params; a.log_alpha = log_alpha; a.noise = noise;
+  a.out_actions = out_actions; a.out_agents = out_agents; a.state = state;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
+  a.B = batch; a.S = stack_size; a.n_obs = n_obs; a.n_actions = n_actions; a.n_agents = n_agents;
+  a.max_delta = (float)max_delta; a.gamma = (float)gamma;
+  const dim3 grid((unsigned)((batch + PEDN_SAC_TILE - 1) / PEDN_SAC_TILE), (unsigned)n_agents);
+  hipLaunchKernelGGL(sac_target_kernel, grid, dim3(192), 0, (hipStream_t)stream, a);
+  HIP_TRY(nullptr, hipGetLastError());
+  return PEDN_OK;
+}
+
+int pedn_sac_soft_update(float* target, const float* online, int64_t n_floats, double tau, void* stream) {
+  if (!target || !online) return fail(nullptr, PEDN_E_ARG, "null argument");
+  if (n_floats < 4 || n_floats % 4) return fail(nullptr, PEDN_E_ARG, "the packs' length must be a positive multiple of 4 floats");
+  if (((uintptr_t)target | (uintptr_t)online) & 15) return fail(nullptr, PEDN_E_ARG, "the packs must be 16-byte aligned");
+  if (!(tau >= 0.0 && tau <= 1.0)) return fail(nullptr, PEDN_E_ARG, "tau must be in [0, 1]");
+  const int64_t n4 = n_floats / 4;
+  const int64_t blocks = (n4 + 255) / 256;
+  hipLaunchKernelGGL(sac_polyak_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<float4*>(target), reinterpret_cast<const float4*>(online), n4, (float)(1.0 - tau), (float)tau);
+  HIP_TRY(nullptr, hipGetLastError());
+  return PEDN_OK;
+}

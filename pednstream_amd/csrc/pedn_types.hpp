@@ -158,3 +158,62 @@ struct DevView {
   char* rb[RB_COUNT];
   uint32_t *quiet_rd, *quiet_wr;
 };
+
+// ---- views of the training-side subsystems (pedn_ctrl / norm / rollout / replay.hpp): what their launches carry by value.  Here, not with
+// their kernels, because the engine's handle embeds them (pedn_host.hpp); pedn_rl_clock_signature hashes them as bytes.
+struct CtrlAgent {
+  int32_t kind;     // 0 no controller, 1 gater rule, 2 separator rule
+  int32_t window;   // separator: moving-average window (0: no smoothing)
+  int32_t wide;     // separator without smoothing: the width is a binary64 numpy scalar (binary64 arithmetic instead of float32)
+  int32_t ring;     // separator with smoothing: first row of its window in CtrlView::ring
+  float thr;        // gater: threshold rounded to float32
+  float w32;        // separator: road width rounded to float32
+  double w64;       // separator: road width
+};
+
+struct CtrlView {
+  const CtrlAgent* agent;   // [n_agents]
+  const float* open;        // [A] gater slots: float32 physical width of the slot's link
+  double* actions;          // [R][A] next actions
+  float* ep;                // [R][n_agents] episode reward sums
+  float* ring;              // [rows][RS] moving-average values
+  int32_t* count;           // [n_agents][RS] values appended to each buffer so far
+  int32_t ep_mode;          // 1: add this step's reward; 2: start from 0 (the reset observation)
+  int32_t RS;               // replica stride of ring / count rows
+};
+
+struct NormView {
+  const float *obs, *rew;        // the raw rows: [R][O], [R][n_agents]
+  float *obs_n, *rew_n;          // the normalised rows (rew_n right behind obs_n)
+  double *mean, *var, *count;    // [O] each
+  double *ret;                   // [R][n_agents] discounted returns
+  double *ret_stats;             // mean, var, count of the returns
+  const int32_t* tracked;        // [O] 1: normalised; 0: copied (a gater's gate width)
+  const int32_t* clock;          // the device-resident step clock (a clocked launch takes `terminated` from it)
+  int32_t R, O, n_agents, T;
+  int32_t norm_obs, norm_reward, training, pad_;
+  double clip_obs, clip_reward, gamma;
+};
+
+struct RolloutView {
+  const float *obs_src, *rew_src;   // what the fetches hand out: the normalised rows while the running normalisation is on
+  double* actions;
+  float *values, *rewards, *done, *obs;   // obs: NULL when observations are not kept
+  float *td_target, *adv, *adv_n;         // [cap][N][A] each
+  double* rowsum;                         // [2][cap][A]: row sums of the two normalisation passes
+  int32_t* state;                         // cursor, ticket, overflow, (unused)
+  const int32_t* clock;                   // the device-resident step clock
+  int32_t cap, N, A, n_actions, n_obs, T, pad_[2];
+};
+
+struct ReplayView {
+  const float *obs_src, *rew_src;   // what the fetches hand out: the normalised rows while the running normalisation is on
+  float* frames;
+  double* actions;
+  float *rewards, *done, *stacked;
+  int64_t *first, *step_serial, *state;
+  const int32_t* clock;             // the device-resident step clock
+  int64_t cap, R;
+  uint32_t k0, k1;                  // key(seed)
+  int32_t N, A, n_actions, n_obs, stack, T;
+};
