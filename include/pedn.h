@@ -534,6 +534,27 @@ int pedn_sac_td_target(const float* next_states, const float* rewards, const flo
  * 0 <= tau <= 1): the reference's soft_update of every target critic at once.  One launch on `stream`, capturable like the above. */
 int pedn_sac_soft_update(float* target, const float* online, int64_t n_floats, double tau, void* stream);
 
+/* ---- PPO's value critics and old log-probabilities of a whole rollout (rl/agents/PPO_org.py:175-197 StackedValueNetwork, :543-577) -------
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 16 (tests/ppo_eval_model.py restates it in numpy).
+ *   obs          f32 [T + 1][N][n_obs]: every observation once (array 4 of pedn_rollout_device_ptr behind pedn_rollout_finish).  The state
+ *                of row t, 0 <= t <= T, of env e is the frames obs[max(t - (stack_size - 1) + s, 0)][e], s = 0 .. stack_size - 1, oldest
+ *                first; input i = f * stack_size + s of an agent is that frame's column obs0 + f
+ *   actions      [T][N][n_actions], f32 (actions_f64 = 0) or f64 (1, read as (float)x): the actions whose log-probability is wanted
+ *   table        the int32 [n_agents][6] table of pedn_actor_forward, with the same guarantees; actor_params its PPO-kind pack
+ *   value_table  int32 [n_agents]: the offset (floats, a multiple of 4) of the agent's value network in value_params
+ *   value_params f32: per agent, in nn.Linear's [out][in] layout, encoder.fc1 [64][stack_size * obs_w] + [64], encoder.fc2 [64][64] + [64],
+ *                fc [64][64] + [64], value_head [1][64] + [1]; v = value_head(relu(fc(encoder))), no LayerNorm
+ *   values       f32 [T + 1][N][n_agents]: V of every state, row T the bootstrap value; values[t + 1] is the reference's next_values[t]
+ *   old_log_probs  f32 [T][N][n_actions]: Normal(mu, std).log_prob(action) with mu, std of pedn_actor_forward's kind 1 (std clamped to
+ *                [min_std, max_std]), evaluated in double from the float32 values and rounded once
+ *   mu, std      f32 [T][N][n_actions], or NULL: not written
+ * Written for every column some agent owns.  hidden_size must be 64.  One launch on `stream` (NULL = the default stream); no allocation,
+ * no synchronisation, no event query, constant arguments: safe under stream capture. */
+int pedn_ppo_evaluate(const float* obs, const void* actions, const int32_t* table, const int32_t* value_table, const float* actor_params,
+                      const float* value_params, float* values, float* old_log_probs, float* mu, float* std, int32_t T, int32_t N,
+                      int32_t stack_size, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size, int32_t actions_f64,
+                      double min_std, double max_std, void* stream);
+
 /* ---- replay store of the off-policy trainers on the device (rl/rl_utils.py:37-50 ReplayBuffer; rl/agents/SAC.py:127-225) ----------
  * A device-resident ring of transitions of every env that keeps each observation ONCE, filled by ONE launch per policy step, and a
  * gather of sampled minibatches as stacks of the last `stack_size` observations.  The contract (restated in numpy by

@@ -2,7 +2,7 @@
 // and plan choice (pedn_create), the setters and reads, the step path (launch_step, pedn_step, pedn_run, rl_step and the clocked step) and
 // the agent set (pedn_rl_configure) of the C-ABI of include/pedn.h.  The kernels live in pedn_kernels.hpp, the device data structures in
 // pedn_types.hpp, the bit-exact arithmetic primitives in pedn_math.hpp, the handle and the shared host helpers in pedn_host.hpp.
-// Every training-side feature (controllers, running normalisation, rollout and replay stores, stacked actors, SAC targets, evaluation
+// Every training-side feature (controllers, running normalisation, rollout and replay stores, stacked actors, SAC targets, PPO evaluation, evaluation
 // metrics) lives entirely in its own header, kernels first and host section behind them; this file knows them by a few named functions
 // (norm_launch, norm_reset_returns, store_drop, metrics_free), they know it by the services declared at the end of pedn_host.hpp.
 //
@@ -20,6 +20,7 @@
 #include "pedn_replay.hpp"
 #include "pedn_actor.hpp"
 #include "pedn_sac.hpp"
+#include "pedn_ppo.hpp"
 #include "pedn_metrics.hpp"
 
 // The first launch on a stream and the first cross-stream wait cost the runtime ~0.2 ms (queue creation, signal set-up): pay

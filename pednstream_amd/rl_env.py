@@ -707,6 +707,14 @@ class VecPedNetEnv:
 
         return for_env(self, actors, gamma, tau, seed)
 
+    def ppo_targets(self, actors):
+        """The gradient-free half of the reference's ``PPOAgent.update`` for every agent of this env (``pednstream_amd.ppo.PpoTargets``):
+        ``evaluate_store(rollout_store)`` writes the value of every state of a finished fill into the store and returns the old
+        log-probabilities of its actions, in ONE launch.  ``actors``: this env's ``stacked_actors("ppo", stack_size)``."""
+        from .ppo import for_env
+
+        return for_env(self, actors)
+
     def _ordered_behind_engine(self):
         """The caller's current torch stream waits (on the device) for everything enqueued on the engine's stream so far."""
         import torch
@@ -1038,6 +1046,10 @@ class MultiScenarioVecEnv:
     def sac_targets(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv steps separate engines: SAC targets belong to one VecPedNetEnv (one per group: "
                          "env.groups[i].sac_targets(...))")
+
+    def ppo_targets(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv steps separate engines: PPO targets belong to one VecPedNetEnv (one per group: "
+                         "env.groups[i].ppo_targets(...))")
 
     def set_running_norm(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv does not run the running normalisation: its groups are separate engines with statistics of "
