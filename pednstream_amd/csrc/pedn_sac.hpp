@@ -7,9 +7,9 @@
 //                     per neuron, 8 accumulators (one per row), chunks of 32 inputs whose weight rows (nn.Linear's [out][in], read with
 //                     128-byte row pieces) it copies into its OWN LDS rows of 33 words; within a wave the LDS unit serves reads behind the
 //                     writes issued before them, so a wave's staging needs no workgroup barrier, only the compiler kept from reordering
-//                     (sac_wave_sync).  acc[r] = acc[r] + w * x[r][k], k ascending, one accumulator per (row, neuron): section 14's order.
-//                     The actor wave ends with the double-precision tail on a lane per (row, action): softplus, the noise, tanh, the
-//                     log-probability; then the entropy on a lane per row.  ONE workgroup barrier hands next_action to the critic waves,
+//                     (sac_wave_sync).  The accumulation is pedn_mlp.hpp's mlp_mac, the one of section 14's mlp_layer.  The actor wave
+//                     ends with the double-precision tail on a lane per (row, action): mlp_softplus, the noise (philox_normal), tanh,
+//                     normal_log_prob; then the entropy on a lane per row.  ONE workgroup barrier hands next_action to the critic waves,
 //                     which by then have their encoders behind them; they append it and the newest gate width to their 64 encoder outputs
 //                     (an LDS row of 76 words), run fc (K = 65 + act_w, no ReLU) and fc_out (a lane per row).  A second barrier hands q1
 //                     and q2 to the 8 lanes that form the target.  The last workgroup to finish advances the draw counter (ticket
@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pedn_actor.hpp"
+#include "pedn_mlp.hpp"
 
 #define PEDN_SAC_TILE 8           // rows per workgroup (and per wave: every wave sees the whole tile)
 #define PEDN_SAC_FEAT 76          // words of a critic's fc input row: 64 + act_w + 1 <= 73, rounded up to 16 bytes
@@ -51,7 +51,7 @@ __device__ __forceinline__ void sac_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// One layer of one wave for the tile's 8 rows: acc[r] = b[o]; acc[r] = acc[r] + w[o][k] * x[r][k], k = 0 .. K - 1, for lane o < rows.  Row
+// One layer of one wave for the tile's 8 rows: acc[r] = b[o]; then mlp_mac over chunks of 32 inputs, for lane o < rows.  Row
 // o of the weights starts at w + o * K, behind `gap` more floats from row n0 on (the two heads with fc_mu's bias between them); the biases
 // of rows [0, n0) lie behind row n0 - 1, the others behind the last row.  first: x is gathered from the next stacks (through sXc, rows of
 // 32); otherwise x is the wave's LDS rows xin of stride xs (a multiple of 4 words).  sW, sXc: this wave's own.
@@ -96,28 +96,7 @@ __device__ __forceinline__ void sac_layer(const SacTargetArgs& a, float (&acc)[P
       for (unsigned i = 0; i < PEDN_SAC_TILE / 2; ++i) sXc[(2 * i + half) * PEDN_ACTOR_CHUNK + kk] = x[i];
     }
     sac_wave_sync();
-    if (lane < rows) {
-      const float* wr = sW + lane * (PEDN_ACTOR_CHUNK + 1);
-      const float* xr = first ? sXc : xin + c0;
-      const int st = first ? PEDN_ACTOR_CHUNK : xs;
-      int kk = 0;
-      for (; kk + 4 <= kmax; kk += 4) {
-        const float wa = wr[kk], wb = wr[kk + 1], wc = wr[kk + 2], wd = wr[kk + 3];
-#pragma unroll
-        for (int r = 0; r < PEDN_SAC_TILE; ++r) {
-          const float4 x = *reinterpret_cast<const float4*>(xr + r * st + kk);   // (one address for the wave: a broadcast)
-          acc[r] = acc[r] + wa * x.x;
-          acc[r] = acc[r] + wb * x.y;
-          acc[r] = acc[r] + wc * x.z;
-          acc[r] = acc[r] + wd * x.w;
-        }
-      }
-      for (; kk < kmax; ++kk) {
-        const float w = wr[kk];
-#pragma unroll
-        for (int r = 0; r < PEDN_SAC_TILE; ++r) acc[r] = acc[r] + w * xr[r * st + kk];
-      }
-    }
+    if (lane < rows) mlp_mac(acc, sW + lane * (PEDN_ACTOR_CHUNK + 1), first ? sXc : xin + c0, first ? PEDN_ACTOR_CHUNK : xs, kmax);
   }
 }
 
@@ -178,23 +157,18 @@ __global__ __launch_bounds__(192) void sac_target_kernel(SacTargetArgs a) {
       const int col = act0 + j;
       const bool live = row < (unsigned)a.B;
       const size_t at = (size_t)row * a.n_actions + col;
-      const float sd = z > 20.0f ? z : (float)log1p(exp((double)z));
+      const float sd = mlp_softplus(z);
       float eps = 0.0f;
       if (a.noise) {
         if (live) eps = a.noise[at];
-      } else {
-        const int64_t d = a.state[0];
-        uint32_t w[4] = {row, (uint32_t)d, PEDN_SAC_NOISE_SITE | ((uint32_t)col << 8), (uint32_t)((uint64_t)d >> 32)};
-        philox4x32_10(w, a.k0, a.k1);
-        const double u1 = ((double)w[0] + 1.0) * 0x1p-32, u2 = (double)w[1] * 0x1p-32;
-        eps = (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
-      }
+      } else
+        eps = philox_normal(a.k0, a.k1, row, a.state[0], PEDN_SAC_NOISE_SITE | ((uint32_t)col << 8));
       const float u = mu + sd * eps;
       const float th = (float)tanh((double)u);
       const float na = th * a.max_delta;
       // Normal(mu, std).log_prob(u) - log(1 - tanh(tanh(u))^2 + 1e-7): the reference squashes the squashed action once more
-      const double U = (double)u, M = (double)mu, Sd = (double)sd, T2 = tanh((double)th);
-      const double lp = -((U - M) * (U - M)) / (2.0 * (Sd * Sd)) - log(Sd) - 0.91893853320467267 - log(1.0 - T2 * T2 + 1e-7);
+      const double T2 = tanh((double)th);
+      const double lp = normal_log_prob(u, mu, sd) - log(1.0 - T2 * T2 + 1e-7);
       const float logp = (float)lp;
       sAct[lr * PEDN_ACTOR_MAX_ACT + j] = na;
       sLogp[lr * PEDN_ACTOR_MAX_ACT + j] = logp;
@@ -243,15 +217,7 @@ __global__ __launch_bounds__(192) void sac_target_kernel(SacTargetArgs a) {
     a.out_agents[3 * (size_t)a.B * a.n_agents + at] = a.rewards[at] + (a.gamma * nv) * (1.0f - a.dones[row]);
   }
   if (a.noise) return;
-  if (threadIdx.x == 0) {   // (this lane's wave has read the draw counter)
-    const int64_t d = a.state[0];
-    unsigned* ticket = reinterpret_cast<unsigned*>(a.state + 1);
-    const unsigned mine = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (mine + 1u == gridDim.x * gridDim.y) {
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.state, d + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) advance_draw_counter(a.state, a.state[0]);   // (this lane's wave has read the draw counter)
 }
 
 // target[i] = target[i] * (1 - tau) + online[i] * tau; n4 = the pack's length in float4.

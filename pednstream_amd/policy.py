@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import engine as _engine
+from . import packs
 
 HIDDEN = 64
 MAX_ACT_W = 8
@@ -36,15 +37,7 @@ def tensor_shapes(kind, obs_w, act_w, stack_size, hidden_size=HIDDEN):
 def pack_layout(kind, agents, stack_size, hidden_size=HIDDEN):
     """(offsets, total): offsets[i] = {key: (offset in floats, shape)} of agent i = (obs0, obs_w, act0, act_w), one agent behind the
     other; every agent starts on a multiple of 4 floats."""
-    offsets, at = [], 0
-    for (_, obs_w, _, act_w) in agents:
-        at = -(-at // 4) * 4
-        cur = {}
-        for key, shape in tensor_shapes(kind, obs_w, act_w, stack_size, hidden_size):
-            cur[key] = (at, shape)
-            at += int(np.prod(shape))
-        offsets.append(cur)
-    return offsets, at
+    return packs.layout([tensor_shapes(kind, obs_w, act_w, stack_size, hidden_size) for (_, obs_w, _, act_w) in agents], round_total=False)
 
 
 def agent_table(kind, agents, stack_size):
@@ -62,18 +55,10 @@ def make_module(kind, obs_w, act_w, stack_size, min_std=1e-3, max_std=10.0):
     if kind not in KINDS:
         raise ValueError(f"kind must be 'sac' or 'ppo', got {kind!r}")
 
-    class Encoder(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.fc1, self.fc2 = nn.Linear(int(stack_size) * int(obs_w), HIDDEN), nn.Linear(HIDDEN, HIDDEN)
-
-        def forward(self, x):
-            return torch.relu(self.fc2(torch.relu(self.fc1(x))))
-
     class Actor(nn.Module):
         def __init__(self):
             super().__init__()
-            self.encoder, self.fc = Encoder(), nn.Linear(HIDDEN, HIDDEN)
+            self.encoder, self.fc = packs.make_encoder(obs_w, stack_size), nn.Linear(HIDDEN, HIDDEN)
             if kind == "ppo":
                 self.ln = nn.LayerNorm(HIDDEN)
             self.fc_mu, self.fc_std = nn.Linear(HIDDEN, int(act_w)), nn.Linear(HIDDEN, int(act_w))
@@ -138,10 +123,7 @@ class StackedActors:
 
     # ------------------------------------------------------------------------------------------------ parameters
     def _index(self, agent_id):
-        try:
-            return self.agent_ids.index(agent_id)
-        except ValueError:
-            raise ValueError(f"Unknown agent: {agent_id}") from None
+        return packs.index(self.agent_ids, agent_id)
 
     def _device(self):
         if self._dev is None:
@@ -156,51 +138,28 @@ class StackedActors:
                          "actions": z(torch.float64)}
         return self._dev
 
-    def _checked(self, agent_id, state_dict):
+    def load_state_dict(self, agent_id, state_dict):
+        """Copy an actor's tensors (the reference's keys, ``nn.Linear`` layout; torch tensors or arrays) into the pack."""
         i = self._index(agent_id)
-        keys = {k: v for k, v in state_dict.items()}
-        has_ln = any(k.startswith("ln.") for k in keys)
+        has_ln = any(k.startswith("ln.") for k in state_dict)
         if self.kind == "sac" and has_ln:
             raise ValueError("a state dict with ln.* belongs to the PPO kind (StackedPolicyNetwork), these actors are kind='sac'")
         if self.kind == "ppo" and not has_ln:
             raise ValueError("kind='ppo' needs the LayerNorm's ln.weight / ln.bias (StackedPolicyNetwork)")
-        want = self.offsets[i]
-        if set(keys) != set(want):
-            raise ValueError(f"state dict keys {sorted(keys)} do not match {sorted(want)}")
-        for k, (_, shape) in want.items():
-            if tuple(keys[k].shape) != tuple(shape):
-                raise ValueError(f"{k}: expected shape {tuple(shape)}, got {tuple(keys[k].shape)}")
-        return i, keys
-
-    def load_state_dict(self, agent_id, state_dict):
-        """Copy an actor's tensors (the reference's keys, ``nn.Linear`` layout; torch tensors or arrays) into the pack."""
-        import torch
-
-        i, keys = self._checked(agent_id, state_dict)
-        views = self.parameters(agent_id)
-        with torch.no_grad():
-            for k, v in keys.items():
-                views[k].copy_(torch.as_tensor(np.asarray(v, dtype=np.float32)) if not isinstance(v, torch.Tensor) else v.detach().to(torch.float32))
+        packs.load(self.offsets[i], state_dict, lambda: self._device()["pack"])
         self._loaded.add(i)
 
     def parameters(self, agent_id):
         """{key: float32 CUDA tensor} in ``nn.Linear`` shapes; the tensors ALIAS the pack the kernel reads."""
-        i = self._index(agent_id)
-        pack = self._device()["pack"]
-        return {k: pack[at:at + int(np.prod(shape))].view(*shape) for k, (at, shape) in self.offsets[i].items()}
+        want = self.offsets[self._index(agent_id)]
+        return packs.views(self._device()["pack"], want)
 
     def bind(self, agent_id, module):
         """Copy the module's parameters into the pack and point every ``param.data`` at its view there: an optimiser that steps the
         module updates what the kernel reads, with no copy per update."""
-        sd = {k: v for k, v in module.state_dict().items()}
-        self.load_state_dict(agent_id, sd)
-        views = self.parameters(agent_id)
-        params = dict(module.named_parameters())
-        if set(params) != set(views):
-            raise ValueError(f"the module's parameters {sorted(params)} do not match {sorted(views)}")
-        for k, p in params.items():
-            p.data = views[k]
-        return module
+        self.load_state_dict(agent_id, {k: v for k, v in module.state_dict().items()})
+        packs.check_module(module, self.offsets[self._index(agent_id)])
+        return packs.repoint(module, self.parameters(agent_id))
 
     # ------------------------------------------------------------------------------------------------ acting
     def act(self, stack, deterministic=False, noise=None):

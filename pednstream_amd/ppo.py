@@ -25,6 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import engine as _engine
+from . import packs
 from .policy import HIDDEN, StackedActors
 
 TILE = 32                       # rows per workgroup of ppo_eval_kernel (PEDN_PPO_TILE)
@@ -40,15 +41,7 @@ def value_tensor_shapes(obs_w, stack_size, hidden_size=HIDDEN):
 def value_pack_layout(agents, stack_size, hidden_size=HIDDEN):
     """(offsets, total): offsets[i] = {key: (offset in floats, shape)} of the value network of agent i = (obs0, obs_w, act0, act_w), one
     agent behind the other, every agent on a multiple of 4 floats; total is a multiple of 4 (the padding is zero)."""
-    offsets, at = [], 0
-    for (_, obs_w, _, _) in agents:
-        at = -(-at // 4) * 4
-        cur = {}
-        for key, shape in value_tensor_shapes(obs_w, stack_size, hidden_size):
-            cur[key] = (at, shape)
-            at += int(np.prod(shape))
-        offsets.append(cur)
-    return offsets, -(-at // 4) * 4
+    return packs.layout([value_tensor_shapes(obs_w, stack_size, hidden_size) for (_, obs_w, _, _) in agents])
 
 
 def make_value_module(obs_w, stack_size):
@@ -57,18 +50,10 @@ def make_value_module(obs_w, stack_size):
     import torch
     from torch import nn
 
-    class Encoder(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.fc1, self.fc2 = nn.Linear(int(stack_size) * int(obs_w), HIDDEN), nn.Linear(HIDDEN, HIDDEN)
-
-        def forward(self, x):
-            return torch.relu(self.fc2(torch.relu(self.fc1(x))))
-
     class Value(nn.Module):
         def __init__(self):
             super().__init__()
-            self.encoder, self.fc, self.value_head = Encoder(), nn.Linear(HIDDEN, HIDDEN), nn.Linear(HIDDEN, 1)
+            self.encoder, self.fc, self.value_head = packs.make_encoder(obs_w, stack_size), nn.Linear(HIDDEN, HIDDEN), nn.Linear(HIDDEN, 1)
 
         def forward(self, x):
             zs = self.encoder(x.transpose(1, 2).flatten(1))               # input f * S + s is x[b, s, f]
@@ -98,10 +83,7 @@ class PpoTargets:
 
     # ------------------------------------------------------------------------------------------------ parameters
     def _index(self, agent_id):
-        try:
-            return self.agent_ids.index(agent_id)
-        except ValueError:
-            raise ValueError(f"Unknown agent: {agent_id}") from None
+        return packs.index(self.agent_ids, agent_id)
 
     def _device(self):
         if self._dev is None:
@@ -114,54 +96,23 @@ class PpoTargets:
 
     def parameters(self, agent_id):
         """{key: float32 CUDA tensor} in ``nn.Linear`` shapes; the tensors ALIAS the pack the kernel reads."""
-        i = self._index(agent_id)
-        pack = self._device()["pack"]
-        return {k: pack[at:at + int(np.prod(shape))].view(*shape) for k, (at, shape) in self.offsets[i].items()}
+        want = self.offsets[self._index(agent_id)]
+        return packs.views(self._device()["pack"], want)
 
     def load_state_dict(self, agent_id, state_dict):
         """Copy a value network's tensors (the reference's keys, ``nn.Linear`` layout; torch tensors or arrays) into the pack."""
-        import torch
-
         i = self._index(agent_id)
-        keys = {k: v for k, v in state_dict.items()}
-        want = self.offsets[i]
-        if set(keys) != set(want):
-            raise ValueError(f"state dict keys {sorted(keys)} do not match {sorted(want)}")
-        for k, (_, shape) in want.items():
-            if tuple(keys[k].shape) != tuple(shape):
-                raise ValueError(f"{k}: expected shape {tuple(shape)}, got {tuple(keys[k].shape)}")
-        views = self.parameters(agent_id)
-        with torch.no_grad():
-            for k, v in keys.items():
-                views[k].copy_(torch.as_tensor(np.asarray(v, dtype=np.float32)) if not isinstance(v, torch.Tensor) else v.detach().to(torch.float32))
+        packs.load(self.offsets[i], state_dict, lambda: self._device()["pack"])
         self._loaded.add(i)
 
     def bind(self, agent_id, value_module):
         """Copy the module's parameters into the pack and point every ``param.data`` at its view there: an optimiser that steps the
         module updates what the next launch reads, with no copy per update."""
-        i = self._index(agent_id)
-        params = dict(value_module.named_parameters())
-        if set(params) != set(self.offsets[i]):
-            raise ValueError(f"the module's parameters {sorted(params)} do not match {sorted(self.offsets[i])}")
+        packs.check_module(value_module, self.offsets[self._index(agent_id)])
         self.load_state_dict(agent_id, {k: v for k, v in value_module.state_dict().items()})
-        views = self.parameters(agent_id)
-        for k, p in params.items():
-            p.data = views[k]
-        return value_module
+        return packs.repoint(value_module, self.parameters(agent_id))
 
     # ------------------------------------------------------------------------------------------------ the launch
-    def _check(self, name, t, shape, dtypes):
-        import torch
-
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch tensor")
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"{name} must be on cuda:{self.device}")
-        if t.dtype not in dtypes or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {' or '.join(str(d).replace('torch.', '') for d in dtypes)} tensor")
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-
     def evaluate(self, obs, actions, values_out=None, want_mu_std=False):
         """``obs`` [T + 1, N, n_obs] float32 and ``actions`` [T, N, n_actions] float32 or float64 (the actions whose log-probability is
         wanted: with delta actions the clamped delta, ``StackedActors.outputs["raw"]``), contiguous CUDA.  Returns ``{"values": [T + 1, N,
@@ -174,11 +125,10 @@ class PpoTargets:
         if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[0] < 2 or obs.shape[1] < 1:
             raise ValueError("obs must be a torch tensor of shape [T + 1, N, n_obs] with T >= 1")
         T, N = int(obs.shape[0]) - 1, int(obs.shape[1])
-        f32 = (torch.float32,)
-        self._check("obs", obs, (T + 1, N, self.n_obs), f32)
-        self._check("actions", actions, (T, N, self.n_actions), (torch.float32, torch.float64))
+        packs.check_tensor("obs", obs, self.device, (T + 1, N, self.n_obs))
+        packs.check_tensor("actions", actions, self.device, (T, N, self.n_actions), (torch.float32, torch.float64))
         if values_out is not None:
-            self._check("values_out", values_out, (T + 1, N, self.n_agents), f32)
+            packs.check_tensor("values_out", values_out, self.device, (T + 1, N, self.n_agents))
         missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self.actors._loaded]
         if missing:
             raise ValueError(f"no actor parameters were loaded for {missing}: StackedActors.load_state_dict() or bind() first")

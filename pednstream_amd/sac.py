@@ -21,6 +21,7 @@ import math
 import numpy as np
 
 from . import engine as _engine
+from . import packs
 from .policy import HIDDEN, StackedActors
 
 WHICH = ("critic_1", "critic_2", "target_critic_1", "target_critic_2")
@@ -39,18 +40,8 @@ def critic_shapes(obs_w, act_w, stack_size, hidden_size=HIDDEN):
 def critic_pack_layout(agents, stack_size, hidden_size=HIDDEN):
     """(offsets, total): offsets[i][c] = {key: (offset in floats, shape)} of critic c + 1 of agent i = (obs0, obs_w, act0, act_w); per
     agent critic 1 then critic 2, every critic on a multiple of 4 floats; total is a multiple of 4 (the padding is zero)."""
-    offsets, at = [], 0
-    for (_, obs_w, _, act_w) in agents:
-        pair = []
-        for _c in range(2):
-            at = -(-at // 4) * 4
-            cur = {}
-            for key, shape in critic_shapes(obs_w, act_w, stack_size, hidden_size):
-                cur[key] = (at, shape)
-                at += int(np.prod(shape))
-            pair.append(cur)
-        offsets.append(pair)
-    return offsets, -(-at // 4) * 4
+    flat, total = packs.layout([critic_shapes(obs_w, act_w, stack_size, hidden_size) for (_, obs_w, _, act_w) in agents for _c in range(2)])
+    return [flat[2 * i:2 * i + 2] for i in range(len(agents))], total
 
 
 def make_critic_module(obs_w, act_w, stack_size):
@@ -59,18 +50,10 @@ def make_critic_module(obs_w, act_w, stack_size):
     import torch
     from torch import nn
 
-    class Encoder(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.fc1, self.fc2 = nn.Linear(int(stack_size) * int(obs_w), HIDDEN), nn.Linear(HIDDEN, HIDDEN)
-
-        def forward(self, x):
-            return torch.relu(self.fc2(torch.relu(self.fc1(x))))
-
     class Critic(nn.Module):
         def __init__(self):
             super().__init__()
-            self.encoder, self.fc, self.fc_out = Encoder(), nn.Linear(HIDDEN + int(act_w) + 1, HIDDEN), nn.Linear(HIDDEN, 1)
+            self.encoder, self.fc, self.fc_out = packs.make_encoder(obs_w, stack_size), nn.Linear(HIDDEN + int(act_w) + 1, HIDDEN), nn.Linear(HIDDEN, 1)
 
         def forward(self, s, a):
             zs = self.encoder(s.transpose(1, 2).flatten(1))               # input f * S + s is s[b, s, f]
@@ -109,10 +92,7 @@ class SacTargets:
 
     # ------------------------------------------------------------------------------------------------ parameters
     def _index(self, agent_id):
-        try:
-            return self.agent_ids.index(agent_id)
-        except ValueError:
-            raise ValueError(f"Unknown agent: {agent_id}") from None
+        return packs.index(self.agent_ids, agent_id)
 
     @staticmethod
     def _which(which):
@@ -136,26 +116,13 @@ class SacTargets:
         """{key: float32 CUDA tensor} in ``nn.Linear`` shapes; the tensors ALIAS the pack the kernels read and write."""
         i = self._index(agent_id)
         pack_name, c = self._which(which)
-        pack = self._device()[pack_name]
-        return {k: pack[at:at + int(np.prod(shape))].view(*shape) for k, (at, shape) in self.offsets[i][c].items()}
+        return packs.views(self._device()[pack_name], self.offsets[i][c])
 
     def load_state_dict(self, agent_id, which, state_dict):
         """Copy a critic's tensors (the reference's keys, ``nn.Linear`` layout; torch tensors or arrays) into its pack."""
-        import torch
-
         i = self._index(agent_id)
         pack_name, c = self._which(which)
-        keys = {k: v for k, v in state_dict.items()}
-        want = self.offsets[i][c]
-        if set(keys) != set(want):
-            raise ValueError(f"state dict keys {sorted(keys)} do not match {sorted(want)}")
-        for k, (_, shape) in want.items():
-            if tuple(keys[k].shape) != tuple(shape):
-                raise ValueError(f"{k}: expected shape {tuple(shape)}, got {tuple(keys[k].shape)}")
-        views = self.parameters(agent_id, which)
-        with torch.no_grad():
-            for k, v in keys.items():
-                views[k].copy_(torch.as_tensor(np.asarray(v, dtype=np.float32)) if not isinstance(v, torch.Tensor) else v.detach().to(torch.float32))
+        packs.load(self.offsets[i][c], state_dict, lambda: self._device()[pack_name])
         self._loaded.add((i, which))
 
     @property
@@ -174,14 +141,10 @@ class SacTargets:
             raise ValueError("log_alpha must be a torch tensor of one element")
         modules = dict(zip(WHICH, (critic_1, critic_2, target_critic_1, target_critic_2)))
         for which, m in modules.items():
-            params = dict(m.named_parameters())
-            if set(params) != set(self.offsets[i][0]):
-                raise ValueError(f"{which}: the module's parameters {sorted(params)} do not match {sorted(self.offsets[i][0])}")
+            packs.check_module(m, self.offsets[i][0], f"{which}: ")
         for which, m in modules.items():
             self.load_state_dict(agent_id, which, {k: v for k, v in m.state_dict().items()})
-            views = self.parameters(agent_id, which)
-            for k, p in m.named_parameters():
-                p.data = views[k]
+            packs.repoint(m, self.parameters(agent_id, which))
         if log_alpha is not None:
             view = self.log_alpha[i:i + 1].view(log_alpha.shape)
             with torch.no_grad():
@@ -190,18 +153,6 @@ class SacTargets:
         return modules
 
     # ------------------------------------------------------------------------------------------------ the two launches
-    def _check(self, name, t, shape):
-        import torch
-
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name} must be a torch tensor")
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"{name} must be on cuda:{self.device}")
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous float32 tensor")
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-
     def td_target(self, rewards, next_states, dones, noise=None):
         """``td_target`` float32 [B, n_agents] (one tensor per batch size, written again by the next call of that size) for a whole-row
         minibatch as ``ReplayStore.sample(B)`` hands it out: ``rewards`` [B, n_agents], ``next_states`` [B, stack_size, n_obs], ``dones``
@@ -212,11 +163,11 @@ class SacTargets:
         if not isinstance(dones, torch.Tensor) or dones.dim() != 1 or dones.shape[0] < 1:
             raise ValueError("dones must be a torch tensor of shape [B]")
         B = int(dones.shape[0])
-        self._check("dones", dones, (B,))
-        self._check("rewards", rewards, (B, self.n_agents))
-        self._check("next_states", next_states, (B, self.stack_size, self.n_obs))
+        packs.check_tensor("dones", dones, self.device, (B,))
+        packs.check_tensor("rewards", rewards, self.device, (B, self.n_agents))
+        packs.check_tensor("next_states", next_states, self.device, (B, self.stack_size, self.n_obs))
         if noise is not None:
-            self._check("noise", noise, (B, self.n_actions))
+            packs.check_tensor("noise", noise, self.device, (B, self.n_actions))
         missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self.actors._loaded]
         if missing:
             raise ValueError(f"no actor parameters were loaded for {missing}: StackedActors.load_state_dict() or bind() first")

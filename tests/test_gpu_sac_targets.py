@@ -170,6 +170,36 @@ def test_kernel_equals_the_model(name, S):
     assert first.data_ptr() == again.data_ptr()                          # allocated once per batch size
 
 
+def test_the_acting_kernel_computes_the_same_mu_std_and_eps():
+    """sac_target_kernel's actor wave against actor_forward_kernel (kind "sac") on the same weights, stacks and noise, bit for bit.  The
+    smallest shapes that reach every branch of the shared layer: 9 rows are a full SAC tile of 8 and a ragged one, and for the actors
+    one workgroup with 23 dead envs; K1 = 5 * 7 = 35 is a full chunk and a tail of 3, which takes the scalar remainder loop; the heads
+    are layers of 2 and of 16 rows."""
+    torch = pytest.importorskip("torch")
+    from pednstream_amd.policy import StackedActors
+    from pednstream_amd.sac import SacTargets
+
+    B, S, agents, n_obs, n_actions = TILE + 1, 5, [(0, 7, 0, 1), (7, 7, 1, 8)], 14, 9
+    rng = np.random.default_rng(35)
+    low, high = np.zeros(n_actions, dtype=F), np.full(n_actions, 4.0, dtype=F)
+    actors = StackedActors("sac", agents, low, high, B, n_obs, n_actions, stack_size=S, delta_actions=False, max_delta=MAX_DELTA)
+    sac = SacTargets(actors, gamma=GAMMA)
+    for i, (_, ow, _, aw) in enumerate(agents):
+        actors.load_state_dict(i, random_sd(rng, "sac", ow, aw, S))
+        for which in ("target_critic_1", "target_critic_2"):
+            sac.load_state_dict(i, which, random_critic(rng, ow, aw, S))
+    dev = lambda v: torch.as_tensor(v).cuda()
+    stack = dev((rng.standard_normal((B, S, n_obs)) * 2 + 1).astype(F))
+    noise = rng.standard_normal((B, n_actions)).astype(F)
+    actors.act(stack, noise=dev(noise))
+    acted = {k: host(v) for k, v in actors.outputs.items()}
+    sac.td_target(dev(rng.standard_normal((B, len(agents))).astype(F)), stack, dev(np.zeros(B, dtype=F)), noise=dev(noise))
+    out = {k: host(v) for k, v in sac.outputs.items()}
+    assert same(acted["eps"], noise) and np.all(acted["std"] > 0) and np.all(acted["mu"] != 0)          # (the launches wrote every column)
+    for k in ("mu", "std", "eps"):
+        assert same(out[k], acted[k]), k
+
+
 def test_awkward_values_stay_in_their_row():
     torch = pytest.importorskip("torch")
     name, S, B = "mixed", 4, 20

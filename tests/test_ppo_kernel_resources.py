@@ -7,6 +7,7 @@ KERNELS = {"ppo_eval_kernel"}
 # the sum the kernel's comment derives: a weight chunk 64 x 33 words, an input chunk 32 x 32, hidden rows 32 x 64, the heads' hand-over
 # 32 x 16, the tile's time rows and envs 2 x 32 words
 LDS_BYTES = 4 * (64 * 33 + 32 * 32 + 32 * 64 + 32 * 16 + 2 * 32)
+VGPRS = 128        # the kernel's cap (4 waves per SIMD), which it took in full before its layers moved to pedn_mlp.hpp
 
 
 def test_ppo_kernels_have_no_scratch(tmp_path):
@@ -19,3 +20,4 @@ def test_ppo_kernels_have_no_scratch(tmp_path):
         assert k.get("scratch_instructions", 0) == 0, (name, k)
         assert k.get("vgpr_spill_count", 0) == 0 and k.get("sgpr_spill_count", 0) == 0, (name, k)
     assert 0 < mine["ppo_eval_kernel"].get("group_segment_fixed_size", 0) <= LDS_BYTES == 23040
+    assert mine["ppo_eval_kernel"]["vgpr_count"] <= VGPRS
