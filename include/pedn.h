@@ -299,7 +299,11 @@ int pedn_set_streams(pedn_sim* sim, int32_t n);
  * full-record mode only; results are the same either way; pedn_device_ptr on one of those fields, and the clocked steps, turn it
  * off until the next pedn_reset); with n >= 8: info[7] = node-kernel launches that could skip such stores since the last reset of
  * either kind; with n >= 9: info[8] = 1 when the quiet-corridor launches of info[5] also skip the column pass / row sums of a node
- * slot whose flows are +0.0 in all 64 replicas of a group (PEDN_QUIET_LEAN=0|1, default on; results are the same either way). */
+ * slot whose flows are +0.0 in all 64 replicas of a group (PEDN_QUIET_LEAN=0|1, default on; results are the same either way); with
+ * n >= 10: info[9] = the links that a two-chain range of pedn_run steps in the lean dead-link kernel because no pedestrian can ever
+ * reach them -- proven on the host from the demand rows, turning fractions and gates -- while the node kernel runs over the other
+ * nodes only, on a third stream (PEDN_DEAD_LINKS=0|1, default on; results are the same either way); 0 when that plan is off; with
+ * n >= 11: info[10] = the steps launched under that plan since the last reset of either kind. */
 int pedn_plan_info(pedn_sim* sim, int32_t* info, int32_t n);
 
 /* reset all histories and dynamic state to t = 0 (widths, turning fractions and demand are kept) */

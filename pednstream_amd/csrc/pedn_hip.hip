@@ -14,6 +14,7 @@
 // Compile with -ffp-contract=off: results must match the reference bit for bit.
 #include "pedn_kernels.hpp"
 #include "pedn_host.hpp"
+#include "pedn_partition.hpp"
 #include "pedn_ctrl.hpp"
 #include "pedn_norm.hpp"
 #include "pedn_rollout.hpp"
@@ -31,16 +32,20 @@
 // step, delft 42.8 -> 64.8, profiles/r04_stream_queues.txt).  So the pairing is probed, not assumed: a 300 us spin on each stream,
 // timed together; while they do not overlap another candidate for stream2 is created (the rejected ones stay alive until the
 // search ends, so that the runtime moves on to its other queues).
-static hipStream_t chain_stream(const pedn_sim* s, int c) { return c <= 0 ? s->stream : s->stream2; }
+// (chain 2: the stream of the live bins under the dead-link plan, launch_split_step)
+static hipStream_t chain_stream(const pedn_sim* s, int c) { return c <= 0 ? s->stream : c == 1 ? s->stream2 : s->stream3; }
 
-// a 300 us spin on the engine's stream and on stream2 at once; *ms = how long both took together
-static int probe_overlap(pedn_sim* s, float* ms) {
+// a 300 us spin on the engine's stream and on stream2 (n = 3: and on stream3) at once; *ms = how long all took together
+static int probe_overlap(pedn_sim* s, float* ms, int n = 2) {
   HIP_TRY(s, hipEventRecord(s->ev_fork, s->stream));
-  HIP_TRY(s, hipStreamWaitEvent(s->stream2, s->ev_fork, 0));
+  for (int c = 1; c < n; ++c) HIP_TRY(s, hipStreamWaitEvent(chain_stream(s, c), s->ev_fork, 0));
   HIP_TRY(s, hipEventRecord(s->ev0, s->stream));
-  for (int c = 0; c < 2; ++c) hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, chain_stream(s, c), 30000ull);   // ticks of the constant 100 MHz clock
-  HIP_TRY(s, hipEventRecord(s->ev_join, s->stream2));
-  HIP_TRY(s, hipStreamWaitEvent(s->stream, s->ev_join, 0));
+  for (int c = 0; c < n; ++c) hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, chain_stream(s, c), 30000ull);   // ticks of the constant 100 MHz clock
+  for (int c = 1; c < n; ++c) {
+    hipEvent_t ev = c == 1 ? s->ev_join : s->ev_join3;
+    HIP_TRY(s, hipEventRecord(ev, chain_stream(s, c)));
+    HIP_TRY(s, hipStreamWaitEvent(s->stream, ev, 0));
+  }
   HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
   HIP_TRY(s, hipEventSynchronize(s->ev1));
   HIP_TRY(s, hipEventElapsedTime(ms, s->ev0, s->ev1));
@@ -73,6 +78,34 @@ static int warm_chain_streams(pedn_sim* s, int* got) {
   return rc;
 }
 
+// The third stream (the live bins of the dead-link plan, launch_split_step), probed to run beside BOTH chains' streams as stream2 was
+// probed against the engine's; left null when no candidate does: the plan then stays off (the live launch behind a chain's launches
+// would only lengthen that chain).
+static int warm_third_stream(pedn_sim* s) {
+  if (s->stream3 || !s->dead_links || s->chains < 2) return PEDN_OK;
+  bool probe = true;
+  if (const char* f = getenv("PEDN_STREAM_PROBE")) probe = atoi(f) != 0;
+  std::vector<hipStream_t> rejected;
+  int rc = PEDN_OK;
+  bool ok = false;
+  for (int attempt = 0; attempt < 6 && rc == PEDN_OK && !ok; ++attempt) {
+    // at the highest stream priority: the live launch is a one-generation chain of latencies (3-4 bins x the replica groups) beside
+    // two streams that keep every wave place taken -- its workgroups must not queue behind theirs for a place
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = greatest = 0;
+    if (hipStreamCreateWithPriority(&s->stream3, hipStreamNonBlocking, greatest) != hipSuccess) { s->stream3 = nullptr; break; }
+    if (!probe) { ok = true; break; }
+    float ms = 0.0f;
+    rc = probe_overlap(s, &ms, 3);
+    if (rc == PEDN_OK) rc = probe_overlap(s, &ms, 3);
+    if (rc == PEDN_OK && ms < 0.45f) ok = true;
+    else { rejected.push_back(s->stream3); s->stream3 = nullptr; }
+  }
+  for (hipStream_t x : rejected) hipStreamDestroy(x);
+  (void)hipGetLastError();
+  return rc;
+}
+
 // rows [row0, row1) of every history field back to their initial values (`what` as in init_state_kernel; 1 = everything)
 static int clear_rows(pedn_sim* s, int row0, int row1, int what) {
   DevView& v = s->v;
@@ -101,7 +134,9 @@ static int reset_state(pedn_sim* s) {
   HIP_TRY(s, hipMemsetAsync(v.flags, 0, (size_t)v.RS * sizeof(uint32_t), s->stream));
   s->valid_hi = v.valid_hi = 0x7fffffff;
   s->zhw64 = s->zhw32 = -1;   // every row of the six fields is +0.0 once clear_rows has run
-  s->zgated = 0;
+  s->dl_grow = s->dl_dirty = true;   // dead links: proven afresh from here
+  s->dl_off = false;
+  s->zgated = s->split_steps = 0;
   return clear_rows(s, 0, v.T1, 1);
 }
 
@@ -115,7 +150,7 @@ static int reset_state_lazy(pedn_sim* s) {
   int rc;
   if ((rc = clear_rows(s, 0, 1, 1)) || (rc = clear_rows(s, 1, std::min(v.W, v.T1), 2)) || (rc = clear_rows(s, 1, v.T1, 4))) return rc;
   s->valid_hi = v.valid_hi = 0;
-  s->zgated = 0;   // (the zero-elision marks stay: the rows above row 0 still hold the old episode's values)
+  s->zgated = s->split_steps = 0;   // (the zero-elision marks stay: the rows above row 0 still hold the old episode's values)
   return PEDN_OK;
 }
 
@@ -207,6 +242,11 @@ static int tabulate_pair_pod(pedn_sim* s) {
     }
   for (int t = 0; t < T1; ++t) finish_tabulated_rows(s, &ttab[(size_t)t * nt], 1);
   s->h_ttab = ttab;
+  s->h_tab_nz.assign(std::max(nt, 1), 0);   // dead links: can a tabulated fraction ever be anything but +-0.0?
+  for (int t = 0; t < T1; ++t)
+    for (int tn = 0; tn < nt; ++tn)
+      if (!pedn_part::is_zero(ttab[(size_t)t * nt + tn])) s->h_tab_nz[tn] = 1;
+  s->dl_dirty = true;
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   HIP_TRY(s, hipMemcpy(s->d_pair_pod, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(s, hipMemcpy(s->d_turn_tab, ttab.data(), ttab.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -293,7 +333,8 @@ static void flush_links(pedn_sim* s, int half, hipEvent_t* ev);
 typedef void (*step_kernel_fn)(DevView, int);   // node_kernel, turn_frac_kernel, link_kernel_1r
 static step_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf);
 static void prewarm_chains(pedn_sim* s);
-static int fork_chains(pedn_sim* s, int n);
+static int fork_chains(pedn_sim* s, int n, int idle = -1);
+static int dl_refresh(pedn_sim* s);
 
 int pedn_abi_version(void) { return PEDN_ABI_VERSION; }
 
@@ -389,6 +430,21 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
   s->h_node_slot_ptr.assign(m->node_slot_ptr, m->node_slot_ptr + N + 1);
   s->h_tf_set_epoch.assign(N, 0);
   s->node_demand_row.assign(m->node_demand_row, m->node_demand_row + N);
+  {  // dead links (pedn_partition.hpp): the host's copy of what the proof reads
+    s->h_node_kind.assign(m->node_kind, m->node_kind + N);
+    s->h_slot_in.assign(m->slot_in_link, m->slot_in_link + n_slots);
+    s->h_slot_out.assign(m->slot_out_link, m->slot_out_link + n_slots);
+    s->h_link_rev.assign(m->link_rev, m->link_rev + L);
+    s->h_link_sep.assign(m->link_sep, m->link_sep + L);
+    s->h_link_tau_sw.assign(m->link_tau_sw, m->link_tau_sw + L);
+    s->h_demand_nz.assign(std::max(m->n_demand, 1), 0);
+    for (int row = 0; row < m->n_demand; ++row)
+      for (int t = 0; t < m->T + 1 && !s->h_demand_nz[row]; ++t) s->h_demand_nz[row] = pedn_part::not_plus_zero(m->demand[(size_t)row * (m->T + 1) + t]);
+    if (const char* f = getenv("PEDN_DEAD_LINKS")) s->dead_links = atoi(f) != 0;
+    // PEDN_DEAD_WAVES=3..8: waves per SIMD the lean kernel may hold (see pedn_sim.dead_waves); PEDN_DEAD_STREAMS=1|2: its launches per step
+    if (const char* f = getenv("PEDN_DEAD_WAVES")) s->dead_waves = std::max(3, std::min(atoi(f), 8));
+    if (const char* f = getenv("PEDN_DEAD_STREAMS")) s->dead_streams = atoi(f) == 1 ? 1 : 2;
+  }
 
 #define TRY(expr) do { int _rc = (expr); if (_rc != PEDN_OK) { std::string keep = g_last_error; pedn_destroy(s); g_last_error = keep; return _rc; } } while (0)
   {
@@ -398,6 +454,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join3, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreate(&s->ev0);
     if (e == hipSuccess) e = hipEventCreate(&s->ev1);
     if (e != hipSuccess) { pedn_destroy(s); return fail(nullptr, PEDN_E_DEVICE, std::string("second stream / events: ") + hipGetErrorString(e)); }
@@ -669,6 +726,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
       for (int n = 0; n < N; ++n) load[n] = m->turn_pair_ptr[m->node_turn_ptr[n + 1]] - m->turn_pair_ptr[m->node_turn_ptr[n]];
     s->packed_by = by_load;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return load[a] != load[b] ? load[a] > load[b] : deg(a) > deg(b); });
+    s->h_pack_order.assign(order.begin(), order.end());
     std::vector<std::vector<int>> bins;
     std::vector<int> fill;
     for (int n : order) {
@@ -812,6 +870,17 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
       TRY(dalloc(s, nq, &s->d_quiet));
       HIP_TRY(s, hipMemset(s->d_quiet, 0, nq * sizeof(uint32_t)));
     }
+    if (s->dead_links && s->quiet && s->link_owner && !s->inline_tf && !v.hist && m->node_model != PEDN_NODE_OPTIMAL && v.n_trow == 0 && L > 0) {
+      // dead links: room for a packing of the live nodes alone (at most one bin per node, one idle block behind them), its quiet words,
+      // and the records of every slot dead_link_kernel may step (dl_refresh fills them)
+      const size_t cap = ((size_t)N + 1) * 8, nq = (size_t)2 * cap * (size_t)(v.RS / 64) * 2;
+      if (nq / 2 < ((size_t)1 << 31)) {
+        TRY(dalloc(s, cap, &s->d_live_rec));
+        TRY(dalloc(s, rec.size(), &s->d_dead_rec));
+        TRY(dalloc(s, nq, &s->d_quiet_live));
+        HIP_TRY(s, hipMemset(s->d_quiet_live, 0, nq * sizeof(uint32_t)));
+      }
+    }
   }
   // ---- dynamic state
   {
@@ -873,6 +942,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     TRY(warm_chain_streams(s, &got));
     s->chains = s->warmed_chains = got;
     s->two_streams = s->chains > 1;
+    if (s->d_live_rec) TRY(warm_third_stream(s));
     prewarm_chains(s);
   }
 #undef TRY
@@ -884,6 +954,7 @@ int pedn_destroy(pedn_sim* s) {
   if (!s) return PEDN_OK;
   hipSetDevice(s->device);
   if (s->clocked) hipDeviceSynchronize();   // clocked steps may still run on a caller's stream (or in a graph being replayed there)
+  if (s->stream3) hipStreamSynchronize(s->stream3);
   if (s->stream2) hipStreamSynchronize(s->stream2);
   if (s->stream) hipStreamSynchronize(s->stream);
   metrics_free(s);
@@ -899,6 +970,8 @@ int pedn_destroy(pedn_sim* s) {
   if (s->ev0) hipEventDestroy(s->ev0);
   if (s->ev1) hipEventDestroy(s->ev1);
   if (s->stream2) hipStreamDestroy(s->stream2);
+  if (s->stream3) hipStreamDestroy(s->stream3);
+  if (s->ev_join3) hipEventDestroy(s->ev_join3);
   if (s->ev_fork) hipEventDestroy(s->ev_fork);
   if (s->ev_join) hipEventDestroy(s->ev_join);
   if (s->stream) hipStreamDestroy(s->stream);
@@ -927,6 +1000,15 @@ int pedn_reset_lazy(pedn_sim* s) {
   return rc != PEDN_OK ? rc : reset_state_lazy(s);
 }
 
+// dead links: an upload into demand row `row` -- the host looks at the values (outside any step): a row that may now hold anything but
+// +0.0 is a source of the proof; all = the upload replaces the whole row in every replica
+static void dl_demand_upload(pedn_sim* s, int row, const double* values, size_t n, bool all) {
+  char nz = 0;
+  for (size_t i = 0; i < n && !nz; ++i) nz = pedn_part::not_plus_zero(values[i]);
+  const char now = all ? nz : (char)(s->h_demand_nz[row] | nz);
+  if (now != s->h_demand_nz[row]) { s->h_demand_nz[row] = now; s->dl_dirty = true; }
+}
+
 // values (host) -> rows of a [rows][RS] device array, one replica or all
 static int push_rows(pedn_sim* s, double* dst, const double* values, int n_rows, size_t row0, size_t row_stride, int replica) {
   if (n_rows <= 0) return PEDN_OK;
@@ -952,6 +1034,7 @@ int pedn_set_demand(pedn_sim* s, int32_t node, int32_t replica, const double* va
   if (row < 0) return fail(s, PEDN_E_ARG, "node has no virtual (origin/destination) link");
   std::vector<double> full(s->v.T1, 0.0);  // copied into the pinned staging buffer before push_rows returns
   for (int i = 0; i < n && i < s->v.T1; ++i) full[i] = values[i];
+  dl_demand_upload(s, row, full.data(), full.size(), replica == PEDN_ALL);
   return push_rows(s, s->v.demand, full.data(), s->v.T1, (size_t)row * s->v.T1, 1, replica);
 }
 
@@ -979,6 +1062,7 @@ int pedn_set_demand_matrix(pedn_sim* s, int32_t node, const double* values, int3
   DevView& v = s->v;
   if (n < 0 || n > v.T1) return fail(s, PEDN_E_ARG, "more demand values than time indices");
   if (n == 0) return PEDN_OK;
+  dl_demand_upload(s, row, values, (size_t)v.R * n, false);
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
   const size_t bytes = (size_t)v.R * n * 8;
@@ -1002,6 +1086,7 @@ int pedn_set_demand_rows(pedn_sim* s, int32_t node, const int32_t* replicas, int
   for (int k = 0; k < n_rep; ++k)
     if (replicas[k] < 0 || replicas[k] >= v.R) return fail(s, PEDN_E_ARG, "replica out of range");
   if (n == 0 || n_rep <= 0) return PEDN_OK;
+  dl_demand_upload(s, row, values, (size_t)n_rep * n, false);
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
   // staging layout: values [n_rep][n] (f64), then the replica ids (int32)
@@ -1028,6 +1113,7 @@ int pedn_draw_demand(pedn_sim* s, int32_t node, uint64_t seed, const int32_t* pa
     if (pattern[r] < 0 || pattern[r] > 2) return fail(s, PEDN_E_ARG, "demand pattern outside 0..2");
     if (!(base[r] >= 0.0) || !(peak[r] >= 0.0) || base[r] + 2.0 * peak[r] > 500.0) return fail(s, PEDN_E_ARG, "demand rate outside [0, 500]");
   }
+  if (!s->h_demand_nz[row]) { s->h_demand_nz[row] = 1; s->dl_dirty = true; }   // dead links: a row drawn on the device counts as non-zero
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
   // staging layout: pattern, spike_start, spike_len (int32 [R] each, padded to 8 bytes), then base, peak, spike_height (f64 [R])
@@ -1072,6 +1158,7 @@ int pedn_set_turning_fractions(pedn_sim* s, int32_t node, int32_t replica, const
   if (n != b - a) return fail(s, PEDN_E_ARG, "turning-fraction count does not match m(m-1)");
   int rc = push_rows(s, s->v.tf, tf, n, (size_t)a, 1, replica);
   if (rc != PEDN_OK) return rc;
+  s->dl_dirty = true;
   // a dynamic node recomputes its fractions every step (network.py:272-275); until then a read returns what was imposed
   s->h_tf_set_epoch[node] = s->step_epoch;
   // (the imposed values go into the buffer of the last step too, see below: a REPEAT of that step must recompute them, not take them
@@ -1118,6 +1205,7 @@ int pedn_set_width(pedn_sim* s, int32_t which, int32_t link, int32_t replica, do
   double* dst = which == PEDN_W_FRONT ? s->v.front : which == PEDN_W_BACK ? s->v.back : which == PEDN_W_SEP ? s->v.sepw : s->v.sepnp;
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);     // the link update records the gate / reads the separator width of its own step
+  s->dl_dirty = true;
   if (which == PEDN_W_BACK) s->tp_ready = -1;  // capacity fallback of the turn probabilities (path_finder.py:575-576)
   join_forked(s);   // (as every setter: ordered behind both chains)
   // one launch, its values as kernel arguments: the row's replicas and the link's entry of the replica-uniform shortcut (front_u / back_u:
@@ -1145,6 +1233,7 @@ int pedn_set_widths(pedn_sim* s, int32_t which, const double* values) {
   double* dst = which == PEDN_W_FRONT ? v.front : which == PEDN_W_BACK ? v.back : which == PEDN_W_SEP ? v.sepw : v.sepnp;
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
+  s->dl_dirty = true;
   size_t bytes = (size_t)v.L * v.R * 8;
   pedn_sim::Stage* st;
   int rc = stage_acquire(s, bytes, &st);
@@ -1173,6 +1262,7 @@ int pedn_reset_widths(pedn_sim* s, const double* front, const double* back, cons
   if (v.L == 0) return PEDN_OK;
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
+  s->dl_dirty = true;
   int rc;
   if ((rc = push_rows(s, v.front, front, v.L, 0, 1, PEDN_ALL)) || (rc = push_rows(s, v.back, back, v.L, 0, 1, PEDN_ALL)) ||
       (rc = push_rows(s, v.sepw, sep, v.L, 0, 1, PEDN_ALL)))
@@ -1341,7 +1431,7 @@ static void flush_links(pedn_sim* s, int half, hipEvent_t* ev) {
 // pedn_profile_step.  Returns 1 through *observed when the observations were part of the launch.
 // Every entry point that looks at or changes what a link update reads or writes calls this first: under the owner-wave plan the link
 // update of the last step launched may still be pending (link_pending) -- the next step's node kernel would perform it.
-static int join_chains(pedn_sim* s, int n);
+static int join_chains(pedn_sim* s, int n, int idle = -1);
 // (also: pedn_rl_step may have left the two halves of the batch stepping as two chains on two streams across calls -- `forked` -- so
 // that the engine's stream does not order stream2's work yet: joined first.  Anything that enqueues on the engine's stream or reads
 // device memory calls this, i.e. every entry point but the stepping calls themselves and the pure host getters.)
@@ -1380,8 +1470,170 @@ static void prewarm_chains(pedn_sim* s) {
     if (s->inline_tf) hipLaunchKernelGGL(node_kernel_for(s, true, true), dim3(1, 1), dim3(s->inline_help ? 1024 : 512), s->node_lds_tf, st, v, 2);
     hipLaunchKernelGGL(link_turn_kernel_for(sel, false, false), dim3(1), dim3(256), 0, st, vl, 1, 0u, 0u, 0u, q, 0);
     hipLaunchKernelGGL(link_kernel_1r_for(sel), dim3(1), dim3(256), 0, st, vl, 1);
+    if (s->stream3) hipLaunchKernelGGL(dead_link_kernel, dim3(1), dim3(256), 0, st, v, 2, (const SlotRec*)s->d_dead_rec, 0);   // (no slot: its waves leave)
+  }
+  if (s->stream3) {   // the live bins' stream of the dead-link plan
+    hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3(1, 1), dim3(512), s->node_lds, s->stream3, v, 2);
+    hipStreamSynchronize(s->stream3);
   }
   for (int c = s->chains - 1; c >= 0; --c) hipStreamSynchronize(chain_stream(s, c));
+}
+
+// ---- Dead links (pedn_partition.hpp, dead_link_kernel; pedn_sim.dead_links)
+// The proof, from what the host knows now, and the two things built from it: the records of the dead nodes' slots (dead_link_kernel's
+// work list) and a second packing of the live nodes alone for node_kernel<LU>.  Between full resets the set only
+// shrinks (dl_grow).  A live slot whose corridor's other end is a dead slot mirrors ITSELF: its own quiet word fills its inbox -- the
+// dead end writes +0.0 only, has no separator and a shock-wave look-back >= 1 (eligibility), which is all the inbox vouches for.
+static int dl_refresh(pedn_sim* s) {
+  s->dl_dirty = false;
+  if (!s->d_live_rec) return PEDN_OK;
+  const DevView& v = s->v;
+  const int N = s->n_nodes, L = v.L;
+  std::vector<char> tab(std::max(s->n_turns, 1), 1);
+  if (!v.pod_pr && (int)s->h_tab_nz.size() >= s->n_turns) tab.assign(s->h_tab_nz.begin(), s->h_tab_nz.end());
+  pedn_part::Model pm;
+  pm.n_nodes = N; pm.n_links = L;
+  pm.node_slot_ptr = s->h_node_slot_ptr.data(); pm.node_turn_ptr = s->node_turn_ptr.data(); pm.node_kind = s->h_node_kind.data();
+  pm.node_demand_row = s->node_demand_row.data(); pm.slot_in = s->h_slot_in.data(); pm.slot_out = s->h_slot_out.data();
+  pm.link_rev = s->h_link_rev.data(); pm.slot_dyn = s->h_slot_dyn.data(); pm.node_lp = s->node_lp;
+  pm.demand_nz = s->h_demand_nz.data(); pm.tf_u = s->h_tf_u.data(); pm.tab_nz = tab.data();
+  pm.link_sep = s->h_link_sep.data(); pm.link_tau_sw = s->h_link_tau_sw.data();
+  pm.front_u = s->h_front_u.data(); pm.back_u = s->h_back_u.data();
+  pm.link_rl = s->h_rl_link.size() >= (size_t)L ? s->h_rl_link.data() : nullptr;
+  pm.per_replica_params = v.pr != 0 || s->rl_ready;   // (an agent set: its action slots and controllers stay with the node kernel)
+  std::vector<char> dead = pedn_part::partition(pm).node_dead;
+  if (!s->dl_grow && s->dl_node.size() == dead.size())
+    for (int n = 0; n < N; ++n) dead[n] = dead[n] && s->dl_node[n];
+  else if (!s->dl_grow) dead.assign(N, 0);
+  if (dead == s->dl_node) return PEDN_OK;
+  s->dl_node = dead;
+  no_quiet(s);
+  // the work list of dead_link_kernel, and the live packing: the full packing's records of the live nodes, first-fit in its order
+  const std::vector<SlotRec>& full = s->h_slot_rec;
+  std::vector<SlotRec> pos;
+  std::vector<int32_t> first(N, -1);
+  int n_links = 0;
+  for (size_t i = 0; i < full.size(); ++i) {
+    if (full[i].node < 0) continue;
+    if (full[i].slot == 0) first[full[i].node] = (int32_t)i;
+    if (dead[full[i].node]) { pos.push_back(full[i]); n_links += full[i].lin < L; }
+  }
+  std::vector<std::vector<int>> bins;
+  std::vector<int> fill;
+  for (int n : s->h_pack_order) {
+    if (dead[n]) continue;
+    const int d = s->h_node_slot_ptr[n + 1] - s->h_node_slot_ptr[n];
+    int chosen = -1;
+    for (size_t b = 0; b < bins.size(); ++b)
+      if (fill[b] + d <= 8) { chosen = (int)b; break; }
+    if (chosen < 0) { bins.emplace_back(); fill.push_back(0); chosen = (int)bins.size() - 1; }
+    bins[chosen].push_back(n);
+    fill[chosen] += d;
+  }
+  SlotRec idle{};
+  idle.node = -1; idle.trow = -1; idle.act = -1; idle.lp = -1; idle.mirror = -1;
+  std::vector<SlotRec> rec((bins.size() + 1) * 8, idle);
+  int tiles = 1;
+  for (size_t b = 0; b < bins.size(); ++b) {
+    int wave = 0, base = 0;
+    for (int n : bins[b]) {
+      const int d = s->h_node_slot_ptr[n + 1] - s->h_node_slot_ptr[n];
+      for (int k = 0; k < d; ++k) {
+        SlotRec& R = rec[b * 8 + wave++];
+        R = full[first[n] + k];   // (a node's slots are consecutive waves of one block)
+        R.base = base;
+      }
+      base += d * d;
+    }
+    tiles = std::max(tiles, base);
+  }
+  std::vector<int32_t> pos_of(std::max(L, 1), -1);
+  for (size_t i = 0; i < rec.size(); ++i)
+    if (rec[i].node >= 0 && rec[i].lin < L) pos_of[rec[i].lin] = (int32_t)i;
+  for (size_t i = 0; i < rec.size(); ++i) {
+    SlotRec& R = rec[i];
+    R.mirror = R.node >= 0 && R.lin < L && R.lout < L ? (pos_of[R.lout] >= 0 ? pos_of[R.lout] : (int32_t)i) : -1;
+  }
+  s->n_dead_links = n_links;
+  s->n_dead_pos = (int)pos.size();
+  s->n_live_blocks = (int)bins.size();
+  s->live_npos = (int)rec.size();
+  s->node_lds_live = (size_t)(8 + tiles) * 64 * sizeof(double);
+  // every launch that read the old lists was joined into the engine's stream by the pedn_run that made it
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  HIP_TRY(s, hipMemcpy(s->d_live_rec, rec.data(), rec.size() * sizeof(SlotRec), hipMemcpyHostToDevice));
+  if (!pos.empty()) HIP_TRY(s, hipMemcpy(s->d_dead_rec, pos.data(), pos.size() * sizeof(SlotRec), hipMemcpyHostToDevice));
+  return PEDN_OK;
+}
+
+// Does a two-chain range of pedn_run take the split plan now?  Everything the proof and dead_link_kernel do not cover keeps the plan
+// off: recent-history mode, the node LP, rows of fractions computed on the device, per-replica link parameters, an agent set, no
+// third stream that overlaps, a state the host does not follow (dl_off) -- and a model without a dead link.
+static bool dl_split_ok(pedn_sim* s) {
+  if (!s->dead_links || !s->d_live_rec || !s->stream3 || s->dl_off || s->chains < 2 || !s->link_owner || !s->quiet || s->node_lp || s->inline_tf ||
+      s->v.hist || s->v.pr || s->rl_ready || s->v.n_trow > 0 || s->v.n_pairs_corr == 0)
+    return false;
+  if (s->dl_dirty && dl_refresh(s) != PEDN_OK) return false;
+  return s->n_dead_links > 0;
+}
+
+// Dynamic LDS per workgroup (four waves) of dead_link_kernel such that exactly n of them fit a CU's 160 KB, n = 3..7: the SMALLEST such
+// size, so that the rest stays free for the live workgroups of node_kernel<LU> (n = 5: 28 160 B each, 23 040 B left; the live packing of
+// melbourne asks for 20 480).  In units of 2 560 B, a multiple of both LDS allocation granules in use on CDNA (512 and 1 280 B), so the
+// count does not depend on which one the device rounds to: k units with n k <= 64 < (n + 1) k.
+static size_t dead_lds_bytes(int n) {
+  if (n >= 8) return 0;   // the register budget's own 8 waves per SIMD
+  return (size_t)(64 / (n + 1) + 1) * 2560;
+}
+
+// One step t >= 2 of a split range: dead_link_kernel for the whole batch on the engine's stream (dead_streams = 2: for each half of the
+// replicas on the two chain streams), node_kernel<LU> over the live bins for the whole batch on the third stream; the host's marks
+// advance once, as in launch_step.  Proof obligations -- why the
+// three launches of a step, and the launches of successive steps on different streams, need no order between them:
+//   * the two kinds of wave write disjoint elements: a slot wave of either kernel writes the rows of ITS incoming link (link update,
+//     sending flow, outflow / cumulative_outflow), the receiving flow, gate record and inflow / cumulative_inflow of ITS outgoing link,
+//     and every physical link is the incoming link of exactly one slot, which one of the two work lists holds;
+//   * every element that one kind reads of what the other kind writes is +0.0 in every row since the last full reset: a live slot
+//     next to a dead node reads outflow / cumulative_outflow / num_pedestrians of its outgoing link (written by the dead slot: +0.0 by
+//     construction), a dead slot takes the inflow / cumulative_inflow that a live slot writes into it as +0.0 without reading them --
+//     the link is outside REACH (pedn_partition.hpp), so the node model can only produce +0.0 for it;
+//   * the error flags are OR-ed atomically by both; the live waves read them only to decide their quiet word, which selects between
+//     two paths that give the same bits.
+static void launch_split_step(pedn_sim* s, int t) {
+  const int zg64 = zero_gate(s, s->zhw64, t), zg32 = zero_gate(s, s->zhw32, t - 1);
+  const size_t lds = dead_lds_bytes(s->dead_waves);   // the lean kernel's share of the wave places
+  for (int c = 0; c < s->dead_streams; ++c) {
+    hipStream_t stream;
+    DevView vd = view_of(s, s->dead_streams == 1 ? -1 : c, &stream);
+    vd.zg64 = zg64; vd.zg32 = zg32;
+    row_bases(vd, t);
+    const unsigned waves = (unsigned)s->n_dead_pos * (unsigned)(vd.subRS / 64);
+    if (waves > 0) hipLaunchKernelGGL(dead_link_kernel, dim3((waves + 3) / 4), dim3(256), lds, stream, vd, t, (const SlotRec*)s->d_dead_rec, s->n_dead_pos);
+    if (zg64 || zg32) ++s->zgated;
+  }
+  if (s->n_live_blocks > 0) {
+    DevView vn = s->v;
+    vn.slot_rec = s->d_live_rec;
+    vn.quiet = s->d_quiet_live;
+    vn.quiet_npos = s->live_npos;
+    vn.quiet_use = s->quiet_valid == t - 1 && s->quiet_pack == 1;
+    vn.quiet_lean = s->quiet_lean ? 1 : 0;
+    vn.rl_actions = nullptr;
+    vn.zg64 = zg64; vn.zg32 = zg32;
+    row_bases(vn, t);
+    hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3((unsigned)(vn.RS / 64), (unsigned)s->n_live_blocks), dim3(512), s->node_lds_live, s->stream3, vn, t);
+    if (zg64 || zg32) ++s->zgated;
+  }
+  ++s->split_steps;
+  s->link_pending = t;
+  s->quiet_valid = s->n_live_blocks > 0 ? t : -1;
+  s->quiet_pack = 1;
+  s->zhw64 = std::max(s->zhw64, t);
+  s->zhw32 = std::max(s->zhw32, t - 1);
+  s->second_launch = 0;
+  if (s->valid_hi != 0x7fffffff && t > s->valid_hi) s->valid_hi = s->v.valid_hi = t;
+  s->last_t = t;
+  ++s->step_epoch;
 }
 
 // lazy (owner-wave plan, pedn_run): the link update of t is left to node_kernel<LU>(t + 1) -- or to flush_links -- and this step's
@@ -1392,6 +1644,7 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
                        const double* fold_actions = nullptr, int half = -1, bool lazy = false, const CtrlView* cv = nullptr) {
   // half = -1: the whole batch on the engine's stream; 0 / 1: the first / second half of the replicas on stream / stream2 (the
   // caller, pedn_run, launches both halves of a step and does the per-step bookkeeping once, after the second one)
+  if (s->dl_dirty && half <= 0) dl_refresh(s);   // dead links: an input of the proof has changed since the last step
   if (half < 0 && t - 1 > s->valid_hi) {   // a step that skips ahead after a lazy reset (chains: their callers do this before the fork)
     const int rc = catch_up(s, t - 1);
     if (rc != PEDN_OK) return rc;
@@ -1418,7 +1671,7 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   // t - 1 when the launch of t - 1 was one of them and nothing has touched the history since (quiet_valid)
   const bool quiet = lu && !inl && s->quiet;
   vn.quiet = quiet ? s->d_quiet : nullptr;
-  vn.quiet_use = quiet && s->quiet_valid == t - 1;
+  vn.quiet_use = quiet && s->quiet_valid == t - 1 && s->quiet_pack == 0;   // (the words of a split step belong to the live packing)
   vn.quiet_lean = quiet && s->quiet_lean ? 1 : 0;
   // zero elision: node_kernel(t) writes row t of the flows and cumulative counts, node_kernel<LU>(t) also row t - 1 of num_pedestrians /
   // density (the link update behind an ordinary node kernel writes row t of those, ungated)
@@ -1451,6 +1704,8 @@ static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe
   if (last_chain(s, half)) {
     s->link_pending = lazy ? t : -1;
     s->quiet_valid = quiet ? t : -1;
+    s->quiet_pack = 0;
+    s->dl_grow = false;   // something has run since the last full reset
     s->zhw64 = std::max(s->zhw64, t);
     if (lu) s->zhw32 = std::max(s->zhw32, t - 1);
     if (g.nlb > 0) s->zhw32 = std::max(s->zhw32, t);   // the link update of t below
@@ -1542,19 +1797,22 @@ static int chains_for(const pedn_sim* s, int t0, int t1) {
   return s->v.RS >= 256 ? 2 : 1;   // (every chain at least one 128-replica segment, view_of)
 }
 
-// Fork: every other chain's stream waits for what the engine's stream holds so far.
-static int fork_chains(pedn_sim* s, int n) {
+// Fork: every other chain's stream waits for what the engine's stream holds so far (idle: a chain that gets no work in this range).
+static int fork_chains(pedn_sim* s, int n, int idle) {
   HIP_TRY(s, hipEventRecord(s->ev_fork, s->stream));
-  for (int c = 1; c < n; ++c) HIP_TRY(s, hipStreamWaitEvent(chain_stream(s, c), s->ev_fork, 0));
+  for (int c = 1; c < n; ++c)
+    if (c != idle) HIP_TRY(s, hipStreamWaitEvent(chain_stream(s, c), s->ev_fork, 0));
   return PEDN_OK;
 }
 // Join of the chains of launches: the engine's stream waits for everything enqueued on the other streams.  If the event path fails
 // the streams are drained instead, so that no call ever returns with work on them that the engine's stream does not order.
-static int join_chains(pedn_sim* s, int n) {
+static int join_chains(pedn_sim* s, int n, int idle) {
   hipError_t e = hipSuccess;
   for (int c = 1; c < n && e == hipSuccess; ++c) {
-    e = hipEventRecord(s->ev_join, chain_stream(s, c));
-    if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, s->ev_join, 0);
+    if (c == idle) continue;
+    hipEvent_t ev = c == 1 ? s->ev_join : s->ev_join3;
+    e = hipEventRecord(ev, chain_stream(s, c));
+    if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, ev, 0);
   }
   if (e != hipSuccess) {
     for (int c = n - 1; c >= 0; --c) hipStreamSynchronize(chain_stream(s, c));
@@ -1581,12 +1839,21 @@ int pedn_run(pedn_sim* s, int32_t t0, int32_t t1) {
   if (nch > 1) {
     if (s->link_pending >= 0 && s->link_pending != t0 - 1) pending_links_first(s);   // a stale pending update: on the whole batch, before the fork
     if (t0 - 1 > s->valid_hi && (rc = catch_up(s, t0 - 1)) != PEDN_OK) return rc;
-    if ((rc = fork_chains(s, nch)) != PEDN_OK) return rc;
+    // Dead-link plan: the first node launch of the range on the whole batch and the full bin set, in front of the fork; every later one
+    // is a node_kernel<LU> launch with quiet words and is split (launch_split_step) -- no event between the streams inside the range; with
+    // one lean launch per step (dead_streams = 1) the second chain's stream has no work and is neither forked nor joined
+    const bool split = nch == 2 && lazy && dl_split_ok(s);
+    int t = t0;
+    if (split && (rc = launch_step(s, t++, nullptr, -1, nullptr, nullptr, -1, lazy)) != PEDN_OK) return rc;
+    const int idle = split && s->dead_streams == 1 ? 1 : -1;
+    if ((rc = fork_chains(s, split ? 3 : nch, idle)) != PEDN_OK) return rc;
     s->run_chains = nch;
-    for (int t = t0; t < t1; ++t)
-      for (int c = 0; c < nch; ++c) launch_step(s, t, nullptr, -1, nullptr, nullptr, c, lazy);
+    for (; t < t1; ++t) {
+      if (split) launch_split_step(s, t);
+      else for (int c = 0; c < nch; ++c) launch_step(s, t, nullptr, -1, nullptr, nullptr, c, lazy);
+    }
     s->run_chains = 1;
-    rc = join_chains(s, nch);    // the last step's link update stays pending on the joined stream (pending_links_first)
+    rc = join_chains(s, split ? 3 : nch, idle);    // the last step's link update stays pending on the joined stream (pending_links_first)
     if (rc != PEDN_OK) return rc;
   } else {
     for (int t = t0; t < t1; ++t)
@@ -1607,6 +1874,8 @@ int pedn_plan_info(pedn_sim* s, int32_t* info, int32_t n) {
   if (n >= 7) info[6] = s->zero_elide && !s->v.hist;   // the node kernels may skip +0.0 stores into clean rows (PEDN_ZERO_ELIDE)
   if (n >= 8) info[7] = s->zgated;   // ... and this many node-kernel launches had a gate open since the last reset
   if (n >= 9) info[8] = s->quiet_lean && s->quiet && info[1];   // the quiet-corridor launches take the lean path (PEDN_QUIET_LEAN)
+  if (n >= 10) info[9] = dl_split_ok(s) ? s->n_dead_links : 0;   // links that dead_link_kernel steps in a two-chain range (PEDN_DEAD_LINKS)
+  if (n >= 11) info[10] = s->split_steps;   // ... and the steps that were launched that way since the last reset
   return PEDN_OK;
 }
 
@@ -1625,6 +1894,7 @@ int pedn_set_streams(pedn_sim* s, int32_t n) {
   const int before = s->chains;
   s->chains = n > 1 ? std::min<int>(n, std::max(s->warmed_chains, 1)) : 1;
   s->two_streams = s->chains > 1;
+  if (s->chains > 1 && s->d_live_rec && (rc = warm_third_stream(s)) != PEDN_OK) return rc;
   if (s->chains > before) prewarm_chains(s);   // (every chain's stream: hipSetDevice above)
   return PEDN_OK;
 }
@@ -1816,6 +2086,7 @@ void* pedn_device_ptr(pedn_sim* s, int32_t field, int64_t* columns, int64_t* rep
   if (!s || field < 0 || field >= PEDN_N_FIELDS) return nullptr;
   if ((s->link_pending >= 0 || s->forked || s->clocked || s->valid_hi != 0x7fffffff) && pedn_flush(s) != PEDN_OK) return nullptr;
   // zero elision: a zero-copy consumer may write any row of the field -- no gate on its group until the next full reset
+  s->dl_off = true;   // dead links: ... and no split plan either
   if (field <= F_CO) s->zhw64 = 0x7fffffff;
   if (field == 7 + G_N || field == 7 + G_K || field == 7 + G_LF) s->zhw32 = 0x7fffffff;
   if (columns) *columns = field < 4 ? s->v.Lall : s->v.L;
@@ -1852,6 +2123,7 @@ int pedn_set_link_params(pedn_sim* s, const double* kc, const double* kj, const 
                          const float* tt0) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   s->tp_ready = -1;
+  s->dl_dirty = true;
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -1925,6 +2197,7 @@ int pedn_set_od_weights_per_replica(pedn_sim* s, const double* w) {
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   DevView& v = s->v;
   s->tp_ready = -1;
+  s->dl_dirty = true;
   if (!w) {
     v.pod_pr = 0;
     return PEDN_OK;
@@ -1954,6 +2227,7 @@ int pedn_randomize_scenarios(pedn_sim* s, uint64_t seed, double link_fraction, i
   DevView& v = s->v;
   pending_links_first(s);
   s->tp_ready = -1;
+  s->dl_dirty = true;
   const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
   int rc;
   if ((what & 1) && v.n_pairs_corr > 0) {
@@ -1994,6 +2268,7 @@ int pedn_randomize_scenarios(pedn_sim* s, uint64_t seed, double link_fraction, i
       const int node = origin_nodes[i];
       if (node < 0 || node >= s->n_nodes || s->node_demand_row[node] < 0) return fail(s, PEDN_E_ARG, "origin node without a virtual link");
       hn[i] = s->node_demand_row[node];
+      s->h_demand_nz[hn[i]] = 1;   // dead links: a row drawn on the device counts as non-zero
       hn[n_origins + i] = node;
     }
     pedn_sim::Stage* st;
@@ -2097,6 +2372,7 @@ int pedn_rl_configure(pedn_sim* s, const pedn_rl_desc* d, int32_t* n_actions, in
     v.rl_actions = nullptr;
   }
   s->rl_ready = true;
+  s->dl_dirty = true;
   s->ctrl.ready = s->ctrl.any = false;   // controllers belong to an agent set: configure them again
   s->norm.on = s->norm.alloc = false;    // so does the running normalisation
   memset(&s->norm.view, 0, sizeof s->norm.view);
@@ -2316,6 +2592,7 @@ int pedn_rl_clock_begin(pedn_sim* s, int32_t t) {
   s->clocked = true;
   s->clock_t0 = t;
   s->zhw64 = s->zhw32 = 0x7fffffff;   // zero elision: the host does not see which rows the clocked steps write (until the next full reset)
+  s->dl_off = true;                   // ... and no dead-link plan
   return PEDN_OK;
 }
 

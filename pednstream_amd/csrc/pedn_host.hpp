@@ -83,6 +83,38 @@ struct pedn_sim {
   int zero_elide = 1;
   int zhw64 = 0x7fffffff, zhw32 = 0x7fffffff;
   int zgated = 0;   // node-kernel launches with a gate open since the last reset of either kind (pedn_plan_info info[7])
+  // Dead links (pedn_partition.hpp; PEDN_DEAD_LINKS=0|1, default on): in a two-chain range of pedn_run the nodes that provably never see
+  // a pedestrian are stepped by dead_link_kernel -- one launch per step for the whole batch on the engine's stream (dead_streams = 2: one
+  // per half on the two chain streams) -- and node_kernel<LU> runs over a second packing of the other (live) nodes only, for the whole
+  // batch, on a third stream (launch_split_step).
+  //   dl_dirty  an input of the proof has changed (or nothing was computed yet): dl_refresh recomputes before the next split range
+  //   dl_grow   nothing has run since the last FULL reset: the recomputed set replaces the old one; otherwise it is intersected with it
+  //             (rows above valid_hi may hold a previous episode's values, and a link that ever carried someone holds them anywhere)
+  //   dl_off    something the host does not follow may have written a state or history field (a zero-copy pointer, the clocked steps):
+  //             no split until the next full reset -- the events that set zhw64 / zhw32 to INT_MAX
+  //   quiet_pack  which packing's quiet words quiet_valid speaks of: 0 the full bin set (d_quiet), 1 the live bins (d_quiet_live)
+  int dead_links = 1;
+  bool dl_dirty = true, dl_grow = true, dl_off = false;
+  std::vector<char> dl_node;           // [nodes] 1: stepped by dead_link_kernel
+  std::vector<char> h_demand_nz;       // [demand rows] the row may hold something else than +0.0
+  std::vector<char> h_tab_nz;          // [turns] a host-tabulated fraction that is not +-0.0 at some step (tabulate_pair_pod)
+  std::vector<int32_t> h_pack_order;   // nodes in the order the bins were packed in
+  std::vector<int32_t> h_link_sep, h_link_tau_sw, h_link_rev, h_node_kind, h_slot_in, h_slot_out;
+  int n_dead_links = 0, n_dead_pos = 0, n_live_blocks = 0, live_npos = 0;
+  int split_steps = 0;                 // steps launched by launch_split_step since the last reset of either kind (pedn_plan_info info[10])
+  size_t node_lds_live = 0;
+  SlotRec* d_live_rec = nullptr;       // the live packing's slot records (capacity: the full packing's)
+  SlotRec* d_dead_rec = nullptr;       // the records of the slots dead_link_kernel steps (copies, in work-list order)
+  // The lean kernel is bound by vector instruction issue, and the live launch is a chain of latencies whose waves share the SIMDs with
+  // it: beside 8 lean waves per SIMD the live launch took 20 us, against 12 us alone (profiles/EXPERIMENTS.md #84).
+  // dead_waves = workgroups of four waves per CU = waves per SIMD the lean kernel may hold (PEDN_DEAD_WAVES=3..8; 8: no limit), through
+  // dynamic LDS that it does not use (dead_lds_bytes in pedn_hip.hip: the size leaves the rest of the CU's LDS to the live workgroups).
+  int dead_waves = 5;
+  int dead_streams = 1;                // PEDN_DEAD_STREAMS=1|2: one lean launch per step for the whole batch, or one per half on the chain streams
+  uint32_t* d_quiet_live = nullptr;
+  int quiet_pack = 0;
+  hipStream_t stream3 = nullptr;       // the live bins' stream; null: not seen to overlap with the chains (no split)
+  hipEvent_t ev_join3 = nullptr;
   int fuse_obs = 1;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
   // (The link update as a launch of its own runs one replica per lane -- link_kernel_1r: 42-47 VGPRs, 8 waves per SIMD; melbourne x 1024
   // 12.3-12.6 against 12.7-13.1 us with two replicas per lane, profiles/r03_link_kernel_variants.txt; inside link_turn_kernel, whose

@@ -1226,6 +1226,76 @@ __global__ __launch_bounds__(1024) void node_kernel_h(DevView v, int t) {
   node_step<PR, false, HIST, MD, true, true, true>(v, t, v.valid_hi, (int)blockIdx.x, (int)blockIdx.y, pedn_lds);
 }
 
+// Dead links (pedn_run's split plan, pedn_hip.hip: launch_split_step; the proof: pedn_partition.hpp): one wave per (slot of a node
+// that no pedestrian can reach, 64 replicas), replica group fastest.  The wave does for its slot what the slot wave of node_kernel<LU>(t)
+// does -- the link update of t - 1 for the incoming link, the sending flow of that link and the receiving flow of the outgoing one,
+// Node.update_links -- with every input that the proof fixes given as the literal +0.0 to the SAME device functions: inflow / outflow /
+// the cumulative counts / num_pedestrians / sending_flow of both directions at every row, and the node's flows qo = qi = +0.0 (zero
+// sending flows times any fraction floor and clamp to +0.0 in the classic rule, min(0, r >= 0) = +0.0 at a one-to-one node).  What is
+// left to load: the running sum, travel_time[t - 1 - W] and receiving_flow[t - 2].  No LDS, no barrier, no quiet words (the slots of the
+// live bins next to it mirror themselves, SlotRec.mirror).  Stores, the gate-record rule, the zero-elision gates (a store is skipped
+// only under zg64 / zg32: every value they cover is +0.0 here) and the error flags are node_step's.  Full-record mode, shared link
+// parameters, classic node model, t >= 2 (the host offers nothing else).  rec: the slots' records, a copy in work-list order (no index
+// between the wave and its record).
+__global__ __launch_bounds__(256, 8) void dead_link_kernel(DevView v, int t, const SlotRec* __restrict__ rec, int n_rec) {
+  const unsigned rgroups = (unsigned)(v.subRS >> 6);
+  const unsigned w = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned idx = w / rgroups;
+  if (idx >= (unsigned)n_rec) return;   // wave-uniform
+  const int lane = (int)(threadIdx.x & 63);
+  const int RS = v.RS, L = v.L;
+  const int r0 = v.sub0 + (int)(w % rgroups) * 64, r = r0 + lane, tp = t - 1;
+  const SlotRec& W = rec[idx];
+  const int lin = W.lin, lout = W.lout;
+  const uint32_t oin = (uint32_t)lin * (uint32_t)RS + (uint32_t)r0, oout = (uint32_t)lout * (uint32_t)RS + (uint32_t)r0;
+#define DROW(T, K, OFF) (reinterpret_cast<T*>(v.rb[K]) + (OFF))
+  if (lin < L) {
+    uint32_t fl = 0;
+    const LinkP& Pin = W.Pin;
+    const LinkP& Pout = W.Pout;
+    const bool lu_win = tp >= v.W;
+    const float lu_rs = v.rsum[(size_t)lin * RS + r];
+    const float lu_old = lu_win ? DROW(float, RB_TT_W, oin)[lane] : 0.0f;
+    SlotIn x{};   // every field +0.0: what the proof fixes
+    x.r_prev = DROW(double, RB_R_Q, oout)[lane];
+    const double fu = v.front_u[lin], bu = v.back_u[lout];
+    x.front_in = fu == fu ? fu : (v.front + oin)[lane];
+    x.back_out = bu == bu ? bu : (v.back + oout)[lane];
+    // Network.update_link_states(t') for the incoming link, as in node_step<LU>
+    const double nz = speed_noise(v, Pin, lin, tp, r);
+    const float na = 0.0f, nb = 0.0f;   // (float)(num_pedestrians[t' - 1] + (inflow[t'] - outflow[t'])) of +0.0 each
+    const float ka = na / Pin.area32, kb = nb / Pout.area32;
+    if (!(v.zg32 && __all((__float_as_int(na) | __float_as_int(ka)) == 0))) {
+      DROW(float, RB_N_P, oin)[lane] = na;
+      DROW(float, RB_K_P, oin)[lane] = ka;
+    }
+    const SpeedOut so = speed_calc(v, Pin, lin, tp, r, ka, kb, lu_rs, lu_old, nz);
+    DROW(float, RB_V_P, oin)[lane] = so.spd;
+    DROW(float, RB_TT_P, oin)[lane] = so.tt;
+    if (!(v.zg32 && __all(__float_as_int(so.lf) == 0))) DROW(float, RB_LF_P, oin)[lane] = so.lf;
+    if (lu_win) DROW(float, RB_ATT_P, oin)[lane] = so.att;
+    v.rsum[(size_t)lin * RS + r] = so.rs;
+    if (x.back_out != Pout.width || v.hist) DROW(double, RB_GATE_P, oout)[lane] = x.back_out;
+    x.n_in = na; x.n_out = nb; x.k_in = ka; x.att_in = so.att;
+    const double rp = recv_reverse_peds(v, Pout, lout, tp, r, x, fl);
+    const double s_i = tp < Pin.fft ? 0.0 : send_flow<false, true>(v, Pin, lin, tp, r, x, 0.0, v.valid_hi, fl, (uint32_t)lin * (uint32_t)RS);
+    DROW(double, RB_S_P, oin)[lane] = s_i;
+    if (s_i < 0.0) fl |= PEDN_F_NEG_FLOW;
+    const double r_i = recv_flow(v, Pout, lout, tp, r, x, s_i, rp, fl);
+    DROW(double, RB_R_P, oout)[lane] = r_i;
+    if (s_i < 0.0 || r_i < 0.0) fl |= PEDN_F_NEG_FLOW;
+    if (fl) atomicOr(&v.flags[r], fl);
+  }
+  // Node.update_links with qo = qi = +0.0 on cumulative counts of +0.0 (a virtual pair of such a node: its demand row is +0.0 too)
+  if (!v.zg64) {
+    DROW(double, RB_CO_T, oin)[lane] = 0.0;
+    DROW(double, RB_OUT_T, oin)[lane] = 0.0;
+    DROW(double, RB_CI_T, oout)[lane] = 0.0;
+    DROW(double, RB_IN_T, oout)[lane] = 0.0;
+  }
+#undef DROW
+}
+
 __device__ __forceinline__ double2 ld2(const double* p, size_t i) { return *reinterpret_cast<const double2*>(p + i); }
 __device__ __forceinline__ float2 ld2(const float* p, size_t i) { return *reinterpret_cast<const float2*>(p + i); }
 __device__ __forceinline__ void st2(double* p, size_t i, double a, double b) { *reinterpret_cast<double2*>(p + i) = make_double2(a, b); }

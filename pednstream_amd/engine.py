@@ -486,12 +486,12 @@ class Engine:
 
     def plan_info(self):
         """The launch plan of run(): chains, owner-wave link update, and the result of the stream-overlap probe (include/pedn.h)."""
-        info = np.zeros(9, dtype=np.int32)
-        self._ck(self._lib.pedn_plan_info(self._h, info.ctypes.data_as(_I32P), 9))
+        info = np.zeros(11, dtype=np.int32)
+        self._ck(self._lib.pedn_plan_info(self._h, info.ctypes.data_as(_I32P), 11))
         return {"chains": int(info[0]), "link_update_by_next_node_kernel": bool(info[1]), "stream_probe_attempts": int(info[2]),
                 "stream_probe_us": int(info[3]), "packed_by": ("degree", "static_load_estimate", "measured_node_cost")[int(info[4])],
                 "quiet_corridors": bool(info[5]), "zero_elide": bool(info[6]), "zero_elide_launches": int(info[7]),
-                "quiet_lean": bool(info[8])}
+                "quiet_lean": bool(info[8]), "dead_links": int(info[9]), "dead_link_steps": int(info[10])}
 
     def set_streams(self, n):
         """Launch plan of run() for long ranges: 1 chain of launches, or 2 (the halves of the replica batch on two streams; falls
