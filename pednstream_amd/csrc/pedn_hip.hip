@@ -1482,7 +1482,7 @@ static void prewarm_chains(pedn_sim* s) {
 // ---- Dead links (pedn_partition.hpp, dead_link_kernel; pedn_sim.dead_links)
 // The proof, from what the host knows now, and the two things built from it: the records of the dead nodes' slots (dead_link_kernel's
 // work list) and a second packing of the live nodes alone for node_kernel<LU>.  Between full resets the set only
-// shrinks (dl_grow).  A live slot whose corridor's other end is a dead slot mirrors ITSELF: its own quiet word fills its inbox -- the
+// shrinks (dl_grow), and the proof's sources only grow (dl_src, dl_reach).  A live slot whose corridor's other end is a dead slot mirrors ITSELF: its own quiet word fills its inbox -- the
 // dead end writes +0.0 only, has no separator and a shock-wave look-back >= 1 (eligibility), which is all the inbox vouches for.
 static int dl_refresh(pedn_sim* s) {
   s->dl_dirty = false;
@@ -1496,12 +1496,22 @@ static int dl_refresh(pedn_sim* s) {
   pm.node_slot_ptr = s->h_node_slot_ptr.data(); pm.node_turn_ptr = s->node_turn_ptr.data(); pm.node_kind = s->h_node_kind.data();
   pm.node_demand_row = s->node_demand_row.data(); pm.slot_in = s->h_slot_in.data(); pm.slot_out = s->h_slot_out.data();
   pm.link_rev = s->h_link_rev.data(); pm.slot_dyn = s->h_slot_dyn.data(); pm.node_lp = s->node_lp;
-  pm.demand_nz = s->h_demand_nz.data(); pm.tf_u = s->h_tf_u.data(); pm.tab_nz = tab.data();
+  // once a step has run, the sources of the earlier proofs stay sources: their pedestrians may still be on the way
+  if (s->dl_grow || s->dl_src.size() != s->h_demand_nz.size() || s->dl_reach.size() != (size_t)std::max(L, 1)) {
+    s->dl_src = s->h_demand_nz;
+    s->dl_reach.assign(std::max(L, 1), 0);
+  } else {
+    for (size_t i = 0; i < s->dl_src.size(); ++i) s->dl_src[i] |= s->h_demand_nz[i];
+  }
+  pm.demand_nz = s->dl_src.data(); pm.tf_u = s->h_tf_u.data(); pm.tab_nz = tab.data();
+  pm.seed_links = s->dl_reach.data();
   pm.link_sep = s->h_link_sep.data(); pm.link_tau_sw = s->h_link_tau_sw.data();
   pm.front_u = s->h_front_u.data(); pm.back_u = s->h_back_u.data();
   pm.link_rl = s->h_rl_link.size() >= (size_t)L ? s->h_rl_link.data() : nullptr;
   pm.per_replica_params = v.pr != 0 || s->rl_ready;   // (an agent set: its action slots and controllers stay with the node kernel)
-  std::vector<char> dead = pedn_part::partition(pm).node_dead;
+  const pedn_part::Result proof = pedn_part::partition(pm);
+  std::copy(proof.reach.begin(), proof.reach.end(), s->dl_reach.begin());   // (a superset of the seeds)
+  std::vector<char> dead = proof.node_dead;
   if (!s->dl_grow && s->dl_node.size() == dead.size())
     for (int n = 0; n < N; ++n) dead[n] = dead[n] && s->dl_node[n];
   else if (!s->dl_grow) dead.assign(N, 0);

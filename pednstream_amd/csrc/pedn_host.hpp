@@ -96,6 +96,10 @@ struct pedn_sim {
   int dead_links = 1;
   bool dl_dirty = true, dl_grow = true, dl_off = false;
   std::vector<char> dl_node;           // [nodes] 1: stepped by dead_link_kernel
+  // what the earlier proofs since the last full reset took for sources and found reachable: pedestrians that entered under them are
+  // still walking when a demand row is zeroed or a turn closed behind them, so both stay sources of every later proof (dl_refresh)
+  std::vector<char> dl_src;            // [demand rows] h_demand_nz, OR-ed over those proofs
+  std::vector<char> dl_reach;          // [links] REACH, OR-ed over those proofs
   std::vector<char> h_demand_nz;       // [demand rows] the row may hold something else than +0.0
   std::vector<char> h_tab_nz;          // [turns] a host-tabulated fraction that is not +-0.0 at some step (tabulate_pair_pod)
   std::vector<int32_t> h_pack_order;   // nodes in the order the bins were packed in

@@ -8,6 +8,12 @@
 // rows computed on the device, the node LP).  A link outside REACH has inflow = outflow = +0.0 at every step, whatever the random draws:
 // a zero sending flow times a finite fraction is +-0.0 or NaN, the node model floors and clamps that to +0.0 (node_step in
 // pedn_kernels.hpp), and a fraction that is exactly +-0.0 turns any finite sending flow into +-0.0 the same way.
+// Two more sources, both found by tests/test_gpu_dead_links_random.py:
+//   * a link whose front gate may be negative (a negative shared value, or per-replica values the host does not follow): its sending
+//     flow is min(gate * capacity, ...) < 0 even while it is empty, and a one-to-one node hands min(s, r) on unclamped -- the link fills
+//     with the pedestrians its negative outflow invents and its neighbour gets a negative inflow;
+//   * a link that an EARLIER state of the inputs has reached since the histories were last cleared (Model::seed_links): its pedestrians
+//     are still walking when a demand row is zeroed or a turn is closed behind them, and a turn opened in front of them lets them on.
 //   LIVE  the nodes incident to a link of REACH, and the nodes whose own demand row is non-zero
 //   DEAD  the physical links whose head node (the node whose slot owns the link as its incoming link) is not in LIVE -- then no link at
 //         that node, in either direction, is in REACH -- narrowed to whole nodes all of whose corridors the lean kernel can step
@@ -49,6 +55,7 @@ struct Model {
   // eligibility of a corridor for the lean kernel
   const int32_t *link_sep = nullptr, *link_tau_sw = nullptr;
   const double *front_u = nullptr, *back_u = nullptr;   // [links] the gate every replica shares, NaN: per-replica
+  const char* seed_links = nullptr;    // [links] links that may hold pedestrians already: REACH of the earlier proofs since the last full reset (nullptr: none)
   const char* link_rl = nullptr;       // [links] an RL action slot or a controller drives the link's gate (nullptr: none)
   bool per_replica_params = false;     // per-replica link parameters are in use (DevView.pr)
 };
@@ -74,6 +81,8 @@ static inline bool turn_possible(const Model& m, int n, int i, int j) {
 }
 
 static inline bool gate_ok(double g) { return g == g && g >= 0.0 && g < __builtin_inf(); }
+// a front gate that is, or in some replica may be, below zero: the link sends a negative flow (send_flow: min(gate * capacity, ...))
+static inline bool front_may_be_negative(double g) { return !(g >= 0.0); }
 
 // both directions of the corridor whose one direction is l
 static inline bool corridor_eligible(const Model& m, int l) {
@@ -115,6 +124,11 @@ static inline Result partition(const Model& m) {
     for (int k = m.node_slot_ptr[n]; k < m.node_slot_ptr[n + 1]; ++k)
       if (m.slot_in[k] >= L) { out.live[n] = 1; spread(n, k - m.node_slot_ptr[n]); }
   }
+  for (int l = 0; l < L; ++l)
+    if (!out.reach[l] && ((m.seed_links && m.seed_links[l]) || front_may_be_negative(m.front_u[l]))) {
+      out.reach[l] = 1;
+      todo.push_back(l);
+    }
   while (!todo.empty()) {
     const int l = todo.back();
     todo.pop_back();

@@ -112,6 +112,12 @@ def partition(inp):
         if row >= 0 and inp["demand_nz"][row]:
             live.add(n)
             todo += [(n, k - sp[n]) for k in range(sp[n], sp[n + 1]) if inp["slot_in"][k] >= L]
+    # two more kinds of source: a front gate that is, or in some replica may be, negative (the link sends a negative flow however empty
+    # it is), and what an earlier proof has reached since the histories were last cleared (its pedestrians are still walking)
+    for l in range(L):
+        if l not in reach and (l in inp.get("seed_links", ()) or not inp["front_u"][l] >= 0):
+            reach.add(l)
+            todo.append(owner[l])
     while todo:
         n, i = todo.pop()
         for j in range(sp[n + 1] - sp[n]):
@@ -160,6 +166,7 @@ def run_prog(exe, inp, path):
     lines.append(_hex(inp["tf_u"]))
     lines.append(_ints(inp["tab_nz"][:len(inp["tf_u"])]))
     lines += [_ints(inp["link_sep"]), _ints(inp["link_tau_sw"]), _hex(inp["front_u"]), _hex(inp["back_u"]), _ints(inp["link_rl"])]
+    lines.append(_ints([l in inp.get("seed_links", ()) for l in range(inp["n_links"])]))
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
     out = subprocess.run([exe, "model", str(path)], check=True, capture_output=True, text=True).stdout

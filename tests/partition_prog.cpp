@@ -166,9 +166,40 @@ static int selftest() {
       default: n.pr = true; what = "per-replica parameters"; break;
     }
     const Result r = pedn_part::partition(n.model());
+    if (k == 1) {   // a negative front gate makes 1->3 a source: it sends a negative flow through the one-to-one node 3 into 3->4
+      expect("negative front gate reach", r.reach, {0, 2, 4, 6});
+      expect("negative front gate dead", r.dead, {});
+      continue;
+    }
     expect(what, r.dead_raw, {4, 6, 7});
     if (k < 6) { expect(what, r.node_dead, {4}); expect(what, r.dead, {6}); }
     else expect(what, r.dead, {});
+  }
+  {  // a per-replica front gate may be negative somewhere; a negative BACK gate only closes the link (recv_flow clamps at 0)
+    Net n = y();
+    n.tf_u[n.turn(1, 0, 4)] = 0.0;
+    n.back[4] = -1.0;
+    expect("negative back gate", pedn_part::partition(n.model()).dead, {6});
+    n.front[7] = __builtin_nan("");   // 4->3: through node 3 into 3->1, and on from junction 1
+    const Result r = pedn_part::partition(n.model());
+    expect("per-replica front gate reach", r.reach, {0, 1, 2, 5, 7});
+    expect("per-replica front gate dead", r.dead, {});
+  }
+  {  // what an earlier proof has reached stays a source: the branch was open, pedestrians are on 1->3, then the turn into it is closed
+    Net n = y();
+    n.tf_u[n.turn(1, 0, 4)] = 0.0;
+    std::vector<char> seen(n.L, 0);
+    seen[4] = 1;
+    Model m = n.model();
+    m.seed_links = seen.data();
+    const Result r = pedn_part::partition(m);
+    expect("seeded reach", r.reach, {0, 2, 4, 6});
+    expect("seeded dead", r.dead, {});
+    n.demand_nz[0] = 0;   // ... and with the origin's row zeroed as well
+    m = n.model();
+    m.seed_links = seen.data();
+    expect("seeded, no demand: reach", pedn_part::partition(m).reach, {4, 6});
+    expect("seeded, no demand: dead", pedn_part::partition(m).dead, {1, 2});   // 1->0 and 1->2: nodes 0 and 2 see nobody
   }
   if (!failures) printf("selftest ok\n");
   return failures ? 1 : 0;
@@ -192,7 +223,7 @@ static int from_file(const char* path) {
   const auto tab = flags(NT);
   const auto sep = ints(L), tsw = ints(L);
   const auto front = dbls(L), back = dbls(L);
-  const auto rl = flags(L);
+  const auto rl = flags(L), seen = flags(L);
   fclose(f);
   Model m;
   m.n_nodes = N; m.n_links = L;
@@ -201,6 +232,7 @@ static int from_file(const char* path) {
   m.demand_nz = dnz.data(); m.tf_u = tfu.data(); m.tab_nz = tab.data();
   m.link_sep = sep.data(); m.link_tau_sw = tsw.data(); m.front_u = front.data(); m.back_u = back.data(); m.link_rl = rl.data();
   m.per_replica_params = pr != 0;
+  m.seed_links = seen.data();
   const Result r = pedn_part::partition(m);
   printf("reach: %s\nlive: %s\ndead_raw: %s\nnode_dead: %s\ndead: %s\n", ones(r.reach).c_str(), ones(r.live).c_str(), ones(r.dead_raw).c_str(),
          ones(r.node_dead).c_str(), ones(r.dead).c_str());

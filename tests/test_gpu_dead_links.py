@@ -24,11 +24,10 @@ import os
 import numpy as np
 import pytest
 
-import oracle_driver as od
+import dead_link_cases as dl
 import sparse_demand as sd
+from dead_link_cases import KEYS
 from golden_util import ALL_FIELDS
-from pednstream_amd import Network
-from pednstream_amd.flatten import flatten_network
 from sparse_oracle import assert_same_bits
 
 pytestmark = pytest.mark.gpu
@@ -36,10 +35,10 @@ pytestmark = pytest.mark.gpu
 EDGES = [(0, 1), (1, 2), (2, 3), (3, 4), (2, 5), (5, 6), (6, 7), (6, 8), (8, 9), (5, 10), (8, 11)]
 N_NODES, STEPS, SEED = 12, 41, 9
 DEAD_LINKS = 13          # head node in {5 .. 11}
-KEYS = ("PEDN_DEAD_LINKS", "PEDN_STREAMS", "PEDN_STREAM_PROBE", "PEDN_DEAD_STREAMS", "PEDN_DEAD_WAVES")
 
 
-def build(R, dead, history="full", origins=(0,), knobs=None):
+def tree(origins=(0,)):
+    """(adj, params, origins, dests) of the 12-node tree"""
     adj = np.zeros((N_NODES, N_NODES), dtype=int)
     for a, b in EDGES:
         adj[a, b] = adj[b, a] = 1
@@ -47,103 +46,12 @@ def build(R, dead, history="full", origins=(0,), knobs=None):
               "default_link": {"length": 60.0, "width": 3.0, "free_flow_speed": 1.3, "k_critical": 2.0, "k_jam": 6.0, "gamma": 0.01,
                                "speed_noise_std": 0.03, "fd_type": "yperman", "bi_factor": 1.0, "activity_probability": 0.1},
               "links": {}, "demand": {f"origin_{o}": {"pattern": "constant", "peak_lambda": 10.0, "base_lambda": 5.0} for o in origins}}
-    keep = {k: os.environ.get(k) for k in KEYS}
-    os.environ.update({"PEDN_DEAD_LINKS": "1" if dead else "0", "PEDN_STREAMS": "2", "PEDN_STREAM_PROBE": "0"})
-    os.environ.update(knobs or {})          # PEDN_DEAD_STREAMS / PEDN_DEAD_WAVES: how the lean kernel is launched
-    try:
-        np.random.seed(SEED)
-        net = Network(adj, params, origin_nodes=list(origins), destination_nodes=[], verbose=False, n_replicas=R, rng_seed=SEED, history=history)
-        e = net.engine()
-    finally:
-        for k, v in keep.items():
-            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-    assert e.plan_info()["chains"] == 2 and e.plan_info()["link_update_by_next_node_kernel"]
-    return net, e
+    return adj, params, list(origins), []
 
 
-def closed_row(net, node, frm, closed):
-    """the node's m (m - 1) fractions, uniform, but in the row of the link frm -> node the turn into node -> closed is 0.0 and the others
-    share 1.0"""
-    m = flatten_network(net)
-    n = net.nodes[node].index
-    s0, d = int(m["node_slot_ptr"][n]), int(m["node_slot_ptr"][n + 1] - m["node_slot_ptr"][n])
-    tf = np.full(d * (d - 1), 1.0 / (d - 1))
-    i = list(m["slot_in_link"][s0:s0 + d]).index(net.links[(frm, node)].index)
-    j = list(m["slot_out_link"][s0:s0 + d]).index(net.links[(node, closed)].index)
-    tf[i * (d - 1):(i + 1) * (d - 1)] = 1.0 / (d - 2)
-    tf[i * (d - 1) + (j if j < i else j - 1)] = 0.0
-    return n, tf
-
-
-class Pair:
-    """The same network with the plan on and off, and one CPU oracle per sampled replica; every call goes to all of them."""
-
-    def __init__(self, R, history="full", oracle=True, knobs=None):
-        self.R = R
-        self.nets = [build(R, True, history, knobs=knobs), build(R, False, history)]
-        self.on, self.off = self.nets[0][1], self.nets[1][1]
-        net = self.nets[0][0]
-        self.net, self.T = net, int(net.simulation_steps)
-        self.model = flatten_network(net)
-        self.sample = sorted({0, 63, 64, R - 1}) if oracle else []
-        self.oracles = [od.Oracle(self.model, seed=SEED, replica=r) for r in self.sample]
-        self.index = {nid: net.nodes[nid].index for nid in net.nodes}
-
-    def tf(self, node, frm, closed):
-        n, tf = closed_row(self.net, node, frm, closed)
-        for e in (self.on, self.off):
-            e.set_turning_fractions(n, tf)
-        for o in self.oracles:
-            o.set_tf(n, tf)
-
-    def demand(self, node, rows):
-        for e in (self.on, self.off):
-            e.set_demand_matrix(self.index[node], rows)
-        for o, r in zip(self.oracles, self.sample):
-            o.set_demand(self.index[node], rows[r])
-
-    def width(self, which, link, value):
-        for e in (self.on, self.off):
-            e.set_width(which, link, value)
-        for o in self.oracles:
-            o.set_width(which, link, value)
-
-    def run(self, t0, t1):
-        for e in (self.on, self.off):
-            e.run(t0, t1)
-        od.run_many(self.oracles, t0, t1) if self.oracles else None
-
-    def step(self, t):
-        for e in (self.on, self.off):
-            e.step(t)
-        for o in self.oracles:
-            o.step(t)
-
-    def dead(self):
-        assert self.off.plan_info()["dead_links"] == 0
-        return self.on.plan_info()["dead_links"]
-
-    def split_steps(self):
-        """steps that went through the lean kernel since the last reset"""
-        assert self.off.plan_info()["dead_link_steps"] == 0
-        return self.on.plan_info()["dead_link_steps"]
-
-    def check(self, steps, what, oracle=True):
-        fa, fb = self.on.error_flags(), self.off.error_flags()
-        assert fa[0] == fb[0] and fa[1].tobytes() == fb[1].tobytes(), what
-        for fid, name in enumerate(ALL_FIELDS):
-            got, want = self.on.read_block(fid, 0, steps), self.off.read_block(fid, 0, steps)
-            assert_same_bits(got, want, f"{what}: {name} against PEDN_DEAD_LINKS=0", "[t, column, replica]")
-            for o, r in zip(self.oracles if oracle else [], self.sample):
-                assert_same_bits(got[:, :self.on.n_links, r], o.field(name)[:self.on.n_links, :steps].T.astype(got.dtype), f"{what}: {name} of replica {r} against the oracle", "[t, link]")
-        for o, r in zip(self.oracles if oracle else [], self.sample):
-            assert int(fa[1][r]) == o.flags(), (what, r)
-
-    def close(self):
-        for net, _ in self.nets:
-            net.close()
-        for o in self.oracles:
-            o.close()
+def Pair(R, history="full", oracle=True, knobs=None):
+    """dead_link_cases.Pair on the tree: the same network with the plan on and off, and one CPU oracle per sampled replica"""
+    return dl.Pair(tree(), R, SEED, history=history, oracle=oracle, knobs=knobs)
 
 
 def start(R, **kw):
@@ -224,6 +132,26 @@ def test_upload_into_a_zero_row_shrinks_the_set_mid_episode():
     assert left == 5, left         # 6 -> 8, 9 -> 8, 11 -> 8, 8 -> 9, 8 -> 11
     p.run(21, STEPS)
     p.check(STEPS, "demand into node 7 at step 21")
+    p.close()
+
+
+def test_pedestrians_on_their_way_stay_a_source_when_their_origin_is_zeroed():
+    """Found by tests/test_gpu_dead_links_random.py (seed 4481): the origin's row is zeroed in every replica while its pedestrians are
+    between nodes 0 and 2, then the turn 1 -> 2 -> 5 opens in front of them.  A proof that starts from the demand rows alone has no source
+    left and keeps the branch dead; the links reached so far are sources too, and the whole branch goes back to the node kernel."""
+    p = start(320)
+    p.run(1, 21)
+    assert p.dead() == DEAD_LINKS
+    p.set_demand(p.index[0], np.zeros(p.T + 1))
+    assert p.dead() == DEAD_LINKS
+    n = p.index[2]
+    d = int(p.model["node_slot_ptr"][n + 1] - p.model["node_slot_ptr"][n])
+    p.set_tf(n, np.full(d * (d - 1), 1.0 / (d - 1)))
+    assert p.dead() == 0
+    p.run(21, STEPS)
+    p.check(STEPS, "origin zeroed at step 21, then the closed turn opened")
+    branch = p.net.links[(2, 5)].index
+    assert p.on.read_block(0, 21, STEPS, branch, branch + 1).any()          # somebody did turn into the branch
     p.close()
 
 
