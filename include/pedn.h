@@ -484,6 +484,12 @@ int pedn_rollout_compute(pedn_sim* sim, double gamma, double lmbda, int32_t norm
 void* pedn_rollout_device_ptr(pedn_sim* sim, int32_t which);
 int pedn_gae(const float* rewards, const float* values, const float* dones, int32_t T, int32_t lanes, double gamma, double lmbda,
              float* td_target, float* adv, void* stream);
+/* pedn_gae with the next values in an array of their own: values and next_values f32 [T][lanes], td_target[t] = r[t] + (f32(gamma) *
+ * next_values[t]) * (1 - done[t]), everything else (the kernel, the order, the roundings) pedn_gae's; with next_values[t] = values[t + 1]
+ * the results are pedn_gae's bit for bit.  For recurrent critics, whose next_values are a run of their own (pedn_lstm_ppo_evaluate).  No
+ * pointer may be NULL. */
+int pedn_gae_next(const float* rewards, const float* values, const float* next_values, const float* dones, int32_t T, int32_t lanes,
+                  double gamma, double lmbda, float* td_target, float* adv, void* stream);
 
 /* ---- the reference's stacked actors for all envs and agents in one launch (rl/agents/SAC.py:72-107,277-293; PPO_org.py:145-172,470-516) --
  * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 14 (tests/actor_model.py restates it in numpy).
@@ -558,6 +564,43 @@ int pedn_ppo_evaluate(const float* obs, const void* actions, const int32_t* tabl
                       const float* value_params, float* values, float* old_log_probs, float* mu, float* std, int32_t T, int32_t N,
                       int32_t stack_size, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size, int32_t actions_f64,
                       double min_std, double max_std, void* stream);
+
+/* ---- the reference's stateful LSTM PPO agents (rl/agents/PPO_org.py:20-138 LSTMPolicyNetwork / LSTMValueNetwork, :470-516, :543-577) ----
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 17 (tests/lstm_model.py restates it in numpy).  One
+ * nn.LSTM layer of 64 units (hidden_size must be 64, num_layers 1), gate rows i, f, g, o; an agent's input is the single frame's columns
+ * obs0 .. obs0 + obs_w - 1.
+ *   table    the int32 [n_agents][6] table of pedn_actor_forward, with the same guarantees; the offset is the agent's in `params`
+ *   params   f32: per agent lstm.weight_ih_l0 [256][obs_w], lstm.weight_hh_l0 [256][64], lstm.bias_ih_l0 [256], lstm.bias_hh_l0 [256],
+ *            mean_head [act_w][64] + [act_w], std_head the same
+ *   hc       f32 [n_agents][n_envs][2][64], 16-byte aligned: h, then c, of every (agent, env); read and updated in place, one writer per
+ *            (agent, env, unit).  The caller zeroes it once (pedn_lstm_reset)
+ *   obs      f32 [n_envs][n_obs]; low, high, noise, mu, std, eps, raw, actions, state as in pedn_actor_forward
+ * pedn_lstm_actor_forward: one step of every agent's actor for every env: (h, c) <- LSTM(obs, (h, c)), mu = mean_head(relu(h)), std =
+ * softplus(std_head(relu(h))) clamped to [min_std, max_std], then pedn_actor_forward's kind-1 tail (raw, actions, the three modes); the
+ * drawn noise uses site byte 0x74.  One launch on `stream` (NULL = the default stream); no allocation, no synchronisation, no event query,
+ * constant arguments: safe under stream capture, and a captured launch is replayed with the step.
+ * pedn_lstm_reset: h = c = +0.0 for the envs whose mask byte is not 0 (mask u8 [n_envs] on the device, NULL: every env), of every agent:
+ * the reference's reset_buffer().  One launch, capturable like the above. */
+int pedn_lstm_actor_forward(const float* obs, const int32_t* table, const float* low, const float* high, const float* params,
+                            const float* noise, float* hc, float* mu, float* std, float* eps, float* raw, double* actions, int64_t* state,
+                            int32_t n_envs, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size, int32_t num_layers,
+                            int32_t delta_actions, int32_t mode, double max_delta, double min_std, double max_std, uint64_t seed,
+                            uint32_t replica_offset, void* stream);
+int pedn_lstm_reset(float* hc, const uint8_t* mask, int32_t n_envs, int32_t n_agents, int32_t hidden_size, void* stream);
+/* What PPOAgent.update computes under no_grad with the LSTM networks, for every env and agent in ONE launch; each of the three runs
+ * starts from a zero state and steps t inside the kernel:
+ *   obs          f32 [T + 1][N][n_obs] (array 4 of pedn_rollout_device_ptr behind pedn_rollout_finish); actions as in pedn_ppo_evaluate
+ *   value_params f32: per agent lstm.* as above, value_head [1][64] + [1]; value_table int32 [n_agents]: its offsets (multiples of 4)
+ *   values       f32 [T][N][n_agents]: the value LSTM over obs[0 .. T - 1]
+ *   next_values  f32 [T][N][n_agents]: the value LSTM over obs[1 .. T], a run of its own (NOT values[t + 1]: forward_all_steps of the
+ *                next states with hidden = None)
+ *   old_log_probs  f32 [T][N][n_actions]: Normal(mu, std).log_prob(action) of the actor LSTM over obs[0 .. T - 1]; mu, std f32 [T][N][n_actions]
+ *                or NULL: not written
+ * Written for every column some agent owns.  Capturable like the above. */
+int pedn_lstm_ppo_evaluate(const float* obs, const void* actions, const int32_t* table, const int32_t* value_table, const float* actor_params,
+                           const float* value_params, float* values, float* next_values, float* old_log_probs, float* mu, float* std,
+                           int32_t T, int32_t N, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size, int32_t num_layers,
+                           int32_t actions_f64, double min_std, double max_std, void* stream);
 
 /* ---- replay store of the off-policy trainers on the device (rl/rl_utils.py:37-50 ReplayBuffer; rl/agents/SAC.py:127-225) ----------
  * A device-resident ring of transitions of every env that keeps each observation ONCE, filled by ONE launch per policy step, and a

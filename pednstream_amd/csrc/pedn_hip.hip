@@ -22,6 +22,7 @@
 #include "pedn_actor.hpp"
 #include "pedn_sac.hpp"
 #include "pedn_ppo.hpp"
+#include "pedn_lstm.hpp"
 #include "pedn_metrics.hpp"
 
 // The first launch on a stream and the first cross-stream wait cost the runtime ~0.2 ms (queue creation, signal set-up): pay

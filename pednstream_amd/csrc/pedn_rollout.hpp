@@ -70,17 +70,18 @@ __global__ __launch_bounds__(256) void rollout_record_kernel(RolloutView r, cons
   }
 }
 
-struct GaeRows { float r[PEDN_GAE_UNROLL], v[PEDN_GAE_UNROLL], d[PEDN_GAE_UNROLL]; };
+struct GaeRows { float r[PEDN_GAE_UNROLL], v[PEDN_GAE_UNROLL], d[PEDN_GAE_UNROLL], n[PEDN_GAE_UNROLL]; };
 
-// rows t - 1, t - 2, ..., t - PEDN_GAE_UNROLL of one lane
+// rows t - 1, t - 2, ..., t - PEDN_GAE_UNROLL of one lane; nx: the rows' next values where they are an array of their own (pedn_gae_next)
 template <bool DELTA>
-__device__ __forceinline__ void gae_load(GaeRows& b, const float* rew, const float* val, const float* done, int t, size_t L, size_t DL) {
+__device__ __forceinline__ void gae_load(GaeRows& b, const float* rew, const float* val, const float* done, const float* nx, int t, size_t L, size_t DL) {
 #pragma unroll
   for (int j = 0; j < PEDN_GAE_UNROLL; ++j) {
     const size_t row = (size_t)(t - 1 - j);
     b.r[j] = rew[row * L];
     b.v[j] = DELTA ? 0.0f : val[row * L];
     b.d[j] = DELTA ? 0.0f : done[row * DL];
+    b.n[j] = !DELTA && nx ? nx[row * L] : 0.0f;
   }
 }
 
@@ -99,29 +100,31 @@ __device__ __forceinline__ float gae_row(float r, float v, float d, float vnext,
 }
 
 // rew, td, adv [T][lanes]; val [T + 1][lanes]; done [T][lanes / done_div], read at lane / done_div (1: a flag per lane; the store keeps
-// one per env: done_div = n_agents).  DELTA: rew holds td_delta; val, done and td are not touched.
+// one per env: done_div = n_agents).  nx (or null) [T][lanes]: row t's next value is nx[t] instead of val[t + 1], and val has T rows
+// (pedn_gae_next).  DELTA: rew holds td_delta; val, done, nx and td are not touched.
 template <bool DELTA>
-__global__ __launch_bounds__(256) void rollout_gae_kernel(const float* rew, const float* val, const float* done, int T, int lanes, int done_div,
-                                                          float g, float c, float* td, float* adv) {
+__global__ __launch_bounds__(256) void rollout_gae_kernel(const float* rew, const float* val, const float* done, const float* nx, int T, int lanes,
+                                                          int done_div, float g, float c, float* td, float* adv) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= lanes) return;
   const size_t L = (size_t)lanes, DL = (size_t)(lanes / done_div);
   rew += i; adv += i;
   if (!DELTA) { val += i; td += i; done += i / done_div; }
+  if (!DELTA && nx) nx += i;   // (uniform over the launch)
   float carry = 0.0f;
-  float vnext = DELTA ? 0.0f : val[(size_t)T * L];
+  float vnext = DELTA || nx ? 0.0f : val[(size_t)T * L];
   int t = T;
   if (t >= PEDN_GAE_UNROLL) {
     GaeRows cur, nxt;
-    gae_load<DELTA>(cur, rew, val, done, t, L, DL);
+    gae_load<DELTA>(cur, rew, val, done, nx, t, L, DL);
     nxt = cur;
     while (t >= PEDN_GAE_UNROLL) {
       const int tn = t - PEDN_GAE_UNROLL;
-      if (tn >= PEDN_GAE_UNROLL) gae_load<DELTA>(nxt, rew, val, done, tn, L, DL);   // in flight while the chain below runs
+      if (tn >= PEDN_GAE_UNROLL) gae_load<DELTA>(nxt, rew, val, done, nx, tn, L, DL);   // in flight while the chain below runs
 #pragma unroll
       for (int j = 0; j < PEDN_GAE_UNROLL; ++j) {
         const size_t row = (size_t)(t - 1 - j);
-        vnext = gae_row<DELTA>(cur.r[j], cur.v[j], cur.d[j], vnext, g, c, carry, td + row * L, adv + row * L);
+        vnext = gae_row<DELTA>(cur.r[j], cur.v[j], cur.d[j], !DELTA && nx ? cur.n[j] : vnext, g, c, carry, td + row * L, adv + row * L);
       }
       cur = nxt;
       t = tn;
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(256) void rollout_gae_kernel(const float* rew, cons
   }
   for (; t >= 1; --t) {   // the rows that do not fill a block
     const size_t row = (size_t)(t - 1);
-    vnext = gae_row<DELTA>(rew[row * L], DELTA ? 0.0f : val[row * L], DELTA ? 0.0f : done[row * DL], vnext, g, c, carry, td + row * L, adv + row * L);
+    vnext = gae_row<DELTA>(rew[row * L], DELTA ? 0.0f : val[row * L], DELTA ? 0.0f : done[row * DL], !DELTA && nx ? nx[row * L] : vnext, g, c, carry, td + row * L, adv + row * L);
   }
 }
 
@@ -273,12 +276,12 @@ int pedn_rollout_finish(pedn_sim* s, const float* last_values, int32_t* rows, in
   return PEDN_OK;
 }
 
-static void gae_launch(const float* rew, const float* val, const float* done, int T, int lanes, int done_div, double gamma, double lmbda,
+static void gae_launch(const float* rew, const float* val, const float* done, const float* nx, int T, int lanes, int done_div, double gamma, double lmbda,
                        float* td, float* adv, hipStream_t st) {
   const float g = (float)gamma, c = (float)(gamma * lmbda);   // (the product in binary64, rounded once)
   const dim3 grid((unsigned)((lanes + 255) / 256));
-  if (val) hipLaunchKernelGGL(rollout_gae_kernel<false>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
-  else hipLaunchKernelGGL(rollout_gae_kernel<true>, grid, dim3(256), 0, st, rew, val, done, T, lanes, done_div, g, c, td, adv);
+  if (val) hipLaunchKernelGGL(rollout_gae_kernel<false>, grid, dim3(256), 0, st, rew, val, done, nx, T, lanes, done_div, g, c, td, adv);
+  else hipLaunchKernelGGL(rollout_gae_kernel<true>, grid, dim3(256), 0, st, rew, val, done, nx, T, lanes, done_div, g, c, td, adv);
 }
 
 int pedn_rollout_compute(pedn_sim* s, double gamma, double lmbda, int32_t normalize) {
@@ -289,7 +292,7 @@ int pedn_rollout_compute(pedn_sim* s, double gamma, double lmbda, int32_t normal
   if (T < 1) return fail(s, PEDN_E_ARG, "the store is empty");
   if (normalize && (int64_t)T * r.N < 2) return fail(s, PEDN_E_ARG, "advantage normalisation needs at least two entries per agent");
   HIP_TRY(s, hipSetDevice(s->device));
-  gae_launch(r.rewards, r.values, r.done, T, r.N * r.A, r.A, gamma, lmbda, r.td_target, r.adv, s->stream);
+  gae_launch(r.rewards, r.values, r.done, nullptr, T, r.N * r.A, r.A, gamma, lmbda, r.td_target, r.adv, s->stream);
   if (normalize) {
     const dim3 grid((unsigned)((r.A + PEDN_NORM_COLS - 1) / PEDN_NORM_COLS), (unsigned)T);
     for (int pass = 0; pass < 3; ++pass)   // (a launch per pass: each needs every workgroup's row sums of the one before)
@@ -321,7 +324,16 @@ int pedn_gae(const float* rewards, const float* values, const float* dones, int3
              float* td_target, float* adv, void* stream) {
   if (!rewards || !adv || (values && (!dones || !td_target))) return fail(nullptr, PEDN_E_ARG, "null argument");
   if (T < 1 || lanes < 1) return fail(nullptr, PEDN_E_ARG, "T and lanes must be positive");
-  gae_launch(rewards, values, dones, T, lanes, 1, gamma, lmbda, td_target, adv, (hipStream_t)stream);
+  gae_launch(rewards, values, dones, nullptr, T, lanes, 1, gamma, lmbda, td_target, adv, (hipStream_t)stream);
+  HIP_TRY(nullptr, hipGetLastError());
+  return PEDN_OK;
+}
+
+int pedn_gae_next(const float* rewards, const float* values, const float* next_values, const float* dones, int32_t T, int32_t lanes,
+                  double gamma, double lmbda, float* td_target, float* adv, void* stream) {
+  if (!rewards || !values || !next_values || !dones || !td_target || !adv) return fail(nullptr, PEDN_E_ARG, "null argument");
+  if (T < 1 || lanes < 1) return fail(nullptr, PEDN_E_ARG, "T and lanes must be positive");
+  gae_launch(rewards, values, dones, next_values, T, lanes, 1, gamma, lmbda, td_target, adv, (hipStream_t)stream);
   HIP_TRY(nullptr, hipGetLastError());
   return PEDN_OK;
 }

@@ -715,6 +715,22 @@ class VecPedNetEnv:
 
         return for_env(self, actors)
 
+    def lstm_actors(self, delta_actions=True, max_delta=2.5, min_std=1e-3, max_std=10.0, seed=0, hidden_size=64, num_layers=1):
+        """The reference's stateful LSTM actors (its default PPO configuration) of every agent of this env, one step for all envs in ONE
+        launch with the recurrent state kept on the device (``pednstream_amd.lstm.LstmActors``).  ``lambda obs: actors.act(obs)`` is a
+        ``policy_fn`` of ``capture``; ``actors.reset_hidden()`` belongs beside ``env.reset()``."""
+        from .lstm import for_env
+
+        return for_env(self, delta_actions, max_delta, min_std, max_std, seed, hidden_size, num_layers)
+
+    def lstm_ppo_targets(self, actors):
+        """The gradient-free half of the reference's ``PPOAgent.update`` with the LSTM networks (``pednstream_amd.lstm.LstmPpoTargets``):
+        ``evaluate_store(rollout_store)`` returns ``values``, ``next_values`` and ``old_log_probs`` of a finished fill in ONE launch,
+        ``compute_gae`` the TD targets and advantages from them.  ``actors``: this env's ``lstm_actors()``."""
+        from .lstm import targets_for_env
+
+        return targets_for_env(self, actors)
+
     def _ordered_behind_engine(self):
         """The caller's current torch stream waits (on the device) for everything enqueued on the engine's stream so far."""
         import torch
@@ -1050,6 +1066,14 @@ class MultiScenarioVecEnv:
     def ppo_targets(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv steps separate engines: PPO targets belong to one VecPedNetEnv (one per group: "
                          "env.groups[i].ppo_targets(...))")
+
+    def lstm_actors(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv steps separate engines: LSTM actors belong to one VecPedNetEnv (one per group: "
+                         "env.groups[i].lstm_actors(...))")
+
+    def lstm_ppo_targets(self, *a, **k):
+        raise ValueError("MultiScenarioVecEnv steps separate engines: LSTM PPO targets belong to one VecPedNetEnv (one per group: "
+                         "env.groups[i].lstm_ppo_targets(...))")
 
     def set_running_norm(self, *a, **k):
         raise ValueError("MultiScenarioVecEnv does not run the running normalisation: its groups are separate engines with statistics of "

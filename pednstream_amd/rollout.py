@@ -173,24 +173,36 @@ class RolloutStore:
         self._full = None
 
 
-def _gae_call(rew, val, done, T, lanes, gamma, lmbda, td, adv, stream_ptr):
+def _gae_call(rew, val, done, T, lanes, gamma, lmbda, td, adv, stream_ptr, nxt=None):
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    rc = _engine.lib().pedn_gae(p(rew), p(val), p(done), int(T), int(lanes), float(gamma), float(lmbda), p(td), p(adv),
-                                C.c_void_p(int(stream_ptr)) if stream_ptr else None)
+    lib, st = _engine.lib(), C.c_void_p(int(stream_ptr)) if stream_ptr else None
+    if nxt is None:
+        name, rc = "pedn_gae", lib.pedn_gae(p(rew), p(val), p(done), int(T), int(lanes), float(gamma), float(lmbda), p(td), p(adv), st)
+    else:
+        name, rc = "pedn_gae_next", lib.pedn_gae_next(p(rew), p(val), p(nxt), p(done), int(T), int(lanes), float(gamma), float(lmbda), p(td), p(adv), st)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"pedn_gae failed ({rc}): {_engine.lib().pedn_last_error(None).decode()}")
+        raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed ({rc}): {lib.pedn_last_error(None).decode()}")
 
 
-def gae(rewards, values, dones, gamma, lmbda):
+def gae(rewards, values, dones, gamma, lmbda, next_values=None):
     """(advantages, td_target) of shape ``rewards.shape``: ``rewards`` and ``dones`` are float32 CUDA tensors [T, ...], ``values``
-    [T + 1, ...] (row t = V(s_t), row T the bootstrap value); every trailing index is a trajectory of its own.  One launch on the
-    current torch stream, no host synchronisation."""
+    [T + 1, ...] (row t = V(s_t), row T the bootstrap value); every trailing index is a trajectory of its own.  With ``next_values``
+    [T, ...] (recurrent critics, whose next values are a run of their own: ``pednstream_amd.lstm``) row t's next value is
+    ``next_values[t]`` and ``values`` is [T, ...].  One launch on the current torch stream, no host synchronisation."""
     import torch
 
     ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
-    if not (ok(rewards) and ok(values) and ok(dones)):
+    if not (ok(rewards) and ok(values) and ok(dones)) or (next_values is not None and not ok(next_values)):
         raise ValueError("rewards, values and dones must be float32 CUDA tensors")
-    if rewards.dim() < 1 or rewards.shape[0] < 1 or tuple(dones.shape) != tuple(rewards.shape) or \
+    if next_values is not None:
+        if rewards.dim() < 1 or rewards.shape[0] < 1 or rewards[0].numel() < 1 or \
+                not (tuple(dones.shape) == tuple(values.shape) == tuple(next_values.shape) == tuple(rewards.shape)):
+            raise ValueError(f"expected rewards / dones / values / next_values [T, ...], got {tuple(rewards.shape)}, {tuple(dones.shape)}, "
+                             f"{tuple(values.shape)}, {tuple(next_values.shape)}")
+        if next_values.device != rewards.device:
+            raise ValueError("rewards, values, next_values and dones must be on one device")
+        next_values = next_values.contiguous()
+    elif rewards.dim() < 1 or rewards.shape[0] < 1 or tuple(dones.shape) != tuple(rewards.shape) or \
             tuple(values.shape) != (rewards.shape[0] + 1,) + tuple(rewards.shape[1:]) or rewards[0].numel() < 1:
         raise ValueError(f"expected rewards / dones [T, ...] and values [T + 1, ...], got {tuple(rewards.shape)}, {tuple(dones.shape)}, "
                          f"{tuple(values.shape)}")
@@ -200,7 +212,7 @@ def gae(rewards, values, dones, gamma, lmbda):
     T, lanes = rewards.shape[0], rewards[0].numel()
     with torch.cuda.device(rewards.device):
         adv, td = torch.empty_like(rewards), torch.empty_like(rewards)
-        _gae_call(rewards, values, dones, T, lanes, gamma, lmbda, td, adv, torch.cuda.current_stream().cuda_stream)
+        _gae_call(rewards, values, dones, T, lanes, gamma, lmbda, td, adv, torch.cuda.current_stream().cuda_stream, next_values)
     return adv, td
 
 
