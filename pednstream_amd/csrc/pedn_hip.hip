@@ -878,6 +878,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
       if (nq / 2 < ((size_t)1 << 31)) {
         TRY(dalloc(s, cap, &s->d_live_rec));
         TRY(dalloc(s, rec.size(), &s->d_dead_rec));
+        TRY(dalloc(s, rec.size(), &s->d_dead_drec));
         TRY(dalloc(s, nq, &s->d_quiet_live));
         HIP_TRY(s, hipMemset(s->d_quiet_live, 0, nq * sizeof(uint32_t)));
       }
@@ -1471,7 +1472,7 @@ static void prewarm_chains(pedn_sim* s) {
     if (s->inline_tf) hipLaunchKernelGGL(node_kernel_for(s, true, true), dim3(1, 1), dim3(s->inline_help ? 1024 : 512), s->node_lds_tf, st, v, 2);
     hipLaunchKernelGGL(link_turn_kernel_for(sel, false, false), dim3(1), dim3(256), 0, st, vl, 1, 0u, 0u, 0u, q, 0);
     hipLaunchKernelGGL(link_kernel_1r_for(sel), dim3(1), dim3(256), 0, st, vl, 1);
-    if (s->stream3) hipLaunchKernelGGL(dead_link_kernel, dim3(1), dim3(256), 0, st, v, 2, (const SlotRec*)s->d_dead_rec, 0);   // (no slot: its waves leave)
+    if (s->stream3) hipLaunchKernelGGL(dead_link_kernel, dim3(1), dim3(256), 0, st, v, 2, (const DeadRec*)s->d_dead_drec, 0);   // (no slot: its waves leave)
   }
   if (s->stream3) {   // the live bins' stream of the dead-link plan
     hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3(1, 1), dim3(512), s->node_lds, s->stream3, v, 2);
@@ -1485,6 +1486,17 @@ static void prewarm_chains(pedn_sim* s) {
 // work list) and a second packing of the live nodes alone for node_kernel<LU>.  Between full resets the set only
 // shrinks (dl_grow), and the proof's sources only grow (dl_src, dl_reach).  A live slot whose corridor's other end is a dead slot mirrors ITSELF: its own quiet word fills its inbox -- the
 // dead end writes +0.0 only, has no separator and a shock-wave look-back >= 1 (eligibility), which is all the inbox vouches for.
+// The lean waves' records (DeadRec) from the slots' SlotRec copies and the shared gates as they stand on the device now: one launch of
+// dead_prep_kernel on the engine's stream, behind every setter's launch and in front of the fork of the next split range.  Every run of
+// dl_refresh ends here, whether the set of dead nodes changed or not: a shared gate set to another valid width leaves the set as it is.
+static int dl_prep(pedn_sim* s) {
+  if (s->n_dead_pos <= 0) return PEDN_OK;
+  hipLaunchKernelGGL(dead_prep_kernel, dim3((unsigned)((s->n_dead_pos + 63) / 64)), dim3(64), 0, s->stream, s->v, (const SlotRec*)s->d_dead_rec,
+                     s->d_dead_drec, s->n_dead_pos);
+  HIP_TRY(s, hipGetLastError());
+  return PEDN_OK;
+}
+
 static int dl_refresh(pedn_sim* s) {
   s->dl_dirty = false;
   if (!s->d_live_rec) return PEDN_OK;
@@ -1504,6 +1516,11 @@ static int dl_refresh(pedn_sim* s) {
   } else {
     for (size_t i = 0; i < s->dl_src.size(); ++i) s->dl_src[i] |= s->h_demand_nz[i];
   }
+  // A link whose free_flow_tau is 0 is a source of its own: its sending flow of step 1 is smoothed against entry -1 of the history, the
+  // untouched tail's -1.0 (link.py:364: floor(0.8 * 0 + 0.2 * -1) = -1 on an empty link), the node hands the negative flow on, and the
+  // pedestrians it invents walk on from there (tests/test_gpu_dead_record.py: the oracle of such a link).  A seed of every proof.
+  for (const SlotRec& R : s->h_slot_rec)
+    if (R.node >= 0 && R.lin < L && R.Pin.fft < 1) s->dl_reach[R.lin] = 1;
   pm.demand_nz = s->dl_src.data(); pm.tf_u = s->h_tf_u.data(); pm.tab_nz = tab.data();
   pm.seed_links = s->dl_reach.data();
   pm.link_sep = s->h_link_sep.data(); pm.link_tau_sw = s->h_link_tau_sw.data();
@@ -1516,7 +1533,14 @@ static int dl_refresh(pedn_sim* s) {
   if (!s->dl_grow && s->dl_node.size() == dead.size())
     for (int n = 0; n < N; ++n) dead[n] = dead[n] && s->dl_node[n];
   else if (!s->dl_grow) dead.assign(N, 0);
-  if (dead == s->dl_node) return PEDN_OK;
+  // the lean waves take both gates of a slot from the replica-uniform shortcuts: a node with a slot whose gates are not shared stays with
+  // the node kernel (the proof's eligibility rule says as much for every corridor of a dead node; this is the kernel's own condition)
+  for (int n = 0; n < N; ++n)
+    for (int k = s->h_node_slot_ptr[n]; dead[n] && k < s->h_node_slot_ptr[n + 1]; ++k) {
+      const int lin = s->h_slot_in[k], lout = s->h_slot_out[k];
+      if (lin < L && lout < L && (s->h_front_u[lin] != s->h_front_u[lin] || s->h_back_u[lout] != s->h_back_u[lout])) dead[n] = 0;
+    }
+  if (dead == s->dl_node) return dl_prep(s);
   s->dl_node = dead;
   no_quiet(s);
   // the work list of dead_link_kernel, and the live packing: the full packing's records of the live nodes, first-fit in its order
@@ -1574,7 +1598,7 @@ static int dl_refresh(pedn_sim* s) {
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   HIP_TRY(s, hipMemcpy(s->d_live_rec, rec.data(), rec.size() * sizeof(SlotRec), hipMemcpyHostToDevice));
   if (!pos.empty()) HIP_TRY(s, hipMemcpy(s->d_dead_rec, pos.data(), pos.size() * sizeof(SlotRec), hipMemcpyHostToDevice));
-  return PEDN_OK;
+  return dl_prep(s);
 }
 
 // Does a two-chain range of pedn_run take the split plan now?  Everything the proof and dead_link_kernel do not cover keeps the plan
@@ -1619,7 +1643,7 @@ static void launch_split_step(pedn_sim* s, int t) {
     vd.zg64 = zg64; vd.zg32 = zg32;
     row_bases(vd, t);
     const unsigned waves = (unsigned)s->n_dead_pos * (unsigned)(vd.subRS / 64);
-    if (waves > 0) hipLaunchKernelGGL(dead_link_kernel, dim3((waves + 3) / 4), dim3(256), lds, stream, vd, t, (const SlotRec*)s->d_dead_rec, s->n_dead_pos);
+    if (waves > 0) hipLaunchKernelGGL(dead_link_kernel, dim3((waves + 3) / 4), dim3(256), lds, stream, vd, t, (const DeadRec*)s->d_dead_drec, s->n_dead_pos);
     if (zg64 || zg32) ++s->zgated;
   }
   if (s->n_live_blocks > 0) {

@@ -108,9 +108,10 @@ struct pedn_sim {
   int split_steps = 0;                 // steps launched by launch_split_step since the last reset of either kind (pedn_plan_info info[10])
   size_t node_lds_live = 0;
   SlotRec* d_live_rec = nullptr;       // the live packing's slot records (capacity: the full packing's)
-  SlotRec* d_dead_rec = nullptr;       // the records of the slots dead_link_kernel steps (copies, in work-list order)
-  // The lean kernel is bound by vector instruction issue, and the live launch is a chain of latencies whose waves share the SIMDs with
-  // it: beside 8 lean waves per SIMD the live launch took 20 us, against 12 us alone (profiles/EXPERIMENTS.md #84).
+  SlotRec* d_dead_rec = nullptr;       // the records of the slots dead_link_kernel steps (copies, in work-list order): dead_prep_kernel's input
+  DeadRec* d_dead_drec = nullptr;      // ... and what the lean waves read: their slot-uniform results (dead_prep_kernel, launched by dl_refresh)
+  // The live launch is a chain of latencies whose waves share the CUs with the lean kernel's: beside 8 lean waves per SIMD it took 20 us,
+  // against 12 us alone (profiles/EXPERIMENTS.md #84; what the lean waves take from it is cache more than issue slots, #85).
   // dead_waves = workgroups of four waves per CU = waves per SIMD the lean kernel may hold (PEDN_DEAD_WAVES=3..8; 8: no limit), through
   // dynamic LDS that it does not use (dead_lds_bytes in pedn_hip.hip: the size leaves the rest of the CU's LDS to the live workgroups).
   int dead_waves = 5;

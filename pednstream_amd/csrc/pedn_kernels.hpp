@@ -211,6 +211,18 @@ __device__ __forceinline__ double recv_reverse_peds(const DevView& v, const Link
   RngKey key{v.k0, v.k1, v.replica_offset + (uint32_t)r, (uint32_t)l, (uint32_t)tp, 2u};
   return rng_binomial((long long)nrev, 0.9, key, v.meanfield);
 }
+// the two per-replica ends of cal_receiving_flow, shared with dead_link_kernel (which gets the bound in front of them from its record)
+__device__ __forceinline__ double recv_smooth(double rr, double r_prev) {
+  if (r_prev >= 0.0) {  // link.py:400-401
+    double sm = floor(rr * 0.8 + r_prev * 0.2);
+    rr = sm < rr ? sm : rr;
+  }
+  return rr;
+}
+__device__ __forceinline__ double recv_minus_reverse(double rr, double s_rev) {
+  rr = rr - s_rev;  // link.py:415-416
+  return rr > 0.0 ? rr : 0.0;
+}
 __device__ double recv_flow(const DevView& v, const LinkP& P, int l, int tp, int r, const SlotIn& x, double s_rev, double rp, uint32_t& fl) {
   double kjA = P.sep ? P.kj * (P.length * x.sepw_out) : P.kjA;
   int tsw = P.tau_sw;
@@ -232,13 +244,9 @@ __device__ double recv_flow(const DevView& v, const LinkP& P, int l, int tp, int
   double rmax = x.back_out * P.kc * P.vf * v.dt;  // link.py:393
   double rr = rmax < b ? rmax : b;
   if (!(rr > 0.0)) rr = 0.0;
-  if (x.r_prev >= 0.0) {  // link.py:400-401
-    double sm = floor(rr * 0.8 + x.r_prev * 0.2);
-    rr = sm < rr ? sm : rr;
-  }
+  rr = recv_smooth(rr, x.r_prev);
   if (P.sep) return rr > 0.0 ? rr : 0.0;
-  rr = rr - s_rev;  // link.py:415-416
-  return rr > 0.0 ? rr : 0.0;
+  return recv_minus_reverse(rr, s_rev);
 }
 
 // BiDirectionalFd.__call__ + the travel-time part of Link.update_speeds for one direction and one replica; pure arithmetic
@@ -246,12 +254,67 @@ struct SpeedOut { float spd, tt, lf, att, rs; };
 
 // the speed noise of (link, step, replica) (functions.py:132-133): depends on no simulation state, so callers draw it while
 // their loads are in flight
-__device__ __forceinline__ double speed_noise(const DevView& v, const LinkP& P, int l, int t, int r) {
-  if (!(P.noise > 0.0) || v.meanfield) return 0.0;
+__device__ __forceinline__ double speed_noise_of(const DevView& v, double noise, int l, int t, int r) {
+  if (!(noise > 0.0) || v.meanfield) return 0.0;
   RngKey key{v.k0, v.k1, v.replica_offset + (uint32_t)r, (uint32_t)l, (uint32_t)t, 3u};
-  return P.noise * rng_z(key);
+  return noise * rng_z(key);
 }
+__device__ __forceinline__ double speed_noise(const DevView& v, const LinkP& P, int l, int t, int r) { return speed_noise_of(v, P.noise, l, t, r); }
 
+// speed_calc (below) in two parts, for the dead links.  speed_base: the fundamental diagram in front of the noise -- speed_calc's lines from
+// `float ke` to the end of the branch on fd, a function of the link's parameters and the two densities alone (dead_prep_kernel evaluates it
+// once per slot) -- and speed_finish: its lines from `if (P.noise > 0.0)` on, noise, clamp, travel time and the running average
+// (dead_link_kernel, per lane).  COPIES, statement by statement, and to be kept so: with speed_calc itself composed of the two, the
+// compiler schedules link_turn_kernel differently (profiles/dead_record_static.txt), and the other kernels keep their instructions.
+struct SpeedBase {
+  bool is64;  // true: the speed is a Python float (binary64) at this point, false: np.float32
+  double v64;
+  float v32;
+};
+__device__ __forceinline__ SpeedBase speed_base(const LinkP& P, float ks, float ko) {
+  float ke = P.sep ? ks : ks + (float)P.bi * ko;  // functions.py:113
+  bool is64;
+  double v64 = 0.0;
+  float v32 = 0.0f;
+  if (P.fd == 2 && ke <= (float)P.kc) {
+    v32 = (float)P.vf * (1.0f - ke / (float)P.kj);
+    is64 = false;
+  } else if (ke <= (float)P.kc) {
+    v64 = P.vf;
+    is64 = true;
+  } else {
+    if (P.fd == 0) v32 = (float)((P.kc * P.vf) / (P.kj - P.kc)) * ((float)P.kj / ke - 1.0f);
+    else if (P.fd == 1) v32 = ((float)(-P.vf) * (ke - (float)P.kj)) / (float)(P.kj - P.kc);
+    else v32 = (float)(P.vf * P.kc) * (1.0f / ke - (float)(1 / P.kj));
+    is64 = false;
+    if (!(v32 > 0.0f)) { v64 = 0.0; is64 = true; }  // Python max(0, x) returns the int 0
+  }
+  return SpeedBase{is64, v64, v32};
+}
+__device__ __forceinline__ SpeedOut speed_finish(const DevView& v, SpeedBase b, double length, double noise, float tt0, int t, float ks,
+                                                 float rsum_prev, float tt_old, double nz) {
+  bool is64 = b.is64;
+  double v64 = b.v64;
+  float v32 = b.v32;
+  if (noise > 0.0) {  // functions.py:132-133, nz = speed_noise(...)
+    if (is64) v64 = v64 + nz;
+    else v32 = v32 + (float)nz;
+  }
+  if (is64) { if (!(v64 > 0.0)) v64 = 0.0; }
+  else if (!(v32 > 0.0f)) { v64 = 0.0; is64 = true; }
+  SpeedOut o;
+  o.spd = is64 ? (float)v64 : v32;
+  if (is64) o.tt = v64 > 0.0 ? (float)(length / v64) : (float)(length / 0.05);  // link.py:177
+  else o.tt = (float)length / v32;
+  o.lf = ks * o.spd;               // link.py:181
+  o.rs = rsum_prev + o.tt;         // link.py:183-186, float32 running sum
+  o.att = tt0;
+  if (t >= v.W) {
+    o.rs = o.rs - tt_old;
+    o.att = o.rs / (float)v.W;
+  }
+  return o;
+}
 __device__ __forceinline__ SpeedOut speed_calc(const DevView& v, const LinkP& P, int l, int t, int r, float ks, float ko,
                                                float rsum_prev, float tt_old, double nz) {
   float ke = P.sep ? ks : ks + (float)P.bi * ko;  // functions.py:113
@@ -1229,71 +1292,126 @@ __global__ __launch_bounds__(1024) void node_kernel_h(DevView v, int t) {
 // Dead links (pedn_run's split plan, pedn_hip.hip: launch_split_step; the proof: pedn_partition.hpp): one wave per (slot of a node
 // that no pedestrian can reach, 64 replicas), replica group fastest.  The wave does for its slot what the slot wave of node_kernel<LU>(t)
 // does -- the link update of t - 1 for the incoming link, the sending flow of that link and the receiving flow of the outgoing one,
-// Node.update_links -- with every input that the proof fixes given as the literal +0.0 to the SAME device functions: inflow / outflow /
-// the cumulative counts / num_pedestrians / sending_flow of both directions at every row, and the node's flows qo = qi = +0.0 (zero
-// sending flows times any fraction floor and clamp to +0.0 in the classic rule, min(0, r >= 0) = +0.0 at a one-to-one node).  What is
-// left to load: the running sum, travel_time[t - 1 - W] and receiving_flow[t - 2].  No LDS, no barrier, no quiet words (the slots of the
-// live bins next to it mirror themselves, SlotRec.mirror).  Stores, the gate-record rule, the zero-elision gates (a store is skipped
-// only under zg64 / zg32: every value they cover is +0.0 here) and the error flags are node_step's.  Full-record mode, shared link
-// parameters, classic node model, t >= 2 (the host offers nothing else).  rec: the slots' records, a copy in work-list order (no index
-// between the wave and its record).
-__global__ __launch_bounds__(256, 8) void dead_link_kernel(DevView v, int t, const SlotRec* __restrict__ rec, int n_rec) {
+// Node.update_links -- with every input that the proof fixes at +0.0: inflow / outflow / the cumulative counts / num_pedestrians /
+// sending_flow of both directions at every row, and the node's flows qo = qi = +0.0 (zero sending flows times any fraction floor and
+// clamp to +0.0 in the classic rule, min(0, r >= 0) = +0.0 at a one-to-one node).
+// Everything of that step whose operands are such a +0.0, a field of the slot's record, a shared gate (the proof admits no other:
+// corridor_eligible, dl_refresh) or a launch constant is the same in every lane, replica group and step: dead_prep_kernel evaluates it once
+// per slot -- through speed_base, send_flow and recv_flow themselves, in this translation unit -- into the slot's DeadRec, whenever an input
+// of the proof changes (dl_refresh).  The wave here fetches that record in one scalar burst, loads the running sum, travel_time[t - 1 - W]
+// and receiving_flow[t - 2], draws the speed noise under them, and does what depends on the lane: speed_finish, the same-step flag of
+// send_flow's look-back, the smoothing of the receiving flow (recv_smooth, recv_minus_reverse).  The three time switches (t' >= W,
+// t' >= fft, t' + 1 - tau_sw < 0) choose between record fields.  No LDS, no barrier, no quiet words (the slots of the live bins next to
+// it mirror themselves, SlotRec.mirror).  Stores, the gate-record rule, the zero-elision gates (a store is skipped only under zg64 / zg32:
+// every value they cover is +0.0 here) and the error flags are node_step's.  Full-record mode, shared link parameters and gates, classic
+// node model, t >= 2 (the host offers nothing else).  rec: the slots' records in work-list order (no index between the wave and its record).
+// History rows of the dead links stream through the lean kernel: 45 MB per step on melbourne x 1024, each element written once and read
+// again W steps later (travel_time), two launches later (receiving_flow) or never.  Left to the default policy they displace what the live
+// launch next to it keeps in the L2 -- a chain of dependent loads, which sets the step time: with the shorter wave of the record the same
+// bytes arrive in less time and the live launch went from 15.9 to 17.0 us (profiles/dead_record_kernel_stats.txt).  Nontemporal accesses
+// for every history row; the running sum, read and written by the same slot every step, stays cached.
+template <typename T> __device__ __forceinline__ void stream_st(T* p, T x) { __builtin_nontemporal_store(x, p); }
+template <typename T> __device__ __forceinline__ T stream_ld(const T* p) { return __builtin_nontemporal_load(p); }
+__global__ __launch_bounds__(256, 8) void dead_link_kernel(DevView v, int t, const DeadRec* __restrict__ rec, int n_rec) {
   const unsigned rgroups = (unsigned)(v.subRS >> 6);
   const unsigned w = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const unsigned idx = w / rgroups;
   if (idx >= (unsigned)n_rec) return;   // wave-uniform
+  const DeadRec D = rec[idx];           // the whole record, in front of the branch: one burst
   const int lane = (int)(threadIdx.x & 63);
   const int RS = v.RS, L = v.L;
   const int r0 = v.sub0 + (int)(w % rgroups) * 64, r = r0 + lane, tp = t - 1;
-  const SlotRec& W = rec[idx];
-  const int lin = W.lin, lout = W.lout;
+  const int lin = D.lin, lout = D.lout;
   const uint32_t oin = (uint32_t)lin * (uint32_t)RS + (uint32_t)r0, oout = (uint32_t)lout * (uint32_t)RS + (uint32_t)r0;
 #define DROW(T, K, OFF) (reinterpret_cast<T*>(v.rb[K]) + (OFF))
   if (lin < L) {
     uint32_t fl = 0;
-    const LinkP& Pin = W.Pin;
-    const LinkP& Pout = W.Pout;
     const bool lu_win = tp >= v.W;
     const float lu_rs = v.rsum[(size_t)lin * RS + r];
-    const float lu_old = lu_win ? DROW(float, RB_TT_W, oin)[lane] : 0.0f;
-    SlotIn x{};   // every field +0.0: what the proof fixes
-    x.r_prev = DROW(double, RB_R_Q, oout)[lane];
-    const double fu = v.front_u[lin], bu = v.back_u[lout];
-    x.front_in = fu == fu ? fu : (v.front + oin)[lane];
-    x.back_out = bu == bu ? bu : (v.back + oout)[lane];
+    const float lu_old = lu_win ? stream_ld(&DROW(float, RB_TT_W, oin)[lane]) : 0.0f;
+    const double r_prev = stream_ld(&DROW(double, RB_R_Q, oout)[lane]);
     // Network.update_link_states(t') for the incoming link, as in node_step<LU>
-    const double nz = speed_noise(v, Pin, lin, tp, r);
-    const float na = 0.0f, nb = 0.0f;   // (float)(num_pedestrians[t' - 1] + (inflow[t'] - outflow[t'])) of +0.0 each
-    const float ka = na / Pin.area32, kb = nb / Pout.area32;
-    if (!(v.zg32 && __all((__float_as_int(na) | __float_as_int(ka)) == 0))) {
-      DROW(float, RB_N_P, oin)[lane] = na;
-      DROW(float, RB_K_P, oin)[lane] = ka;
+    const double nz = speed_noise_of(v, D.noise, lin, tp, r);
+    const float na = 0.0f, ka = D.ka;   // (float)(num_pedestrians[t' - 1] + (inflow[t'] - outflow[t'])) of +0.0 each, and na / area
+    if (!(v.zg32 && (__float_as_int(na) | __float_as_int(ka)) == 0)) {   // (the same in all 64 lanes: no vote)
+      stream_st(&DROW(float, RB_N_P, oin)[lane], na);
+      stream_st(&DROW(float, RB_K_P, oin)[lane], ka);
     }
-    const SpeedOut so = speed_calc(v, Pin, lin, tp, r, ka, kb, lu_rs, lu_old, nz);
-    DROW(float, RB_V_P, oin)[lane] = so.spd;
-    DROW(float, RB_TT_P, oin)[lane] = so.tt;
-    if (!(v.zg32 && __all(__float_as_int(so.lf) == 0))) DROW(float, RB_LF_P, oin)[lane] = so.lf;
-    if (lu_win) DROW(float, RB_ATT_P, oin)[lane] = so.att;
+    const SpeedOut so = speed_finish(v, SpeedBase{(D.bits & DEAD_IS64) != 0, D.v64, D.v32}, D.length, D.noise, D.tt0, tp, ka, lu_rs, lu_old, nz);
+    stream_st(&DROW(float, RB_V_P, oin)[lane], so.spd);
+    stream_st(&DROW(float, RB_TT_P, oin)[lane], so.tt);
+    if (!(v.zg32 && __all(__float_as_int(so.lf) == 0))) stream_st(&DROW(float, RB_LF_P, oin)[lane], so.lf);
+    if (lu_win) stream_st(&DROW(float, RB_ATT_P, oin)[lane], so.att);
     v.rsum[(size_t)lin * RS + r] = so.rs;
-    if (x.back_out != Pout.width || v.hist) DROW(double, RB_GATE_P, oout)[lane] = x.back_out;
-    x.n_in = na; x.n_out = nb; x.k_in = ka; x.att_in = so.att;
-    const double rp = recv_reverse_peds(v, Pout, lout, tp, r, x, fl);
-    const double s_i = tp < Pin.fft ? 0.0 : send_flow<false, true>(v, Pin, lin, tp, r, x, 0.0, v.valid_hi, fl, (uint32_t)lin * (uint32_t)RS);
-    DROW(double, RB_S_P, oin)[lane] = s_i;
-    if (s_i < 0.0) fl |= PEDN_F_NEG_FLOW;
-    const double r_i = recv_flow(v, Pout, lout, tp, r, x, s_i, rp, fl);
-    DROW(double, RB_R_P, oout)[lane] = r_i;
-    if (s_i < 0.0 || r_i < 0.0) fl |= PEDN_F_NEG_FLOW;
+    if ((D.bits & DEAD_GATE_REC) != 0 || v.hist) stream_st(&DROW(double, RB_GATE_P, oout)[lane], D.gate);
+    double s_i = 0.0;
+    if (tp >= D.fft) {
+      const int tau = __float2int_rn(so.att / (float)v.dt);  // link.py:260: send_flow's look-back, here for its flag alone
+      if (tau <= 0) fl |= PEDN_F_SAME_STEP;
+      s_i = D.send;
+      fl |= D.fl_send;
+    }
+    stream_st(&DROW(double, RB_S_P, oin)[lane], s_i);
+    const bool before_sw = tp + 1 - D.tau_sw < 0;
+    fl |= before_sw ? D.fl_rr0 : D.fl_rr1;
+    const double r_i = recv_minus_reverse(recv_smooth(before_sw ? D.rr0 : D.rr1, r_prev), s_i);
+    stream_st(&DROW(double, RB_R_P, oout)[lane], r_i);
     if (fl) atomicOr(&v.flags[r], fl);
   }
   // Node.update_links with qo = qi = +0.0 on cumulative counts of +0.0 (a virtual pair of such a node: its demand row is +0.0 too)
   if (!v.zg64) {
-    DROW(double, RB_CO_T, oin)[lane] = 0.0;
-    DROW(double, RB_OUT_T, oin)[lane] = 0.0;
-    DROW(double, RB_CI_T, oout)[lane] = 0.0;
-    DROW(double, RB_IN_T, oout)[lane] = 0.0;
+    stream_st(&DROW(double, RB_CO_T, oin)[lane], 0.0);
+    stream_st(&DROW(double, RB_OUT_T, oin)[lane], 0.0);
+    stream_st(&DROW(double, RB_CI_T, oout)[lane], 0.0);
+    stream_st(&DROW(double, RB_IN_T, oout)[lane], 0.0);
   }
 #undef DROW
+}
+
+// The records of dead_link_kernel, one lane per slot: the slot's step on the inputs the proof fixes, as far as it is the same in every
+// lane -- the calls dead_link_kernel made for every lane and step before it had a record, with +0.0 where the proof puts it.  Launched by
+// dl_refresh behind the upload of the slots' SlotRec copies, never inside a step.  v: the engine's own view (shared gates, dt, W).
+__global__ __launch_bounds__(64) void dead_prep_kernel(DevView v, const SlotRec* __restrict__ slot, DeadRec* __restrict__ rec, int n_rec) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n_rec) return;
+  const SlotRec& W = slot[i];
+  DeadRec D{};
+  D.lin = W.lin; D.lout = W.lout;
+  if (W.lin < v.L) {
+    const LinkP& Pin = W.Pin;
+    const LinkP& Pout = W.Pout;
+    const int lin = W.lin, lout = W.lout;
+    SlotIn x{};   // every field +0.0: what the proof fixes
+    x.front_in = v.front_u[lin];   // shared (dl_refresh keeps a slot with a per-replica gate out of the list)
+    x.back_out = v.back_u[lout];
+    const float na = 0.0f, nb = 0.0f;   // (float)(num_pedestrians[t' - 1] + (inflow[t'] - outflow[t'])) of +0.0 each
+    const float ka = na / Pin.area32, kb = nb / Pout.area32;
+    const SpeedBase sb = speed_base(Pin, ka, kb);
+    D.ka = ka; D.kb = kb;
+    D.v64 = sb.v64; D.v32 = sb.v32; D.length = Pin.length; D.noise = Pin.noise; D.tt0 = Pin.tt0;
+    D.fft = Pin.fft; D.tau_sw = Pout.tau_sw;
+    D.gate = x.back_out;
+    D.bits = (sb.is64 ? DEAD_IS64 : 0u) | (x.back_out != Pout.width ? DEAD_GATE_REC : 0u);
+    x.n_in = na; x.n_out = nb; x.k_in = ka;
+    // the sending flow at a step t' >= fft.  Its inputs leave min(smax, bnd) at <= +0.0 or NaN, so neither att_in nor the step or the
+    // replica (the binomials' keys, the diffusion's look-backs) reach the result; the same-step flag of att_in is the wave's own
+    x.att_in = Pin.tt0;
+    uint32_t fls = 0;
+    const double s_i = send_flow<false, true>(v, Pin, lin, Pin.fft, 0, x, 0.0, v.valid_hi, fls, (uint32_t)lin * (uint32_t)v.RS);
+    fls &= ~(uint32_t)PEDN_F_SAME_STEP;
+    if (s_i < 0.0) fls |= PEDN_F_NEG_FLOW;
+    D.send = s_i; D.fl_send = fls;
+    // the receiving bound in front of the smoothing: recv_flow without a previous value (r_prev < 0) and without the reverse sending flow
+    // (rr - 0.0 = rr for the rr >= +0.0 it has there), at a step before the shock-wave look-back (tau_sw >= 1: eligibility) and after it
+    x.r_prev = -1.0;
+    uint32_t fl0 = 0, fl1 = 0;
+    const double rp0 = recv_reverse_peds(v, Pout, lout, -1, 0, x, fl0);
+    D.rr0 = recv_flow(v, Pout, lout, -1, 0, x, 0.0, rp0, fl0);
+    const double rp1 = recv_reverse_peds(v, Pout, lout, 0x3ffffffe, 0, x, fl1);
+    D.rr1 = recv_flow(v, Pout, lout, 0x3ffffffe, 0, x, 0.0, rp1, fl1);
+    D.fl_rr0 = fl0; D.fl_rr1 = fl1;
+  }
+  rec[i] = D;
 }
 
 __device__ __forceinline__ double2 ld2(const double* p, size_t i) { return *reinterpret_cast<const double2*>(p + i); }

@@ -51,6 +51,25 @@ struct SlotRec {  // one wave of node_kernel: a (node, slot) with everything sta
   LinkP Pin, Pout;  // parameters of the incoming / outgoing link of the slot (unused for a virtual pair)
 };
 
+// One wave of dead_link_kernel: what the step of a slot that no pedestrian reaches has left once every operand that is a literal +0.0, a
+// field of the slot's SlotRec, a shared gate or a launch constant has been evaluated -- by dead_prep_kernel, on the device, through the
+// device functions the step itself calls (pedn_kernels.hpp), whenever dl_refresh runs.  One scalar load burst at the top of the wave.
+// A virtual pair (lin >= L) uses lin and lout only.
+enum { DEAD_IS64 = 1u, DEAD_GATE_REC = 2u };
+struct alignas(16) DeadRec {
+  int32_t lin, lout;
+  float ka, kb;               // density[t'] of the incoming link and of its reverse: +0.0 / area
+  double v64, length, noise;  // speed_base of (ka, kb) in its binary64 form (DEAD_IS64), Pin.length, Pin.noise
+  double send;                // sending flow of the incoming link once t' >= fft (send_flow on +0.0 inputs and the shared front gate)
+  double rr0, rr1;            // receiving bound of the outgoing link before smoothing: t' + 1 - tau_sw < 0, otherwise (recv_flow)
+  double gate;                // shared back gate of the outgoing link; DEAD_GATE_REC: it differs from Pout.width (the gate-record rule)
+  float v32, tt0;             // speed_base in its float32 form, Pin.tt0
+  int32_t fft, tau_sw;        // Pin.fft, Pout.tau_sw
+  uint32_t bits;              // DEAD_IS64 | DEAD_GATE_REC
+  uint32_t fl_send, fl_rr0, fl_rr1;   // error flags that send (but for the per-lane same-step flag) / rr0 / rr1 raise
+};
+static_assert(sizeof(DeadRec) <= 128, "DeadRec must stay one short scalar load burst");
+
 struct CorrRec {  // one lane group of link_kernel: both directions of a corridor
   int32_t a, b, pad0, pad1;
   LinkP Pa, Pb;
