@@ -1,5 +1,5 @@
-// pedn_hip.hip -- the core of the host side of the MI355X (gfx950) engine for PedNStream's network_loading hot path: model compilation
-// and plan choice (pedn_create), the setters and reads, the step path (launch_step, pedn_step, pedn_run, rl_step and the clocked step) and
+// pedn_hip.hip -- the core of the host side of the MI355X (gfx950) engine for PedNStream's network_loading hot path: uploads of the compiled model
+// (pedn_compile.hpp) and plan choice (pedn_create), the setters and reads, the step path (launch_step, pedn_step, pedn_run, rl_step and the clocked step) and
 // the agent set (pedn_rl_configure) of the C-ABI of include/pedn.h.  The kernels live in pedn_kernels.hpp, the device data structures in
 // pedn_types.hpp, the bit-exact arithmetic primitives in pedn_math.hpp, the handle and the shared host helpers in pedn_host.hpp.
 // Every training-side feature (controllers, running normalisation, rollout and replay stores, stacked actors, SAC targets, PPO evaluation, evaluation
@@ -15,6 +15,7 @@
 #include "pedn_kernels.hpp"
 #include "pedn_host.hpp"
 #include "pedn_partition.hpp"
+#include "pedn_compile.hpp"
 #include "pedn_ctrl.hpp"
 #include "pedn_norm.hpp"
 #include "pedn_rollout.hpp"
@@ -345,41 +346,16 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
                 int32_t device, pedn_sim** out) {
   if (!m || !out) return fail(nullptr, PEDN_E_ARG, "null argument");
   *out = nullptr;
-  if (m->abi_version != PEDN_ABI_VERSION) return fail(nullptr, PEDN_E_ARG, "pedn_model_desc.abi_version mismatch");
-  if (n_replicas < 1 || m->n_nodes < 1 || m->n_links < 0 || m->T < 2 || m->window < 1)
-    return fail(nullptr, PEDN_E_ARG, "bad sizes in model description");
+  // ---- the model compiler (pedn_compile.hpp): every refusal of the description itself, and the static tables; no device, no handle yet
+  pedn_compile::Tables tab;
+  {
+    std::string err;
+    int rc = pedn_compile::validate(*m, n_replicas, &err);
+    if (rc == PEDN_OK) rc = pedn_compile::compile(*m, pedn_compile::options_from_env(), &tab, &err);
+    if (rc != PEDN_OK) return fail(nullptr, rc, err);
+  }
   const int N = m->n_nodes, L = m->n_links;
   const int n_slots = m->node_slot_ptr[N];
-  // ---- validate topology against what the kernels assume
-  for (int n = 0; n < N; ++n) {
-    int deg = m->node_slot_ptr[n + 1] - m->node_slot_ptr[n];
-    if (deg < 2 || deg > PEDN_MAX_DEGREE)
-      return fail(nullptr, PEDN_E_ARG, "node degree " + std::to_string(deg) + " outside 2.." + std::to_string(PEDN_MAX_DEGREE));
-    if (m->node_kind[n] == 0 && deg != 2) return fail(nullptr, PEDN_E_ARG, "one-to-one node with degree != 2");
-    if (m->node_turn_ptr[n + 1] - m->node_turn_ptr[n] != deg * (deg - 1)) return fail(nullptr, PEDN_E_ARG, "node_turn_ptr inconsistent");
-    for (int k = m->node_slot_ptr[n]; k < m->node_slot_ptr[n + 1]; ++k) {
-      int li = m->slot_in_link[k], lo = m->slot_out_link[k];
-      if (li < 0 || lo < 0 || li >= L + m->n_vlinks || lo >= L + m->n_vlinks) return fail(nullptr, PEDN_E_ARG, "slot link index out of range");
-      if ((li >= L) != (lo >= L)) return fail(nullptr, PEDN_E_ARG, "virtual/physical mismatch in a slot");
-      if (li < L && m->link_rev[li] != lo) return fail(nullptr, PEDN_E_ARG, "slot does not hold a reverse pair");
-      if (li >= L && (m->node_demand_row[n] < 0 || m->node_demand_row[n] >= m->n_demand)) return fail(nullptr, PEDN_E_ARG, "virtual slot without demand row");
-    }
-  }
-  for (int l = 0; l < L; ++l) {
-    int rv = m->link_rev[l];
-    if (rv < 0 || rv >= L || rv == l || m->link_rev[rv] != l) return fail(nullptr, PEDN_E_ARG, "link_rev is not an involution");
-    if (m->link_fd[l] < 0 || m->link_fd[l] > 2) return fail(nullptr, PEDN_E_ARG, "unknown fundamental diagram type");
-  }
-  for (int g = 0; g < m->n_grp; ++g)
-    if (m->grp_ent_ptr[g + 1] - m->grp_ent_ptr[g] > PEDN_MAX_DEGREE - 1) return fail(nullptr, PEDN_E_ARG, "softmax group too large");
-
-  if (m->history_mode != PEDN_HIST_FULL && m->history_mode != PEDN_HIST_RECENT) return fail(nullptr, PEDN_E_ARG, "unknown history_mode");
-  if (m->node_model != PEDN_NODE_CLASSIC && m->node_model != PEDN_NODE_OPTIMAL) return fail(nullptr, PEDN_E_ARG, "unknown node_model");
-  // node_step forms the element offset of a column inside a history row, col * RS + r0, and the elements of a row in 32 bits (rowq / rowd in
-  // pedn_kernels.hpp).  A row of 2^31 elements would be 16 GB of every binary64 field per step: no full-record or ring allocation that fits a
-  // device comes near it, so such a batch is refused here instead of being given a 64-bit path of its own.
-  if (((size_t)L + (size_t)m->n_vlinks) * (((size_t)n_replicas + 127) / 128 * 128) >= ((size_t)1 << 31))
-    return fail(nullptr, PEDN_E_ARG, "links x replicas must stay below 2^31 (one history row)");
 
   HIP_TRY(nullptr, hipSetDevice(device));
   pedn_sim* s = new pedn_sim();
@@ -394,32 +370,11 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
   v.subRS = v.RS;
   v.W = m->window;
   v.dt = m->dt;
-  {  // history rows (DevView.m64 / m32)
-    const int FULL = 0x7fffffff;
-    auto ring = [&](int need) {  // power-of-two ring of at least `need` rows, or all rows when that is no saving
-      int p = 1;
-      while (p < need) p <<= 1;
-      return p >= v.T1 ? FULL : p - 1;
-    };
-    for (int f = 0; f < 7; ++f) v.m64[f] = FULL;
-    for (int g = 0; g < 6; ++g) v.m32[g] = FULL;
-    v.hist = m->history_mode == PEDN_HIST_RECENT;
-    if (v.hist) {
-      int max_sw = 0;
-      for (int l = 0; l < L; ++l) max_sw = std::max(max_sw, m->link_tau_sw[l]);
-      // cumulative_outflow[t' + 1 - tau_shockwave] (link.py:380-390) and [t'], with room for the per-replica scenarios of the
-      // randomisers: free_flow_speed x U(0.6, 0.9) stretches the shock-wave look-back by up to 1 / 0.6 (env_loader.py:410-412; the
-      // k_critical / k_jam factor cancels in the shock-wave speed unless a floor binds -- then pedn_set_link_params /
-      // pedn_randomize_scenarios refuse the scenario)
-      // (a look-back of x.5 before rounding divided by 0.6 can round one further up than max_sw / 0.6: sized for that)
-      v.m64[F_CO] = ring((int)ceil(((double)max_sw + 0.5) / 0.6) + 2);
-      v.m64[F_OUT] = v.m64[F_S] = v.m64[F_R] = v.m64[F_GATE] = ring(4);   // [t], [t-1], [t-2] at most
-      v.m32[G_TT] = ring(v.W + 2);        // travel_time[t - W] leaves the moving average (link.py:183-186)
-      v.m32[G_ATT] = v.m32[G_N] = v.m32[G_K] = v.m32[G_V] = v.m32[G_LF] = ring(4);
-    }
-    for (int f = 0; f < 7; ++f) s->rows64[f] = v.m64[f] == FULL ? v.T1 : v.m64[f] + 1;
-    for (int g = 0; g < 6; ++g) s->rows32[g] = v.m32[g] == FULL ? v.T1 : v.m32[g] + 1;
-  }
+  v.hist = m->history_mode == PEDN_HIST_RECENT;
+  std::copy(tab.m64, tab.m64 + 7, v.m64);
+  std::copy(tab.m32, tab.m32 + 6, v.m32);
+  std::copy(tab.rows64, tab.rows64 + 7, s->rows64);
+  std::copy(tab.rows32, tab.rows32 + 6, s->rows32);
   v.pf_temp = m->pf_temp; v.pf_alpha = m->pf_alpha; v.pf_beta = m->pf_beta; v.pf_omega = m->pf_omega; v.pf_eps = m->pf_eps;
   v.k0 = (uint32_t)seed; v.k1 = (uint32_t)(seed >> 32);
   v.replica_offset = (uint32_t)replica_offset;
@@ -438,9 +393,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     s->h_link_rev.assign(m->link_rev, m->link_rev + L);
     s->h_link_sep.assign(m->link_sep, m->link_sep + L);
     s->h_link_tau_sw.assign(m->link_tau_sw, m->link_tau_sw + L);
-    s->h_demand_nz.assign(std::max(m->n_demand, 1), 0);
-    for (int row = 0; row < m->n_demand; ++row)
-      for (int t = 0; t < m->T + 1 && !s->h_demand_nz[row]; ++t) s->h_demand_nz[row] = pedn_part::not_plus_zero(m->demand[(size_t)row * (m->T + 1) + t]);
+    s->h_demand_nz = std::move(tab.demand_nz);
     if (const char* f = getenv("PEDN_DEAD_LINKS")) s->dead_links = atoi(f) != 0;
     // PEDN_DEAD_WAVES=3..8: waves per SIMD the lean kernel may hold (see pedn_sim.dead_waves); PEDN_DEAD_STREAMS=1|2: its launches per step
     if (const char* f = getenv("PEDN_DEAD_WAVES")) s->dead_waves = std::max(3, std::min(atoi(f), 8));
@@ -480,16 +433,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     }
   }
   // ---- static tables
-  std::vector<LinkP> lp(std::max(L, 1));
-  for (int l = 0; l < L; ++l) {
-    LinkP& P = lp[l];
-    P.length = m->link_length[l]; P.width = m->link_width[l]; P.vf = m->link_vf[l]; P.kc = m->link_kc[l]; P.kj = m->link_kj[l];
-    P.gamma = m->link_gamma[l]; P.act = m->link_act[l]; P.bi = m->link_bi[l]; P.noise = m->link_noise[l];
-    P.tt0 = m->link_tt0[l]; P.rev = m->link_rev[l]; P.sep = m->link_sep[l]; P.fd = m->link_fd[l];
-    P.tau_sw = m->link_tau_sw[l]; P.fft = m->link_fft[l]; P.pad = 0;
-    P.derive();
-  }
-  TRY(upload(s, lp.data(), lp.size(), &v.lp));
+  TRY(upload(s, tab.lp.data(), tab.lp.size(), &v.lp));
   TRY(upload(s, m->node_kind, N, &v.node_kind));
   TRY(upload(s, m->node_slot_ptr, N + 1, &v.node_slot_ptr));
   TRY(upload(s, m->node_turn_ptr, N + 1, &v.node_turn_ptr));
@@ -504,287 +448,40 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
   s->n_pair = m->n_pair;
   s->n_up = m->n_up;
   v.n_pair = m->n_pair;
-  {  // every softmax entry feeds exactly one (turn, od) product: store probabilities in product order
-    std::vector<int32_t> ent_pair(std::max(m->n_ent, 1), -1);
-    for (int q = 0; q < m->n_pair; ++q) {
-      int e = m->pair_ent[q];
-      if (e < 0 || e >= m->n_ent || ent_pair[e] != -1) { pedn_destroy(s); return fail(nullptr, PEDN_E_ARG, "pair_ent is not injective"); }
-      ent_pair[e] = q;
-    }
-    // exp(x)/exp(x) == 1 exactly as long as exp(x) is finite and non-zero; |x| <= temp * (|alpha| + |beta|*k_max/8 + |omega| + |eps|)
-    const double xmax = fabs(m->pf_temp) * (fabs(m->pf_alpha) + fabs(m->pf_beta) * 16.0 + fabs(m->pf_omega) + fabs(m->pf_eps));
-    const bool shortcut = xmax < 600.0;
-    std::vector<int32_t> pconst(std::max(m->n_pair, 1), 0);
-    for (int g = 0; g < m->n_grp; ++g)
-      if (m->grp_ent_ptr[g + 1] - m->grp_ent_ptr[g] == 1 && shortcut && ent_pair[m->grp_ent_ptr[g]] >= 0) pconst[ent_pair[m->grp_ent_ptr[g]]] = 1;
-    s->h_pair_const = pconst;
-    s->h_turn_pair_ptr.assign(m->turn_pair_ptr, m->turn_pair_ptr + m->n_turns + 1);
-    s->h_turn_mode.assign(std::max(m->n_turns, 1), 0);
-    for (int tn = 0; tn < m->n_turns; ++tn) {
-      bool all_const = true;   // a turn without products is the constant 0
-      for (int q = m->turn_pair_ptr[tn]; q < m->turn_pair_ptr[tn + 1]; ++q) all_const = all_const && pconst[q];
-      s->h_turn_mode[tn] = all_const ? 1 : 0;
-    }
-    // row (incoming slot) of its node every softmax group belongs to, read off its products: the product (od, up, down) is
-    // summed into the turn (up, down) (path_finder.py:668-686); a group none of whose entries feeds a product is never needed
-    std::vector<int> grp_row(std::max(m->n_grp, 1), -1);
-    for (int g = 0; g < m->n_grp; ++g) {
-      const int n = m->grp_node[g];
-      if (n < 0 || n >= N || g < m->node_grp_ptr[n] || g >= m->node_grp_ptr[n + 1]) {
-        pedn_destroy(s);
-        return fail(nullptr, PEDN_E_ARG, "grp_node / node_grp_ptr inconsistent");
-      }
-      const int d = m->node_slot_ptr[n + 1] - m->node_slot_ptr[n];
-      for (int e = m->grp_ent_ptr[g]; e < m->grp_ent_ptr[g + 1]; ++e) {
-        if (ent_pair[e] < 0) continue;
-        const int tn = (int)(std::upper_bound(m->turn_pair_ptr, m->turn_pair_ptr + m->n_turns + 1, ent_pair[e]) - m->turn_pair_ptr) - 1;
-        const int row = (tn - m->node_turn_ptr[n]) / (d - 1);
-        if (tn < m->node_turn_ptr[n] || tn >= m->node_turn_ptr[n + 1] || (grp_row[g] >= 0 && grp_row[g] != row)) {
-          pedn_destroy(s);
-          return fail(nullptr, PEDN_E_ARG, "products of one softmax group lie in different rows");
-        }
-        grp_row[g] = row;
-      }
-    }
-    // Rows (incoming slots) of dynamic nodes.  A row whose turns are all mode 1 (every product constant) has fractions that
-    // depend on the OD weights only: tabulated and renormalised on the host (tabulate_pair_pod), SlotRec.dyn = 2.  The others
-    // get one record each for turn_frac_kernel -- see pedn_types.hpp for the word layout -- and SlotRec.dyn = 1.
-    struct Row { int node, i, cost, need, groups; };
-    std::vector<Row> rows;
-    s->h_slot_dyn.assign(n_slots, 0);
-    for (int n = 0; n < N; ++n) {
-      if (m->node_kind[n] != 1 || !m->node_dyn[n]) continue;
-      const int d = m->node_slot_ptr[n + 1] - m->node_slot_ptr[n];
-      for (int i = 0; i < d; ++i) {
-        const int ta = m->node_turn_ptr[n] + i * (d - 1), tb = ta + d - 1;
-        int need = 0;
-        for (int q = m->turn_pair_ptr[ta]; q < m->turn_pair_ptr[tb]; ++q) need += pconst[q] ? 0 : 1;
-        s->h_slot_dyn[m->node_slot_ptr[n] + i] = need ? 1 : 2;
-        if (!need) continue;
-        int cost = m->turn_pair_ptr[tb] - m->turn_pair_ptr[ta], groups = 0;
-        for (int g = m->node_grp_ptr[n]; g < m->node_grp_ptr[n + 1]; ++g)
-          if (grp_row[g] == i && (m->grp_ent_ptr[g + 1] - m->grp_ent_ptr[g] > 1 || !shortcut)) ++groups;
-        cost += 16 * groups;  // a group costs two divisions and an exp per downstream
-        rows.push_back(Row{n, i, cost, need, groups});
-      }
-    }
-    // workgroups of four rows, heaviest first (they start first); the rows of a workgroup share its PEDN_TF_LDS_ROWS LDS rows
-    std::stable_sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) { return a.cost > b.cost; });
-    std::vector<Row> packed;
-    std::vector<int> lds_base;
-    const int coop_groups = PEDN_TF_COOP_GROUPS;  // rows with more multi-entry groups get a workgroup of their own (2..12 measured: 8 best)
-    int lds_limit = PEDN_TF_LDS_ROWS;  // diagnostics: PEDN_TF_LDS_LIMIT=n gives a row at most n LDS rows (the rest goes to ent_p)
-    if (const char* d = getenv("PEDN_TF_LDS_LIMIT")) lds_limit = std::max(0, std::min(atoi(d), PEDN_TF_LDS_ROWS));
-    {
-      std::vector<char> taken(rows.size(), 0);
-      for (size_t a0 = 0; a0 < rows.size(); ++a0) {
-        if (taken[a0]) continue;
-        if (rows[a0].groups > coop_groups) {  // a workgroup of its own: four records of the same row (coop)
-          taken[a0] = 1;
-          for (int k = 0; k < 4; ++k) { packed.push_back(rows[a0]); lds_base.push_back(0); }
-          continue;
-        }
-        int fill = 0, cnt = 0;
-        for (size_t k = a0; k < rows.size() && cnt < 4; ++k) {
-          if (taken[k] || rows[k].groups > coop_groups) continue;
-          const int need = std::min(rows[k].need, lds_limit);
-          if (k != a0 && fill + need > PEDN_TF_LDS_ROWS) continue;
-          taken[k] = 1;
-          packed.push_back(rows[k]);
-          lds_base.push_back(fill);
-          fill += need;
-          ++cnt;
-        }
-        for (; cnt < 4; ++cnt) { packed.push_back(Row{-1, 0, 0, 0, 0}); lds_base.push_back(0); }
-      }
-    }
-    s->h_slot_trow.assign(n_slots, -1);
-    s->inline_tf_ok = !packed.empty();
-    std::vector<int32_t> rwords(std::max<size_t>(packed.size(), 1) * PEDN_TROW_WORDS, 0), gwords;
-    std::vector<int32_t> prow(std::max(m->n_pair, 1), -1);  // product -> where its probability is, -1: the constant 1
-    int n_over = 0, n_multi = 0;  // n_over: rows of ent_p, for probabilities beyond a workgroup's LDS rows
-    auto put_d = [](int32_t* w, double x) { memcpy(w, &x, 8); };
-    auto put_f = [](int32_t* w, float x) { memcpy(w, &x, 4); };
-    for (size_t ri = 0; ri < packed.size(); ++ri) {
-      const int n = packed[ri].node, i = packed[ri].i;
-      int32_t* w = &rwords[ri * PEDN_TROW_WORDS];
-      if (n < 0) { w[0] = -1; continue; }
-      if (ri % 4 != 0 && packed[ri - 1].node == n && packed[ri - 1].i == i) {  // coop: copy of the workgroup's first record
-        std::copy(w - PEDN_TROW_WORDS, w, w);
-        continue;
-      }
-      const int s0 = m->node_slot_ptr[n], d = m->node_slot_ptr[n + 1] - s0;
-      const int ta = m->node_turn_ptr[n] + i * (d - 1);
-      w[0] = d; w[1] = ta; w[2] = n_multi; w[4] = m->turn_pair_ptr[ta]; w[5] = m->turn_pair_ptr[ta + d - 1];
-      for (int jj = 0; jj < d - 1; ++jj) {
-        w[84 + 3 * jj] = m->turn_pair_ptr[ta + jj]; w[85 + 3 * jj] = m->turn_pair_ptr[ta + jj + 1]; w[86 + 3 * jj] = s->h_turn_mode[ta + jj];
-      }
-      std::vector<int> used;  // outgoing slots this row's multi-entry groups refer to
-      int n_prob = 0, n_g = 0, any_sep = 0, over = 0;
-      const int lds_rows = std::min(packed[ri].need, lds_limit);
-      for (int g = m->node_grp_ptr[n]; g < m->node_grp_ptr[n + 1]; ++g) {
-        const int a = m->grp_ent_ptr[g], b = m->grp_ent_ptr[g + 1];
-        if (grp_row[g] != i || b - a < 1 || (b - a == 1 && shortcut)) continue;
-        double sumd = 0.0;
-        for (int e = a; e < b; ++e) sumd = (e == a) ? m->ent_dist[e] : sumd + m->ent_dist[e];
-        gwords.resize(gwords.size() + 32, 0);
-        int32_t* G = &gwords[gwords.size() - 32];
-        G[0] = b - a; G[1] = m->grp_allphys[g];
-        for (int k = 0; k < PEDN_MAX_DEGREE - 1; ++k) G[2 + k] = G[9 + k] = -1;
-        for (int e = a; e < b; ++e) {
-          const int k = e - a, l = m->ent_link[e];
-          if (l >= 0) {
-            int slot = -1;
-            for (int j = 0; j < d; ++j)
-              if (l < L && m->slot_out_link[s0 + j] == l) slot = j;
-            if (slot < 0) { pedn_destroy(s); return fail(nullptr, PEDN_E_ARG, "softmax entry is not an outgoing link of its node"); }
-            size_t u = std::find(used.begin(), used.end(), slot) - used.begin();
-            if (u == used.size()) used.push_back(slot);
-            G[2 + k] = (int)u;
-          }
-          if (ent_pair[e] >= 0) {
-            if (n_prob < lds_rows) G[9 + k] = lds_base[ri] + n_prob;
-            else { G[9 + k] = PEDN_TF_LDS_ROWS + n_over++; over = 1; }
-            ++n_prob;
-            prow[ent_pair[e]] = G[9 + k];
-          }
-          put_d(&G[16 + 2 * k], (m->pf_alpha * m->ent_dist[e]) / (sumd + 1e-6));
-        }
-        ++n_g; ++n_multi;
-      }
-      if (used.size() > (size_t)(PEDN_MAX_DEGREE - 1)) { pedn_destroy(s); return fail(nullptr, PEDN_E_ARG, "a row refers to more than 7 downstream links"); }
-      for (int e = 0; e < PEDN_MAX_DEGREE - 1; ++e) {
-        const int slot = used.empty() ? -1 : used[e < (int)used.size() ? e : 0];
-        int32_t* E = e < 5 ? &w[8 + 10 * e] : &w[64 + 10 * (e - 5)];
-        const int l = slot >= 0 ? m->slot_out_link[s0 + slot] : 0;  // only rows with groups come here, and L > 0 then
-        E[0] = l; E[1] = m->link_rev[l]; E[2] = m->link_sep[l];
-        put_f(&E[3], (float)(m->link_length[l] * m->link_width[l]));
-        put_d(&E[4], m->link_vf[l]); put_d(&E[6], m->link_kc[l]); put_d(&E[8], m->link_length[l]);
-        if (slot >= 0 && E[2]) any_sep = 1;
-      }
-      w[3] = n_g; w[6] = (int)used.size(); w[7] = any_sep; w[107] = over; w[108] = packed[ri].groups > coop_groups;
-      w[109] = lds_base[ri];
-      s->h_slot_trow[s0 + i] = (int)ri;
-      if (over || packed[ri].groups > coop_groups || lds_rows > PEDN_TF_INL_ROWS) s->inline_tf_ok = false;
-    }
-    gwords.resize(gwords.size() + 8 * 32, 0);  // turn_frac_body reads a chunk of four records ahead; padding has n = 0
-    rows = packed;
-    {  // the workgroups (quads of rows, heaviest first) whose dependent chains are longer than a link-update workgroup lasts: inside
-       // link_turn_kernel they are dispatched in front of the link update, the short ones behind it (launch_step)
-      int heavy_groups = 2;
-      if (const char* d = getenv("PEDN_TF_HEAVY_GROUPS")) heavy_groups = atoi(d);
-      s->n_tf_heavy_quads = 0;
-      for (size_t q = 0; q * 4 < rows.size(); ++q)
-        if (rows[q * 4].groups > heavy_groups) s->n_tf_heavy_quads = (int)q + 1;
-    }
-    v.n_multi = n_multi;
-    v.n_trow = (int)rows.size();
-    s->n_over = n_over;
-    TRY(upload(s, rwords.data(), rwords.size(), &v.trow_words));
-    TRY(upload(s, gwords.data(), gwords.size(), &v.tgrp_words));
-    TRY(upload(s, prow.data(), prow.size(), &v.pair_row));
-    for (int q = 0; q < m->n_pair; ++q)
-      if (!pconst[q] && prow[q] < 0) { pedn_destroy(s); return fail(nullptr, PEDN_E_ARG, "(turn, od) product without a softmax entry on a dynamic node"); }
-    v.n_turns = m->n_turns;
-  }
+  s->h_turn_pair_ptr.assign(m->turn_pair_ptr, m->turn_pair_ptr + m->n_turns + 1);
+  v.n_multi = tab.n_multi;
+  v.n_trow = tab.n_trow;
+  v.n_turns = m->n_turns;
+  s->n_over = tab.n_over;
+  s->n_tf_heavy_quads = tab.n_tf_heavy_quads;
+  s->inline_tf_ok = tab.inline_tf_ok;
+  TRY(upload(s, tab.trow_words.data(), tab.trow_words.size(), &v.trow_words));
+  TRY(upload(s, tab.tgrp_words.data(), tab.tgrp_words.size(), &v.tgrp_words));
+  TRY(upload(s, tab.pair_row.data(), tab.pair_row.size(), &v.pair_row));
+  s->h_pair_const = std::move(tab.pair_const);
+  s->h_turn_mode = std::move(tab.turn_mode);
+  s->h_slot_dyn = std::move(tab.slot_dyn);
+  s->h_slot_trow = std::move(tab.slot_trow);
   TRY(upload(s, m->od_w, (size_t)m->n_od * v.T1, &v.od_w));
-  {  // corridors: one lane of link_kernel updates both directions
-    std::vector<CorrRec> cr;
-    for (int l = 0; l < L; ++l)
-      if (l < m->link_rev[l]) {
-        CorrRec c{};
-        c.a = l; c.b = m->link_rev[l]; c.Pa = lp[c.a]; c.Pb = lp[c.b];
-        cr.push_back(c);
-      }
-    v.n_pairs_corr = (int)cr.size();
-    v.pairs_adj = 1;
-    for (size_t p = 0; p < cr.size(); ++p)
-      if (cr[p].a != 2 * (int)p || cr[p].b != 2 * (int)p + 1) v.pairs_adj = 0;
-    if (const char* f = getenv("PEDN_PAIRS_ADJ")) if (atoi(f) == 0) v.pairs_adj = 0;   // diagnostic: always through the record
-    TRY(upload(s, cr.data(), cr.size(), &v.corr_rec));
-  }
-  {  // bin nodes into blocks of 8 waves: first-fit over the nodes ordered by (expected load, slot count) decreasing, so that
-    // every block is full regardless of node degree.  The 8 waves of a block meet at two barriers, so a block lasts as long
-    // as its slowest wave, and the slow waves are those of busy links (look-backs, diffusion, binomial draws).  The junctions
-    // that many OD routes pass -- those with many (turn, od) products -- are the likely ones and go first (delft: 32.3 ->
-    // 31.6 us; PEDN_PACK_BY_LOAD=0 orders by slot count only).  Re-packing at run time by the cost the waves measure
-    // themselves (ticks up to the first barrier, sampled every 100 / 250 steps) was tried and changed nothing (30.5 us either
-    // way): the spread inside a block comes from step-to-step variation, not from which junctions share it.
-    // Better than the estimate: the MEASURED cost of every node's slowest wave (pedn_model_desc.node_cost, from a calibration run of
-    // the profiling build, tools/pack_calibrate.py).  tools/pack_analysis.py: the wait at the first barrier is static (92 % of it is
-    // explained by the waves' mean arrival times); half of it is a node's waves waiting for each other -- inherent --, the other half is
-    // the packing's, and packing by measured cost removes at most half of that: 3.4-3.9 % of a wave's life.
-    // PEDN_PACK_BY_LOAD=0: by degree only, =1: by the static estimate even when a measured cost is given.
-    std::vector<int> order(N);
-    std::vector<double> load(N, 0.0);
-    for (int n = 0; n < N; ++n) order[n] = n;
-    auto deg = [&](int n) { return m->node_slot_ptr[n + 1] - m->node_slot_ptr[n]; };
-    int by_load = m->node_cost ? 2 : 1;
-    if (const char* f = getenv("PEDN_PACK_BY_LOAD")) by_load = std::min(atoi(f), by_load);
-    if (by_load == 2)
-      for (int n = 0; n < N; ++n) load[n] = (double)m->node_cost[n];
-    else if (by_load == 1)
-      for (int n = 0; n < N; ++n) load[n] = m->turn_pair_ptr[m->node_turn_ptr[n + 1]] - m->turn_pair_ptr[m->node_turn_ptr[n]];
-    s->packed_by = by_load;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return load[a] != load[b] ? load[a] > load[b] : deg(a) > deg(b); });
-    s->h_pack_order.assign(order.begin(), order.end());
-    std::vector<std::vector<int>> bins;
-    std::vector<int> fill;
-    for (int n : order) {
-      int d = deg(n), chosen = -1;
-      for (size_t b = 0; b < bins.size(); ++b)
-        if (fill[b] + d <= 8) { chosen = (int)b; break; }
-      if (chosen < 0) { bins.emplace_back(); fill.push_back(0); chosen = (int)bins.size() - 1; }
-      bins[chosen].push_back(n);
-      fill[chosen] += d;
-    }
-    SlotRec idle{};
-    idle.node = -1;
-    idle.trow = -1;
-    std::vector<SlotRec> rec((bins.size() + 1) * 8, idle);   // one more block of idle records behind the bins: prewarm_chains
-    for (size_t b = 0; b < bins.size(); ++b) {
-      int wave = 0, base = 0;
-      for (int n : bins[b]) {
-        int d = deg(n);
-        for (int k = 0; k < d; ++k) {
-          SlotRec& R = rec[b * 8 + wave++];
-          R.node = n; R.slot = k; R.base = base; R.m = d;
-          R.kind = m->node_kind[n]; R.dyn = s->h_slot_dyn[m->node_slot_ptr[n] + k];
-          R.trow = s->h_slot_trow.empty() ? -1 : s->h_slot_trow[m->node_slot_ptr[n] + k];
-          R.lin = m->slot_in_link[m->node_slot_ptr[n] + k];
-          R.lout = m->slot_out_link[m->node_slot_ptr[n] + k];
-          R.turn0 = m->node_turn_ptr[n];
-          R.demand_row = m->node_demand_row[n];
-          if (R.lin < L) { R.Pin = lp[R.lin]; R.Pout = lp[R.lout]; }
-        }
-        base += d * d;  // <= 64 tiles because sum(d) <= 8
-      }
-    }
-    {  // the mirror of a physical slot: the slot whose incoming link is its outgoing link (every physical link is the incoming link of one slot)
-      std::vector<int32_t> pos_of(L, -1);
-      for (size_t i = 0; i < rec.size(); ++i)
-        if (rec[i].node >= 0 && rec[i].lin < L) pos_of[rec[i].lin] = (int32_t)i;
-      for (SlotRec& R : rec) R.mirror = R.node >= 0 && R.lin < L && R.lout < L ? pos_of[R.lout] : -1;
-    }
-    s->n_blocks = (int)bins.size();
-    for (int n = 0; n < N; ++n) s->max_degree = std::max(s->max_degree, deg(n));
-    if (const char* f = getenv("PEDN_NODE_MD")) if (atoi(f) == 8) s->max_degree = 8;  // diagnostic: the general instantiation
-    {  // LDS of node_kernel: 8 (LP: 16) rows of 64 doubles + the m*m tiles of the fullest block
-      int tiles = 1;
-      for (const auto& bin : bins) {
-        int t2 = 0;
-        for (int n : bin) t2 += deg(n) * deg(n);
-        tiles = std::max(tiles, t2);
-      }
-      s->node_lds = (size_t)((m->node_model == PEDN_NODE_OPTIMAL ? 16 : 8) + tiles) * 64 * sizeof(double);
-    }
+  v.n_pairs_corr = (int)tab.corr.size();
+  v.pairs_adj = tab.pairs_adj;
+  if (const char* f = getenv("PEDN_PAIRS_ADJ")) if (atoi(f) == 0) v.pairs_adj = 0;   // diagnostic: always through the record
+  TRY(upload(s, tab.corr.data(), tab.corr.size(), &v.corr_rec));
+  {  // the plan, from the compiled tables
+    s->h_slot_rec = std::move(tab.full.rec);
+    const std::vector<SlotRec>& rec = s->h_slot_rec;
+    s->packed_by = tab.packed_by;
+    s->h_pack_order = std::move(tab.pack_order);
+    s->n_blocks = tab.full.n_blocks;
+    s->max_degree = tab.max_degree;
+    // LDS of node_kernel: 8 (LP: 16) rows of 64 doubles + the m*m tiles of the fullest block
+    s->node_lds = (size_t)((m->node_model == PEDN_NODE_OPTIMAL ? 16 : 8) + tab.full.tiles) * 64 * sizeof(double);
     // (register budget of the node kernels: node_kernel_waves() in pedn_kernels.hpp)
     // The link update of t and the turning fractions of t+1 share one launch (both only read what node_kernel(t) and earlier
     // launches wrote); PEDN_FUSE_TP=0 gives the fractions a launch of their own in front of node_kernel(t+1).
     s->fuse_tp = 1;
     if (const char* f = getenv("PEDN_FUSE_TP")) s->fuse_tp = atoi(f) != 0;
     if (const char* f = getenv("PEDN_FUSE_OBS")) s->fuse_obs = atoi(f) != 0;
-    for (SlotRec& R : rec) { R.act = -1; R.lp = -1; }
     // two chains of launches (one per half of the replicas) in pedn_run; PEDN_STREAMS=1|2, pedn_set_streams.  Default from 640
     // replicas: one chain's launch leaves wave places empty while it fills and drains, and the other half's launches use them
     // (delft x 1024: 51.7 -> 45.3 us per step in round 2; round 5, melbourne / delft: x 640 25.8 -> 23.6 / 36.2 -> 34.3, x 768 27.1 -> 24.8,
@@ -850,9 +547,7 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     if (const char* f = getenv("PEDN_RL_CHAINS")) s->rl_chains = atoi(f) == 2 ? 2 : 1;
     s->node_lp = m->node_model == PEDN_NODE_OPTIMAL;
     if (s->node_lp) {  // tableau workspace: one per (regular node, replica group), sized for the largest such node
-      int n_lp = 0, max_m = 0;
-      for (SlotRec& R : rec)
-        if (R.node >= 0 && R.kind == 1 && R.slot == 0) { R.lp = n_lp++; max_m = std::max(max_m, R.m); }
+      const int n_lp = tab.full.n_lp, max_m = tab.full.lp_max_m;
       const int E = max_m * (max_m - 1), rows = 2 * max_m + E, cols = 3 * E + 2 * max_m;
       v.lp_stride = (size_t)(rows + 1) * (cols + 1) * 64;
       v.lp_bstride = (size_t)rows * 64;
@@ -860,7 +555,6 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
       TRY(dalloc(s, waves * v.lp_stride, &v.lp_ws));
       TRY(dalloc(s, waves * v.lp_bstride, &v.lp_basis));
     }
-    s->h_slot_rec = rec;
     TRY(upload(s, rec.data(), rec.size(), &v.slot_rec));
     s->d_slot_rec = const_cast<SlotRec*>(v.slot_rec);
     v.quiet_npos = (int32_t)rec.size();
@@ -1553,47 +1247,14 @@ static int dl_refresh(pedn_sim* s) {
     if (full[i].slot == 0) first[full[i].node] = (int32_t)i;
     if (dead[full[i].node]) { pos.push_back(full[i]); n_links += full[i].lin < L; }
   }
-  std::vector<std::vector<int>> bins;
-  std::vector<int> fill;
-  for (int n : s->h_pack_order) {
-    if (dead[n]) continue;
-    const int d = s->h_node_slot_ptr[n + 1] - s->h_node_slot_ptr[n];
-    int chosen = -1;
-    for (size_t b = 0; b < bins.size(); ++b)
-      if (fill[b] + d <= 8) { chosen = (int)b; break; }
-    if (chosen < 0) { bins.emplace_back(); fill.push_back(0); chosen = (int)bins.size() - 1; }
-    bins[chosen].push_back(n);
-    fill[chosen] += d;
-  }
-  SlotRec idle{};
-  idle.node = -1; idle.trow = -1; idle.act = -1; idle.lp = -1; idle.mirror = -1;
-  std::vector<SlotRec> rec((bins.size() + 1) * 8, idle);
-  int tiles = 1;
-  for (size_t b = 0; b < bins.size(); ++b) {
-    int wave = 0, base = 0;
-    for (int n : bins[b]) {
-      const int d = s->h_node_slot_ptr[n + 1] - s->h_node_slot_ptr[n];
-      for (int k = 0; k < d; ++k) {
-        SlotRec& R = rec[b * 8 + wave++];
-        R = full[first[n] + k];   // (a node's slots are consecutive waves of one block)
-        R.base = base;
-      }
-      base += d * d;
-    }
-    tiles = std::max(tiles, base);
-  }
-  std::vector<int32_t> pos_of(std::max(L, 1), -1);
-  for (size_t i = 0; i < rec.size(); ++i)
-    if (rec[i].node >= 0 && rec[i].lin < L) pos_of[rec[i].lin] = (int32_t)i;
-  for (size_t i = 0; i < rec.size(); ++i) {
-    SlotRec& R = rec[i];
-    R.mirror = R.node >= 0 && R.lin < L && R.lout < L ? (pos_of[R.lout] >= 0 ? pos_of[R.lout] : (int32_t)i) : -1;
-  }
+  const pedn_compile::Packing live = pedn_compile::pack(s->h_pack_order, s->h_node_slot_ptr.data(), dead.data(), L, true, false,
+                                                        [&](int n, int k) { return full[first[n] + k]; });   // (a node's slots are consecutive waves of one block)
+  const std::vector<SlotRec>& rec = live.rec;
   s->n_dead_links = n_links;
   s->n_dead_pos = (int)pos.size();
-  s->n_live_blocks = (int)bins.size();
+  s->n_live_blocks = live.n_blocks;
   s->live_npos = (int)rec.size();
-  s->node_lds_live = (size_t)(8 + tiles) * 64 * sizeof(double);
+  s->node_lds_live = (size_t)(8 + live.tiles) * 64 * sizeof(double);
   // every launch that read the old lists was joined into the engine's stream by the pedn_run that made it
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   HIP_TRY(s, hipMemcpy(s->d_live_rec, rec.data(), rec.size() * sizeof(SlotRec), hipMemcpyHostToDevice));

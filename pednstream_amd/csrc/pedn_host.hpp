@@ -42,7 +42,7 @@ struct pedn_sim {
   int device = 0;
   int n_nodes = 0, n_turns = 0, n_demand = 0, n_od = 0, n_blocks = 0, n_ent = 0;
   int link_owner = 0;  // pedn_run: node_kernel(t + 1)'s slot waves perform the link update of t (one launch per step), PEDN_LINK_OWNER
-  int packed_by = 1;   // how nodes were binned into node_kernel's blocks: 0 by degree, 1 by the static load estimate, 2 by measured cost
+  int packed_by = 1;   // (from the model compiler, pedn_compile.hpp) how nodes were binned into node_kernel's blocks: 0 by degree, 1 by the static load estimate, 2 by measured cost
   // Single-launch plan of small batches with dynamic turning fractions (inline_tf): every device-computed row is short enough for ONE
   // wave and its probabilities fit PEDN_TF_INL_ROWS LDS rows (inline_tf_ok), and the whole node_kernel grid is one generation at 4 waves
   // per SIMD: the slot waves of node_kernel<LU, TF> compute their own rows, a step is one launch.
@@ -102,7 +102,7 @@ struct pedn_sim {
   std::vector<char> dl_reach;          // [links] REACH, OR-ed over those proofs
   std::vector<char> h_demand_nz;       // [demand rows] the row may hold something else than +0.0
   std::vector<char> h_tab_nz;          // [turns] a host-tabulated fraction that is not +-0.0 at some step (tabulate_pair_pod)
-  std::vector<int32_t> h_pack_order;   // nodes in the order the bins were packed in
+  std::vector<int32_t> h_pack_order;   // nodes in the order the bins were packed in (pedn_compile::Tables::pack_order; dl_refresh repacks in it)
   std::vector<int32_t> h_link_sep, h_link_tau_sw, h_link_rev, h_node_kind, h_slot_in, h_slot_out;
   int n_dead_links = 0, n_dead_pos = 0, n_live_blocks = 0, live_npos = 0;
   int split_steps = 0;                 // steps launched by launch_split_step since the last reset of either kind (pedn_plan_info info[10])

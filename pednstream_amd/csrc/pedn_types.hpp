@@ -39,7 +39,7 @@ struct alignas(16) LinkPR {
 };
 static_assert(sizeof(LinkPR) == 32, "LinkPR must stay two 16-byte loads");
 
-struct SlotRec {  // one wave of node_kernel: a (node, slot) with everything static it needs, fetched by ONE scalar load burst
+struct SlotRec {  // one wave of node_kernel: a (node, slot) with everything static it needs, fetched by ONE scalar load burst (filled by pedn_compile::pack)
   // dyn: where the slot's row of turning fractions comes from -- 0 tf / tf_u (default or imposed), 1 tfd[t & 1] (turn_frac_kernel),
   // 2 turn_tab[t] / turn_tab_r (every product constant: replica-independent, tabulated and renormalised on the host)
   // act: action slot of the batched RL step that sets this slot's gate (back gate of lout = front gate of lin), -1 none
@@ -78,11 +78,11 @@ struct CorrRec {  // one lane group of link_kernel: both directions of a corrido
 // ---- route choice (path_finder.py:561-737), organised per row (= incoming slot) of a dynamic node: one wave of
 // turn_frac_kernel owns (row, 64 replicas).  Its static data are int32 word records fetched with vector loads (lane k holds
 // word k) and broadcast with v_readlane -- see turn_frac_body.
-#define PEDN_TF_LDS_ROWS 64    // LDS rows (64 lanes x 8 bytes) of one workgroup = 4 rows of dynamic nodes, shared out by the host
+#define PEDN_TF_LDS_ROWS 64    // LDS rows (64 lanes x 8 bytes) of one workgroup = 4 rows of dynamic nodes, shared out by the compiler (pedn_compile.hpp)
 #define PEDN_TROW_WORDS 128
 #define PEDN_TF_INL_ROWS 8     // LDS rows a slot wave of node_kernel<.., TF> has for the probabilities of its own row (single-launch plan)
 #define PEDN_TF_COOP_GROUPS 8   // rows with more multi-entry groups get a workgroup of their own (see turn_frac_body)
-// row record, PEDN_TROW_WORDS words (m = -1: padding):
+// row record, PEDN_TROW_WORDS words (m = -1: padding), written by pedn_compile::compile:
 //   [0] m  [1] first turn of the row  [2] first group (index into tgrp_words / 32)  [3] number of multi-entry groups
 //   [4] Q0  [5] Q1: the row's (turn, od) products  [6] n_used outgoing links below  [7] some of them is a separator
 //   entries e = 0..4 at 8 + 10 e, e = 5, 6 at 64 + 10 (e - 5): link, reverse link, separator flag, float32(length * width),

@@ -2,7 +2,7 @@
 through its stand-alone driver tests/partition_prog.cpp.
 
 proof_inputs(m) derives from a flattened model what the engine hands the proof (pedn_hip.hip: dl_refresh): which demand rows hold anything
-but +0.0, the shared fractions, where each slot's row of fractions comes from (pedn_create: a row of a dynamic node whose (turn, od)
+but +0.0, the shared fractions, where each slot's row of fractions comes from (pedn_compile.hpp: a row of a dynamic node whose (turn, od)
 products are all the constant 1 is tabulated on the host, dyn = 2) and which of those tabulated fractions can be non-zero
 (tabulate_pair_pod + finish_tabulated_rows).  partition(inp) is the propagation itself, written from the rules of the issue, not from
 the C++."""
@@ -43,7 +43,7 @@ def proof_inputs(m):
            "link_sep": m["link_sep"], "link_tau_sw": m["link_tau_sw"], "front_u": np.array(m["front_gate0"], dtype=np.float64),
            "back_u": np.array(m["back_gate0"], dtype=np.float64), "link_rl": np.zeros(L, dtype=bool)}
     tf_u = np.array(m["tf_init"], dtype=np.float64)
-    # (turn, od) products whose P(down | up, od) is the constant 1: the only entry of its softmax group (pedn_create)
+    # (turn, od) products whose P(down | up, od) is the constant 1: the only entry of its softmax group (pedn_compile.hpp)
     n_pair = int(m["n_pair"])
     xmax = abs(m["pf_temp"]) * (abs(m["pf_alpha"]) + abs(m["pf_beta"]) * 16.0 + abs(m["pf_omega"]) + abs(m["pf_eps"]))
     gptr = np.asarray(m["grp_ent_ptr"])
@@ -80,7 +80,7 @@ def proof_inputs(m):
             fix = np.abs(rowsum - 1) > 1e-3
             fin = np.where(fix, np.where(rowsum > 1e-6, raw / np.where(rowsum > 1e-6, rowsum, 1.0), 1.0 / (d - 1)), raw)
             tab_nz[ta:ta + d - 1] = (~_is_zero(fin)).any(axis=1)
-    inp.update(tf_u=tf_u, slot_dyn=slot_dyn, tab_nz=tab_nz)
+    inp.update(tf_u=tf_u, slot_dyn=slot_dyn, tab_nz=tab_nz, pair_const=pconst)   # (pair_const: for tests/test_model_compile_host.py)
     return inp
 
 
