@@ -134,11 +134,9 @@ static int clear_rows(pedn_sim* s, int row0, int row1, int what) {
 static int reset_state(pedn_sim* s) {
   DevView& v = s->v;
   HIP_TRY(s, hipMemsetAsync(v.flags, 0, (size_t)v.RS * sizeof(uint32_t), s->stream));
-  s->valid_hi = v.valid_hi = 0x7fffffff;
-  s->zhw64 = s->zhw32 = -1;   // every row of the six fields is +0.0 once clear_rows has run
-  s->dl_grow = s->dl_dirty = true;   // dead links: proven afresh from here
-  s->dl_off = false;
-  s->zgated = s->split_steps = 0;
+  pedn_plan::reset_full(s->marks);
+  mirror_marks(s);
+  s->dl_dirty = true;
   return clear_rows(s, 0, v.T1, 1);
 }
 
@@ -151,35 +149,35 @@ static int reset_state_lazy(pedn_sim* s) {
   HIP_TRY(s, hipMemsetAsync(v.flags, 0, (size_t)v.RS * sizeof(uint32_t), s->stream));
   int rc;
   if ((rc = clear_rows(s, 0, 1, 1)) || (rc = clear_rows(s, 1, std::min(v.W, v.T1), 2)) || (rc = clear_rows(s, 1, v.T1, 4))) return rc;
-  s->valid_hi = v.valid_hi = 0;
-  s->zgated = s->split_steps = 0;   // (the zero-elision marks stay: the rows above row 0 still hold the old episode's values)
+  pedn_plan::reset_lazy(s->marks);
+  mirror_marks(s);
   return PEDN_OK;
 }
 
 // Rows (valid_hi, upto] cleared now: something is about to read them from memory (an out-of-order step, an observation of a step that
 // has not run, a zero-copy consumer).
 static int catch_up(pedn_sim* s, int upto) {
-  if (s->valid_hi >= upto) return PEDN_OK;
-  no_quiet(s);
+  if (s->marks.valid_hi >= upto) return PEDN_OK;
   upto = std::min(upto, s->v.T1 - 1);
   DevView view = s->v;
   int rc = PEDN_OK;
-  if (upto > s->valid_hi) {
+  if (upto > s->marks.valid_hi) {
     // everything but the gate record and the low rows of avg_travel_time, which the lazy reset restored already
     DevView& v = s->v;
-    const int a = s->valid_hi + 1, b = upto + 1;
+    const int a = s->marks.valid_hi + 1, b = upto + 1;
     for (int f = 0; f < 4; ++f) HIP_TRY(s, hipMemsetAsync(v.f64[f] + (size_t)a * v.Lall * v.RS, 0, (size_t)(b - a) * v.Lall * v.RS * sizeof(double), s->stream));
     if (v.L > 0) {
       // sending / receiving flow of step t are entries t - 1: entry valid_hi belongs to the step that is being skipped
       const size_t n_1 = (size_t)v.L * v.RS;
-      hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n_1 + 255) / 256)), dim3(256), 0, s->stream, view, s->valid_hi, 1, 16);
+      hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n_1 + 255) / 256)), dim3(256), 0, s->stream, view, s->marks.valid_hi, 1, 16);
       HIP_TRY(s, hipGetLastError());
       const size_t n_l = (size_t)(b - a) * v.L * v.RS;
       hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n_l + 255) / 256)), dim3(256), 0, s->stream, view, a, b - a, 8);
       rc = hipGetLastError() == hipSuccess ? PEDN_OK : fail(s, PEDN_E_DEVICE, "init_state_kernel");
     }
-    s->valid_hi = s->v.valid_hi = upto;
   }
+  pedn_plan::caught_up(s->marks, upto);
+  mirror_marks(s);
   return rc;
 }
 
@@ -331,7 +329,7 @@ static int scenario_pod_tables(pedn_sim* s) {
 
 // (the entry points below have C linkage from their declarations in include/pedn.h)
 static int push_rows(pedn_sim* s, double* dst, const double* values, int n_rows, size_t row0, size_t row_stride, int replica);
-static void flush_links(pedn_sim* s, int half, hipEvent_t* ev);
+static void flush_links(pedn_sim* s, int half, hipEvent_t* ev, bool last = true);
 typedef void (*step_kernel_fn)(DevView, int);   // node_kernel, turn_frac_kernel, link_kernel_1r
 static step_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf);
 static void prewarm_chains(pedn_sim* s);
@@ -675,15 +673,11 @@ int pedn_destroy(pedn_sim* s) {
   return PEDN_OK;
 }
 
-// what both resets do in front of clearing the state: the host's bookkeeping back to "nothing has run"
+// what both resets do in front of clearing the state (which takes the marks back to "nothing has run": reset_full / reset_lazy)
 static int reset_bookkeeping(pedn_sim* s) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   HIP_TRY(s, hipSetDevice(s->device));
   join_forked(s);
-  s->tp_ready = -1;
-  s->last_t = -1;
-  s->link_pending = -1;   // discarded: the state it would complete is being cleared
-  no_quiet(s);
   return norm_reset_returns(s);
 }
 
@@ -843,7 +837,7 @@ int pedn_set_od_weights(pedn_sim* s, int32_t od, const double* values, int32_t n
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   HIP_TRY(s, hipMemcpy((void*)(s->v.od_w + (size_t)od * s->v.T1), values, (size_t)n * 8, hipMemcpyHostToDevice));
   std::copy(values, values + n, s->h_od_w.begin() + (size_t)od * s->v.T1);
-  s->tp_ready = -1;  // fractions of the next step may already sit in tfd, computed with the old weights
+  pedn_plan::fractions_invalid(s->marks);  // fractions of the next step may already sit in tfd, computed with the old weights
   return tabulate_pair_pod(s);
 }
 
@@ -856,11 +850,11 @@ int pedn_set_turning_fractions(pedn_sim* s, int32_t node, int32_t replica, const
   if (rc != PEDN_OK) return rc;
   s->dl_dirty = true;
   // a dynamic node recomputes its fractions every step (network.py:272-275); until then a read returns what was imposed
-  s->h_tf_set_epoch[node] = s->step_epoch;
+  s->h_tf_set_epoch[node] = s->marks.step_epoch;
   // (the imposed values go into the buffer of the last step too, see below: a REPEAT of that step must recompute them, not take them
   // for its own -- under the single-launch plan tp_ready names that very step; found by tools/gpu_fuzz_plans.py)
-  if (s->h_node_dyn[node]) s->tp_ready = -1;
-  if (s->h_node_dyn[node] && s->last_t >= 0 && (rc = push_rows(s, s->v.tfd[s->last_t & 1], tf, n, (size_t)a, 1, replica)) != PEDN_OK) return rc;
+  if (s->h_node_dyn[node]) pedn_plan::fractions_invalid(s->marks);
+  if (s->h_node_dyn[node] && s->marks.last_t >= 0 && (rc = push_rows(s, s->v.tfd[s->marks.last_t & 1], tf, n, (size_t)a, 1, replica)) != PEDN_OK) return rc;
   for (int k = 0; k < n; ++k)
     s->h_tf_u[a + k] = (replica == PEDN_ALL && !s->h_node_dyn[node]) ? tf[k] : __builtin_nan("");
   return push_uniform(s);
@@ -875,20 +869,20 @@ int pedn_get_turning_fractions(pedn_sim* s, int32_t node, int32_t replica, doubl
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
   HIP_TRY(s, hipStreamSynchronize(s->stream));
-  const double* src = (s->h_node_dyn[node] && s->last_t >= 0) ? s->v.tfd[s->last_t & 1] : s->v.tf;
+  const double* src = (s->h_node_dyn[node] && s->marks.last_t >= 0) ? s->v.tfd[s->marks.last_t & 1] : s->v.tf;
   HIP_TRY(s, hipMemcpy2D(tf, 8, src + (size_t)a * s->v.RS + replica, (size_t)s->v.RS * 8, 8, n, hipMemcpyDeviceToHost));
   if (s->v.pod_pr && s->ttab_r_stale) {  // the per-replica tables were derived on the device: fetch the host copy once
     s->h_ttab_r.assign((size_t)std::max(s->n_turns, 1) * s->v.R, 0.0);
     HIP_TRY(s, hipMemcpy2D(s->h_ttab_r.data(), (size_t)s->v.R * 8, s->d_turn_tab_r, (size_t)s->v.RS * 8, (size_t)s->v.R * 8, std::max(s->n_turns, 1), hipMemcpyDeviceToHost));
     s->ttab_r_stale = false;
   }
-  if (s->h_node_dyn[node] && s->last_t >= 0 && s->h_tf_set_epoch[node] != s->step_epoch) {  // rows tabulated on the host (SlotRec.dyn == 2)
+  if (s->h_node_dyn[node] && s->marks.last_t >= 0 && s->h_tf_set_epoch[node] != s->marks.step_epoch) {  // rows tabulated on the host (SlotRec.dyn == 2)
     const int s0 = s->h_node_slot_ptr[node], d = s->h_node_slot_ptr[node + 1] - s0;
     for (int i = 0; i < d; ++i)
       if (s->h_slot_dyn[s0 + i] == 2)
         for (int jj = 0; jj < d - 1; ++jj) {
           const int tn = a + i * (d - 1) + jj;
-          tf[tn - a] = s->v.pod_pr ? s->h_ttab_r[(size_t)tn * s->v.R + replica] : s->h_ttab[(size_t)s->last_t * s->n_turns + tn];
+          tf[tn - a] = s->v.pod_pr ? s->h_ttab_r[(size_t)tn * s->v.R + replica] : s->h_ttab[(size_t)s->marks.last_t * s->n_turns + tn];
         }
   }
   return PEDN_OK;
@@ -902,7 +896,7 @@ int pedn_set_width(pedn_sim* s, int32_t which, int32_t link, int32_t replica, do
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);     // the link update records the gate / reads the separator width of its own step
   s->dl_dirty = true;
-  if (which == PEDN_W_BACK) s->tp_ready = -1;  // capacity fallback of the turn probabilities (path_finder.py:575-576)
+  if (which == PEDN_W_BACK) pedn_plan::fractions_invalid(s->marks);  // capacity fallback of the turn probabilities (path_finder.py:575-576)
   join_forked(s);   // (as every setter: ordered behind both chains)
   // one launch, its values as kernel arguments: the row's replicas and the link's entry of the replica-uniform shortcut (front_u / back_u:
   // NaN = "differs between replicas"; a link the RL agents write per replica keeps NaN, push_uniform)
@@ -924,7 +918,7 @@ int pedn_set_widths(pedn_sim* s, int32_t which, const double* values) {
   if (!s || !values) return fail(s, PEDN_E_ARG, "null argument");
   if (which < 0 || which > 3) return fail(s, PEDN_E_ARG, "selector out of range");
   DevView& v = s->v;
-  if (which == PEDN_W_BACK) s->tp_ready = -1;
+  if (which == PEDN_W_BACK) pedn_plan::fractions_invalid(s->marks);
   if (v.L == 0) return PEDN_OK;
   double* dst = which == PEDN_W_FRONT ? v.front : which == PEDN_W_BACK ? v.back : which == PEDN_W_SEP ? v.sepw : v.sepnp;
   HIP_TRY(s, hipSetDevice(s->device));
@@ -954,7 +948,7 @@ int pedn_set_widths(pedn_sim* s, int32_t which, const double* values) {
 int pedn_reset_widths(pedn_sim* s, const double* front, const double* back, const double* sep) {
   if (!s || !front || !back || !sep) return fail(s, PEDN_E_ARG, "null argument");
   DevView& v = s->v;
-  s->tp_ready = -1;
+  pedn_plan::fractions_invalid(s->marks);
   if (v.L == 0) return PEDN_OK;
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
@@ -1106,27 +1100,20 @@ static DevView view_of(const pedn_sim* s, int half, hipStream_t* stream) {
   }
   return v;
 }
-static inline bool last_chain(const pedn_sim* s, int half) { return half < 0 || half == s->run_chains - 1; }
 
-// Owner-wave plan: the link update of the last step launched is still to be done (link_pending); do it now.
-static void flush_links(pedn_sim* s, int half, hipEvent_t* ev) {
-  if (s->link_pending < 0) return;
-  no_quiet(s);
+// Owner-wave plan: the link update of the last step launched is still to be done (link_pending); do it now.  last: on the last of the
+// chains (the others still see the update as pending).
+static void flush_links(pedn_sim* s, int half, hipEvent_t* ev, bool last) {
+  if (s->marks.link_pending < 0) return;
   hipStream_t stream;
   const DevView v = view_of(s, half, &stream);
-  launch_link_update(s, v, stream, s->link_pending, ev, 4);
-  if (last_chain(s, half)) {
-    s->zhw32 = std::max(s->zhw32, s->link_pending);   // (zero elision) num_pedestrians / density of that row written
-    s->link_pending = -1;
-  }
+  launch_link_update(s, v, stream, s->marks.link_pending, ev, 4);
+  if (last) pedn_plan::flushed(s->marks);
+  else pedn_plan::touch(s->marks);
 }
 
-// One step = node_kernel(t), then ONE launch with the link update of t and -- where they apply -- the turn probabilities of
-// t+1 (models with softmax groups) and the RL observations / rewards of t (observe >= 0: the accumulate flag of
-// rl_observe; only pedn_rl_step asks for it).  ev != nullptr: per-launch start/stop events {turn_prob, node, link} for
-// pedn_profile_step.  Returns 1 through *observed when the observations were part of the launch.
-// Every entry point that looks at or changes what a link update reads or writes calls this first: under the owner-wave plan the link
-// update of the last step launched may still be pending (link_pending) -- the next step's node kernel would perform it.
+// Every entry point that looks at or changes what a link update reads or writes calls pending_links_first: under the owner-wave plan the
+// link update of the last step launched may still be pending (link_pending) -- the next step's node kernel would perform it.
 static int join_chains(pedn_sim* s, int n, int idle = -1);
 // (also: pedn_rl_step may have left the two halves of the batch stepping as two chains on two streams across calls -- `forked` -- so
 // that the engine's stream does not order stream2's work yet: joined first.  Anything that enqueues on the engine's stream or reads
@@ -1140,9 +1127,9 @@ static inline void join_forked(pedn_sim* s) {
 }
 static inline void pending_links_first(pedn_sim* s) {
   s->touched = 1;
-  no_quiet(s);   // whatever comes next may change a history row or break the chain of node_kernel<LU> launches
+  pedn_plan::touch(s->marks);   // whatever comes next may change a history row or break the chain of node_kernel<LU> launches
   join_forked(s);
-  if (s->link_pending >= 0) flush_links(s, -1, nullptr);
+  if (s->marks.link_pending >= 0) flush_links(s, -1, nullptr);
 }
 
 // The first launch of a kernel on a stream that has not run it yet costs the runtime several tens of microseconds (measured: the first
@@ -1204,7 +1191,7 @@ static int dl_refresh(pedn_sim* s) {
   pm.node_demand_row = s->node_demand_row.data(); pm.slot_in = s->h_slot_in.data(); pm.slot_out = s->h_slot_out.data();
   pm.link_rev = s->h_link_rev.data(); pm.slot_dyn = s->h_slot_dyn.data(); pm.node_lp = s->node_lp;
   // once a step has run, the sources of the earlier proofs stay sources: their pedestrians may still be on the way
-  if (s->dl_grow || s->dl_src.size() != s->h_demand_nz.size() || s->dl_reach.size() != (size_t)std::max(L, 1)) {
+  if (s->marks.dl_grow || s->dl_src.size() != s->h_demand_nz.size() || s->dl_reach.size() != (size_t)std::max(L, 1)) {
     s->dl_src = s->h_demand_nz;
     s->dl_reach.assign(std::max(L, 1), 0);
   } else {
@@ -1224,9 +1211,9 @@ static int dl_refresh(pedn_sim* s) {
   const pedn_part::Result proof = pedn_part::partition(pm);
   std::copy(proof.reach.begin(), proof.reach.end(), s->dl_reach.begin());   // (a superset of the seeds)
   std::vector<char> dead = proof.node_dead;
-  if (!s->dl_grow && s->dl_node.size() == dead.size())
+  if (!s->marks.dl_grow && s->dl_node.size() == dead.size())
     for (int n = 0; n < N; ++n) dead[n] = dead[n] && s->dl_node[n];
-  else if (!s->dl_grow) dead.assign(N, 0);
+  else if (!s->marks.dl_grow) dead.assign(N, 0);
   // the lean waves take both gates of a slot from the replica-uniform shortcuts: a node with a slot whose gates are not shared stays with
   // the node kernel (the proof's eligibility rule says as much for every corridor of a dead node; this is the kernel's own condition)
   for (int n = 0; n < N; ++n)
@@ -1236,7 +1223,7 @@ static int dl_refresh(pedn_sim* s) {
     }
   if (dead == s->dl_node) return dl_prep(s);
   s->dl_node = dead;
-  no_quiet(s);
+  pedn_plan::dead_set_changed(s->marks);
   // the work list of dead_link_kernel, and the live packing: the full packing's records of the live nodes, first-fit in its order
   const std::vector<SlotRec>& full = s->h_slot_rec;
   std::vector<SlotRec> pos;
@@ -1266,7 +1253,7 @@ static int dl_refresh(pedn_sim* s) {
 // off: recent-history mode, the node LP, rows of fractions computed on the device, per-replica link parameters, an agent set, no
 // third stream that overlaps, a state the host does not follow (dl_off) -- and a model without a dead link.
 static bool dl_split_ok(pedn_sim* s) {
-  if (!s->dead_links || !s->d_live_rec || !s->stream3 || s->dl_off || s->chains < 2 || !s->link_owner || !s->quiet || s->node_lp || s->inline_tf ||
+  if (!s->dead_links || !s->d_live_rec || !s->stream3 || s->marks.dl_off || s->chains < 2 || !s->link_owner || !s->quiet || s->node_lp || s->inline_tf ||
       s->v.hist || s->v.pr || s->rl_ready || s->v.n_trow > 0 || s->v.n_pairs_corr == 0)
     return false;
   if (s->dl_dirty && dl_refresh(s) != PEDN_OK) return false;
@@ -1280,6 +1267,13 @@ static bool dl_split_ok(pedn_sim* s) {
 static size_t dead_lds_bytes(int n) {
   if (n >= 8) return 0;   // the register budget's own 8 waves per SIMD
   return (size_t)(64 / (n + 1) + 1) * 2560;
+}
+
+// a step of the whole batch, or chain c of n, under the plain (lazy = false) or the owner-wave family
+static inline pedn_plan::StepRequest step_request(int t, bool lazy, int chain = -1, int n_chains = 1) {
+  pedn_plan::StepRequest rq;
+  rq.t = t; rq.lazy = lazy; rq.chain = chain; rq.n_chains = n_chains;
+  return rq;
 }
 
 // One step t >= 2 of a split range: dead_link_kernel for the whole batch on the engine's stream (dead_streams = 2: for each half of the
@@ -1296,135 +1290,79 @@ static size_t dead_lds_bytes(int n) {
 //   * the error flags are OR-ed atomically by both; the live waves read them only to decide their quiet word, which selects between
 //     two paths that give the same bits.
 static void launch_split_step(pedn_sim* s, int t) {
-  const int zg64 = zero_gate(s, s->zhw64, t), zg32 = zero_gate(s, s->zhw32, t - 1);
+  const pedn_plan::SplitPlan p = pedn_plan::plan_split_step(step_caps(s), s->marks, step_request(t, true, -1, s->dead_streams));
   const size_t lds = dead_lds_bytes(s->dead_waves);   // the lean kernel's share of the wave places
-  for (int c = 0; c < s->dead_streams; ++c) {
+  for (int c = 0; c < p.lean_launches; ++c) {
     hipStream_t stream;
-    DevView vd = view_of(s, s->dead_streams == 1 ? -1 : c, &stream);
-    vd.zg64 = zg64; vd.zg32 = zg32;
+    DevView vd = view_of(s, p.lean_launches == 1 ? -1 : c, &stream);
+    vd.zg64 = p.zg64; vd.zg32 = p.zg32;
     row_bases(vd, t);
     const unsigned waves = (unsigned)s->n_dead_pos * (unsigned)(vd.subRS / 64);
     if (waves > 0) hipLaunchKernelGGL(dead_link_kernel, dim3((waves + 3) / 4), dim3(256), lds, stream, vd, t, (const DeadRec*)s->d_dead_drec, s->n_dead_pos);
-    if (zg64 || zg32) ++s->zgated;
   }
-  if (s->n_live_blocks > 0) {
+  if (p.live) {
     DevView vn = s->v;
     vn.slot_rec = s->d_live_rec;
     vn.quiet = s->d_quiet_live;
     vn.quiet_npos = s->live_npos;
-    vn.quiet_use = s->quiet_valid == t - 1 && s->quiet_pack == 1;
-    vn.quiet_lean = s->quiet_lean ? 1 : 0;
+    vn.quiet_use = p.quiet_use;
+    vn.quiet_lean = p.quiet_lean ? 1 : 0;
     vn.rl_actions = nullptr;
-    vn.zg64 = zg64; vn.zg32 = zg32;
+    vn.zg64 = p.zg64; vn.zg32 = p.zg32;
     row_bases(vn, t);
     hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3((unsigned)(vn.RS / 64), (unsigned)s->n_live_blocks), dim3(512), s->node_lds_live, s->stream3, vn, t);
-    if (zg64 || zg32) ++s->zgated;
   }
-  ++s->split_steps;
-  s->link_pending = t;
-  s->quiet_valid = s->n_live_blocks > 0 ? t : -1;
-  s->quiet_pack = 1;
-  s->zhw64 = std::max(s->zhw64, t);
-  s->zhw32 = std::max(s->zhw32, t - 1);
-  s->second_launch = 0;
-  if (s->valid_hi != 0x7fffffff && t > s->valid_hi) s->valid_hi = s->v.valid_hi = t;
-  s->last_t = t;
-  ++s->step_epoch;
+  pedn_plan::commit_split_step(s->marks, p);
+  mirror_marks(s);
 }
 
-// lazy (owner-wave plan, pedn_run): the link update of t is left to node_kernel<LU>(t + 1) -- or to flush_links -- and this step's
-// node_kernel performs the pending one of t - 1.
-// cv != nullptr (observe >= 0): the observations are those of the last sub-step of a controlled env step -- the controller twin of the
-// second launch (ctrl_link_turn_kernel) also computes the next actions and adds the rewards to the episode sums
-static int launch_step(pedn_sim* s, int t, hipEvent_t* ev = nullptr, int observe = -1, bool* observed = nullptr,
-                       const double* fold_actions = nullptr, int half = -1, bool lazy = false, const CtrlView* cv = nullptr) {
-  // half = -1: the whole batch on the engine's stream; 0 / 1: the first / second half of the replicas on stream / stream2 (the
-  // caller, pedn_run, launches both halves of a step and does the per-step bookkeeping once, after the second one)
-  if (s->dl_dirty && half <= 0) dl_refresh(s);   // dead links: an input of the proof has changed since the last step
-  if (half < 0 && t - 1 > s->valid_hi) {   // a step that skips ahead after a lazy reset (chains: their callers do this before the fork)
+// One chain's launches of a step, as the planner names them (pedn_plan::plan_step: the flush of a pending link update, the stand-alone
+// turning fractions, node_kernel(t), the launch behind it), then the commit.  rq.chain = -1: the whole batch on the engine's stream; 0 / 1:
+// the first / second half of the replicas on stream / stream2 (the caller launches every chain of a step; the last one commits).
+// rq.profiled: every launch between the caller's start / stop events ev = {turn_prob, node, link} x 2.  *observed: the observations were part
+// of the second launch.
+static int launch_step(pedn_sim* s, const pedn_plan::StepRequest& rq, hipEvent_t* ev = nullptr, bool* observed = nullptr) {
+  const int t = rq.t;
+  if (s->dl_dirty && rq.chain <= 0) dl_refresh(s);   // dead links: an input of the proof has changed since the last step
+  if (rq.chain < 0 && t - 1 > s->marks.valid_hi) {   // a step that skips ahead after a lazy reset (chains: their callers do this before the fork)
     const int rc = catch_up(s, t - 1);
     if (rc != PEDN_OK) return rc;
   }
   hipStream_t stream;
-  DevView v = view_of(s, half, &stream);
-  // zero elision: the marks as they were before this step (a flush below raises zhw32 first, but then this node kernel is not the
-  // LU one and writes no row of num_pedestrians / density); both chains of a step decide alike, the marks are raised by the last one
-  const int zhw64 = s->zhw64, zhw32 = s->zhw32;
-  lazy = lazy && !s->node_lp && v.n_pairs_corr > 0;
-  // a pending link update is flushed when this is not the step it waits for, or when this step starts with the stand-alone turning
-  // fractions (they read num_pedestrians[t - 1] as stored)
-  // single-launch plan (inline_tf): node_kernel<LU, TF> computes the device-computed rows itself -- wherever it can be the LU kernel
-  const bool inl_plan = lazy && s->inline_tf && v.n_trow > 0;
-  const bool can_inl = inl_plan && s->link_pending == t - 1 && t >= 2;
-  const bool tf_alone = v.n_trow > 0 && s->tp_ready != t && !can_inl;
-  const bool flush_now = s->link_pending >= 0 && (!(lazy && s->link_pending == t - 1) || tf_alone);
-  const bool lu = lazy && s->link_pending == t - 1 && t >= 2 && !flush_now;   // (half 0 of a pair leaves link_pending as it is)
-  const bool inl = can_inl && lu;
-  if (flush_now) flush_links(s, half, nullptr);
+  DevView v = view_of(s, rq.chain, &stream);
+  const pedn_plan::StepPlan p = pedn_plan::plan_step(step_caps(s), s->marks, rq);
+  if (p.flush) flush_links(s, rq.chain, nullptr, p.commits);
   DevView vn = v;                 // node_kernel's view: with the action rows when it applies the gater actions itself
-  vn.rl_actions = fold_actions;
-  // quiet corridors: every node_kernel<LU> launch (not the single-launch plan's <LU, TF>) stores the words of step t; it uses those of
-  // t - 1 when the launch of t - 1 was one of them and nothing has touched the history since (quiet_valid)
-  const bool quiet = lu && !inl && s->quiet;
-  vn.quiet = quiet ? s->d_quiet : nullptr;
-  vn.quiet_use = quiet && s->quiet_valid == t - 1 && s->quiet_pack == 0;   // (the words of a split step belong to the live packing)
-  vn.quiet_lean = quiet && s->quiet_lean ? 1 : 0;
-  // zero elision: node_kernel(t) writes row t of the flows and cumulative counts, node_kernel<LU>(t) also row t - 1 of num_pedestrians /
-  // density (the link update behind an ordinary node kernel writes row t of those, ungated)
-  vn.zg64 = zero_gate(s, zhw64, t);
-  vn.zg32 = lu ? zero_gate(s, zhw32, t - 1) : 0;
-  if (vn.zg64 || vn.zg32) ++s->zgated;
+  vn.rl_actions = rq.fold;
+  vn.quiet = p.quiet ? s->d_quiet : nullptr;
+  vn.quiet_use = p.quiet_use;
+  vn.quiet_lean = p.quiet_lean ? 1 : 0;
+  vn.zg64 = p.zg64;
+  vn.zg32 = p.zg32;
   row_bases(vn, t);
-  // the turning fractions of t + 1 ride in the launch behind node_kernel(t) -- except behind the last step of the horizon, where
-  // pair_pod / turn_tab have no row T + 1 to read (they hold T + 1 rows, 0..T) and nothing would consume the result
-  // (and not under the single-launch plan, where the next step computes its own rows)
-  const bool groups = v.n_trow > 0, fused = groups && s->fuse_tp && t + 1 <= v.T1 - 1 && !inl_plan;
-  const bool obs_fused = observe >= 0 && s->rl_ready && s->fuse_obs;
   auto launch = [&](auto kernel, dim3 grid, dim3 block, int e, auto... args) {
-    if (ev) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ev[e], ev[e + 1], 0, args...);
+    if (rq.profiled) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ev[e], ev[e + 1], 0, args...);
     else hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
   };
-  // link update: one replica per lane as a launch of its own and with per-replica parameters, two inside link_turn_kernel (link_body)
-  const bool one_r = v.pr || (!fused && !obs_fused);
-  // (lazy: no link-update workgroups in this step's second launch)
-  const StepGrid g(s, v, lazy ? 0u : link_blocks(v, one_r), fused, obs_fused);
-  if (tf_alone) {  // first step of an episode, a repeated or an out-of-order step
-    launch(turn_frac_kernel_for(v), dim3(g.tf_blocks(v)), dim3(256), 0, v, t);
-    s->tp_ran = 1;
-  }
-  const size_t nlds = inl ? s->node_lds_tf : s->node_lds;
-  const dim3 nblock(inl && s->inline_help ? 1024 : 512);   // helper waves: sixteen per workgroup
-  if (ev) hipExtLaunchKernelGGL(node_kernel_for(s, lu, inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, ev[2], ev[3], 0, vn, t);
-  else hipLaunchKernelGGL(node_kernel_for(s, lu, inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, vn, t);
-  if (inl && last_chain(s, half)) s->tp_ready = t;   // the fractions of t are in tfd[t & 1] (a following step that cannot inline computes its own)
-  if (last_chain(s, half)) {
-    s->link_pending = lazy ? t : -1;
-    s->quiet_valid = quiet ? t : -1;
-    s->quiet_pack = 0;
-    s->dl_grow = false;   // something has run since the last full reset
-    s->zhw64 = std::max(s->zhw64, t);
-    if (lu) s->zhw32 = std::max(s->zhw32, t - 1);
-    if (g.nlb > 0) s->zhw32 = std::max(s->zhw32, t);   // the link update of t below
-  }
-  s->second_launch = 1;
-  if (fused || obs_fused) {
+  const StepGrid g(s, v, p.link ? link_blocks(v, p.one_r) : 0u, p.fused, p.obs);
+  if (p.tf_alone) launch(turn_frac_kernel_for(v), dim3(g.tf_blocks(v)), dim3(256), 0, v, t);
+  const size_t nlds = p.inl ? s->node_lds_tf : s->node_lds;
+  const dim3 nblock(p.helpers ? 1024 : 512);   // helper waves: sixteen per workgroup
+  if (rq.profiled) hipExtLaunchKernelGGL(node_kernel_for(s, p.lu, p.inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, ev[2], ev[3], 0, vn, t);
+  else hipLaunchKernelGGL(node_kernel_for(s, p.lu, p.inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, vn, t);
+  if (p.second == pedn_plan::SECOND_LINK_TURN) {
     RlView q = s->rl;
-    if (!obs_fused) q.n_agents = 0;
-    const int acc = observe > 0 ? 1 : 0;
+    if (!p.obs) q.n_agents = 0;
+    const int acc = rq.observe > 0 ? 1 : 0;
     const dim3 block(256);
-    if (obs_fused && cv) launch(ctrl_link_turn_kernel_for(v), g.second(), block, 4, v, t, g.nlb, g.ntb, g.nth, q, acc, *cv);
-    else launch(link_turn_kernel_for(v, obs_fused, false), g.second(), block, 4, v, t, g.nlb, g.ntb, g.nth, q, acc);
-    if (fused && last_chain(s, half)) s->tp_ready = t + 1;   // the other chains of this step still have to see the old value
-  } else if (g.nlb > 0) {
-    launch_link_update(s, v, stream, t, ev, 4);
+    if (p.ctrl) launch(ctrl_link_turn_kernel_for(v), g.second(), block, 4, v, t, g.nlb, g.ntb, g.nth, q, acc, *rq.ctrl);
+    else launch(link_turn_kernel_for(v, p.obs, false), g.second(), block, 4, v, t, g.nlb, g.ntb, g.nth, q, acc);
+  } else if (p.second == pedn_plan::SECOND_LINK) {
+    launch_link_update(s, v, stream, t, rq.profiled ? ev : nullptr, 4);
   }
-  else s->second_launch = 0;
-  if (observed) *observed = obs_fused;
-  if (last_chain(s, half)) {
-    if (s->valid_hi != 0x7fffffff && t > s->valid_hi) s->valid_hi = s->v.valid_hi = t;   // rows <= t are written once this step's launches are
-    s->last_t = t;
-    ++s->step_epoch;
-  }
+  if (observed) *observed = p.obs;
+  pedn_plan::commit_step(s->marks, p);
+  mirror_marks(s);
   return PEDN_OK;
 }
 
@@ -1438,7 +1376,7 @@ int pedn_step(pedn_sim* s, int32_t t) {
   // from the third consecutive step that nothing looked at, the halves of the replicas step on two streams and STAY forked across the
   // calls (like pedn_rl_step's chains); whatever reads or changes the state next joins them (join_forked, as after an RL step).
   // melbourne x 1024 in a Python loop: 32.6 -> 28.9 us per step, delft 48.9 -> 43.9 (pedn_run: 28.6 / 43.4).
-  const bool in_sequence = !s->touched && t == s->last_t + 1 && s->chains > 1 && s->warmed_chains >= 2 && s->v.RS >= 256;
+  const bool in_sequence = !s->touched && t == s->marks.last_t + 1 && s->chains > 1 && s->warmed_chains >= 2 && s->v.RS >= 256;
   s->step_streak = in_sequence ? std::min(s->step_streak + 1, 2) : 0;
   const bool two = s->step_streak >= 2;
   if (!two) join_forked(s);
@@ -1452,16 +1390,14 @@ int pedn_step(pedn_sim* s, int32_t t) {
   s->touched = 0;
   if (two) {
     if (!s->forked) {
-      if (s->link_pending >= 0 && s->link_pending != t - 1) { pending_links_first(s); s->touched = 0; }   // a stale pending update: whole batch, before the fork
-      if (t - 1 > s->valid_hi && (rc = catch_up(s, t - 1)) != PEDN_OK) return rc;
+      if (s->marks.link_pending >= 0 && s->marks.link_pending != t - 1) { pending_links_first(s); s->touched = 0; }   // a stale pending update: whole batch, before the fork
+      if (t - 1 > s->marks.valid_hi && (rc = catch_up(s, t - 1)) != PEDN_OK) return rc;
       if ((rc = fork_chains(s, 2)) != PEDN_OK) return rc;
       s->forked = 1;
     }
-    s->run_chains = 2;
-    for (int c = 0; c < 2 && rc == PEDN_OK; ++c) rc = launch_step(s, t, nullptr, -1, nullptr, nullptr, c, lazy);
-    s->run_chains = 1;
+    for (int c = 0; c < 2 && rc == PEDN_OK; ++c) rc = launch_step(s, step_request(t, lazy, c, 2));
     if (rc != PEDN_OK) return rc;
-  } else if ((rc = launch_step(s, t, nullptr, -1, nullptr, nullptr, -1, lazy)) != PEDN_OK) return rc;
+  } else if ((rc = launch_step(s, step_request(t, lazy))) != PEDN_OK) return rc;
   HIP_TRY(s, hipGetLastError());
   return PEDN_OK;
 }
@@ -1475,14 +1411,16 @@ int pedn_profile_step(pedn_sim* s, int32_t t, float ms[3]) {
   // not the enqueue-to-completion interval an ordinary hipEventRecord bracket would measure.
   hipEvent_t ev[6];
   for (int i = 0; i < 6; ++i) HIP_TRY(s, hipEventCreate(&ev[i]));
-  s->tp_ran = 0;
-  launch_step(s, t, ev);
+  pedn_plan::profile_begin(s->marks);
+  pedn_plan::StepRequest rq = step_request(t, false);
+  rq.profiled = true;
+  launch_step(s, rq, ev);
   HIP_TRY(s, hipGetLastError());
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   ms[0] = ms[1] = ms[2] = 0.0f;
-  if (s->tp_ran) HIP_TRY(s, hipEventElapsedTime(&ms[0], ev[0], ev[1]));  // stand-alone turn probabilities (normally fused into [2])
+  if (s->marks.tp_ran) HIP_TRY(s, hipEventElapsedTime(&ms[0], ev[0], ev[1]));  // stand-alone turn probabilities (normally fused into [2])
   HIP_TRY(s, hipEventElapsedTime(&ms[1], ev[2], ev[3]));
-  if (s->second_launch) HIP_TRY(s, hipEventElapsedTime(&ms[2], ev[4], ev[5]));
+  if (s->marks.second_launch) HIP_TRY(s, hipEventElapsedTime(&ms[2], ev[4], ev[5]));
   for (int i = 0; i < 6; ++i) hipEventDestroy(ev[i]);
   return PEDN_OK;
 }
@@ -1533,27 +1471,25 @@ int pedn_run(pedn_sim* s, int32_t t0, int32_t t1) {
   join_forked(s);
   const int nch = chains_for(s, t0, t1);
   if (nch > 1) {
-    if (s->link_pending >= 0 && s->link_pending != t0 - 1) pending_links_first(s);   // a stale pending update: on the whole batch, before the fork
-    if (t0 - 1 > s->valid_hi && (rc = catch_up(s, t0 - 1)) != PEDN_OK) return rc;
+    if (s->marks.link_pending >= 0 && s->marks.link_pending != t0 - 1) pending_links_first(s);   // a stale pending update: on the whole batch, before the fork
+    if (t0 - 1 > s->marks.valid_hi && (rc = catch_up(s, t0 - 1)) != PEDN_OK) return rc;
     // Dead-link plan: the first node launch of the range on the whole batch and the full bin set, in front of the fork; every later one
     // is a node_kernel<LU> launch with quiet words and is split (launch_split_step) -- no event between the streams inside the range; with
     // one lean launch per step (dead_streams = 1) the second chain's stream has no work and is neither forked nor joined
     const bool split = nch == 2 && lazy && dl_split_ok(s);
     int t = t0;
-    if (split && (rc = launch_step(s, t++, nullptr, -1, nullptr, nullptr, -1, lazy)) != PEDN_OK) return rc;
+    if (split && (rc = launch_step(s, step_request(t++, lazy))) != PEDN_OK) return rc;
     const int idle = split && s->dead_streams == 1 ? 1 : -1;
     if ((rc = fork_chains(s, split ? 3 : nch, idle)) != PEDN_OK) return rc;
-    s->run_chains = nch;
     for (; t < t1; ++t) {
       if (split) launch_split_step(s, t);
-      else for (int c = 0; c < nch; ++c) launch_step(s, t, nullptr, -1, nullptr, nullptr, c, lazy);
+      else for (int c = 0; c < nch; ++c) launch_step(s, step_request(t, lazy, c, nch));
     }
-    s->run_chains = 1;
     rc = join_chains(s, split ? 3 : nch, idle);    // the last step's link update stays pending on the joined stream (pending_links_first)
     if (rc != PEDN_OK) return rc;
   } else {
     for (int t = t0; t < t1; ++t)
-      if ((rc = launch_step(s, t, nullptr, -1, nullptr, nullptr, -1, lazy)) != PEDN_OK) return rc;
+      if ((rc = launch_step(s, step_request(t, lazy))) != PEDN_OK) return rc;
   }
   HIP_TRY(s, hipGetLastError());
   return PEDN_OK;
@@ -1568,10 +1504,10 @@ int pedn_plan_info(pedn_sim* s, int32_t* info, int32_t n) {
   if (n >= 5) info[4] = s->packed_by;   // bins of node_kernel packed by 0 degree, 1 the static load estimate, 2 measured node cost
   if (n >= 6) info[5] = s->quiet && info[1];   // the owner-wave launches keep and use the quiet-corridor words (PEDN_QUIET)
   if (n >= 7) info[6] = s->zero_elide && !s->v.hist;   // the node kernels may skip +0.0 stores into clean rows (PEDN_ZERO_ELIDE)
-  if (n >= 8) info[7] = s->zgated;   // ... and this many node-kernel launches had a gate open since the last reset
+  if (n >= 8) info[7] = s->marks.zgated;   // ... and this many node-kernel launches had a gate open since the last reset
   if (n >= 9) info[8] = s->quiet_lean && s->quiet && info[1];   // the quiet-corridor launches take the lean path (PEDN_QUIET_LEAN)
   if (n >= 10) info[9] = dl_split_ok(s) ? s->n_dead_links : 0;   // links that dead_link_kernel steps in a two-chain range (PEDN_DEAD_LINKS)
-  if (n >= 11) info[10] = s->split_steps;   // ... and the steps that were launched that way since the last reset
+  if (n >= 11) info[10] = s->marks.split_steps;   // ... and the steps that were launched that way since the last reset
   return PEDN_OK;
 }
 
@@ -1612,22 +1548,22 @@ static int profile_range(pedn_sim* s, int t0, int t1, std::vector<ProfRow>& rows
   for (auto& e : ev) HIP_TRY(s, hipEventCreate(&e));
   std::vector<int> tp_ran((size_t)n, 0), second((size_t)n, 0);
   if (two) {
-    if (s->link_pending >= 0 && s->link_pending != t0 - 1) pending_links_first(s);
+    if (s->marks.link_pending >= 0 && s->marks.link_pending != t0 - 1) pending_links_first(s);
     int rc = PEDN_OK;
-    if (t0 - 1 > s->valid_hi && (rc = catch_up(s, t0 - 1)) != PEDN_OK) return rc;
+    if (t0 - 1 > s->marks.valid_hi && (rc = catch_up(s, t0 - 1)) != PEDN_OK) return rc;
     if ((rc = fork_chains(s, halves)) != PEDN_OK) return rc;
-    s->run_chains = halves;
   }
   for (int t = t0, k = 0; t < t1; ++t)
     for (int h = 0; h < halves; ++h, ++k) {
-      s->tp_ran = 0;
-      launch_step(s, t, &ev[(size_t)k * 6], -1, nullptr, nullptr, two ? h : -1, lazy);
-      tp_ran[k] = s->tp_ran;
-      second[k] = s->second_launch;
+      pedn_plan::profile_begin(s->marks);
+      pedn_plan::StepRequest rq = step_request(t, lazy, two ? h : -1, halves);
+      rq.profiled = true;
+      launch_step(s, rq, &ev[(size_t)k * 6]);
+      tp_ran[k] = s->marks.tp_ran;
+      second[k] = s->marks.second_launch;
     }
-  const bool flushed = s->link_pending >= 0;
-  for (int h = 0; h < halves; ++h) flush_links(s, two ? h : -1, &ev[(size_t)(n + h) * 6]);
-  s->run_chains = 1;
+  const bool flushed = s->marks.link_pending >= 0;
+  for (int h = 0; h < halves; ++h) flush_links(s, two ? h : -1, &ev[(size_t)(n + h) * 6], h == halves - 1);
   if (two) {
     const int rc = join_chains(s, halves);
     if (rc != PEDN_OK) return rc;
@@ -1726,7 +1662,7 @@ int pedn_read(pedn_sim* s, int32_t field, int32_t t0, int32_t t1, int32_t c0, in
   const int rows = field < 7 ? s->rows64[field] : s->rows32[field - 7], mask = field < 7 ? v.m64[field] : v.m32[field - 7];
   if (rows < v.T1) {  // recent-history mode: only the newest `rows` time indices of this field exist
     // sending_flow / receiving_flow of step t are entries t - 1 (node.py:206, link.py:367): their newest entry is one behind
-    const int newest = std::max((field == F_S || field == F_R) ? s->last_t - 1 : s->last_t, 0);
+    const int newest = std::max((field == F_S || field == F_R) ? s->marks.last_t - 1 : s->marks.last_t, 0);
     if (t1 - 1 > newest || t0 <= newest - rows)
       return fail(s, PEDN_E_ARG, "time index outside the field's ring (recent-history mode keeps the last " + std::to_string(rows) +
                                  " entries of this field; the newest is " + std::to_string(newest) + ")");
@@ -1743,8 +1679,8 @@ int pedn_read(pedn_sim* s, int32_t field, int32_t t0, int32_t t1, int32_t c0, in
   // lazy reset: rows that were neither written nor cleared since the reset read as their initial value.  sending / receiving flow of
   // step t are entries t - 1; the gate record and avg_travel_time below the window were restored by the reset itself.
   int hi = 0x7fffffff;
-  if (s->valid_hi != 0x7fffffff) {
-    hi = s->valid_hi;
+  if (s->marks.valid_hi != 0x7fffffff) {
+    hi = s->marks.valid_hi;
     if (field == F_S || field == F_R) hi = std::max(hi - 1, 0);
     else if (field == F_GATE) hi = 0x7fffffff;
     else if (field == 7 + G_ATT) hi = std::max(hi, v.W - 1);
@@ -1770,21 +1706,21 @@ int pedn_flush(pedn_sim* s) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);   // joins forked chains, ends a clocked section, performs a pending link update -- all on pedn_stream()
-  if (s->valid_hi != 0x7fffffff) {   // a zero-copy consumer may look at any row: finish what a lazy reset left out
+  if (s->marks.valid_hi != 0x7fffffff) {   // a zero-copy consumer may look at any row: finish what a lazy reset left out
     const int rc = catch_up(s, s->v.T1 - 1);
     if (rc != PEDN_OK) return rc;
-    s->valid_hi = s->v.valid_hi = 0x7fffffff;
+    pedn_plan::caught_up(s->marks, pedn_plan::ALL_ROWS);
+    mirror_marks(s);
   }
   return PEDN_OK;
 }
 
 void* pedn_device_ptr(pedn_sim* s, int32_t field, int64_t* columns, int64_t* replica_stride) {
   if (!s || field < 0 || field >= PEDN_N_FIELDS) return nullptr;
-  if ((s->link_pending >= 0 || s->forked || s->clocked || s->valid_hi != 0x7fffffff) && pedn_flush(s) != PEDN_OK) return nullptr;
+  if ((s->marks.link_pending >= 0 || s->forked || s->clocked || s->marks.valid_hi != 0x7fffffff) && pedn_flush(s) != PEDN_OK) return nullptr;
   // zero elision: a zero-copy consumer may write any row of the field -- no gate on its group until the next full reset
-  s->dl_off = true;   // dead links: ... and no split plan either
-  if (field <= F_CO) s->zhw64 = 0x7fffffff;
-  if (field == 7 + G_N || field == 7 + G_K || field == 7 + G_LF) s->zhw32 = 0x7fffffff;
+  // (dead links: ... and no split plan either)
+  pedn_plan::foreign_write(s->marks, field <= F_CO, field == 7 + G_N || field == 7 + G_K || field == 7 + G_LF);
   if (columns) *columns = field < 4 ? s->v.Lall : s->v.L;
   if (replica_stride) *replica_stride = s->v.RS;
   return field < 7 ? (void*)s->v.f64[field] : (void*)s->v.f32[field - 7];
@@ -1818,7 +1754,7 @@ int pedn_timer_end(pedn_sim* s, float* ms) {
 int pedn_set_link_params(pedn_sim* s, const double* kc, const double* kj, const double* vf, const int32_t* fft, const int32_t* tau_sw,
                          const float* tt0) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
-  s->tp_ready = -1;
+  pedn_plan::fractions_invalid(s->marks);
   s->dl_dirty = true;
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
@@ -1892,7 +1828,7 @@ int pedn_set_od_weights_per_replica(pedn_sim* s, const double* w) {
   pending_links_first(s);
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   DevView& v = s->v;
-  s->tp_ready = -1;
+  pedn_plan::fractions_invalid(s->marks);
   s->dl_dirty = true;
   if (!w) {
     v.pod_pr = 0;
@@ -1922,7 +1858,7 @@ int pedn_randomize_scenarios(pedn_sim* s, uint64_t seed, double link_fraction, i
   HIP_TRY(s, hipSetDevice(s->device));
   DevView& v = s->v;
   pending_links_first(s);
-  s->tp_ready = -1;
+  pedn_plan::fractions_invalid(s->marks);
   s->dl_dirty = true;
   const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
   int rc;
@@ -2136,7 +2072,7 @@ static int rl_observe(pedn_sim* s, int32_t t, int32_t accumulate, float* obs, fl
   if (t < 0 || t > s->v.T1 - 1) return fail(s, PEDN_E_ARG, "time step outside 0..T");
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);
-  if (t > s->valid_hi) catch_up(s, t);   // observations of a step that has not run read its rows as they were initialised
+  if (t > s->marks.valid_hi) catch_up(s, t);   // observations of a step that has not run read its rows as they were initialised
   DevView& v = s->v;
   RlView& q = s->rl;
   const dim3 grid((unsigned)q.n_agents * (unsigned)(v.RS / 64));
@@ -2184,7 +2120,7 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
   const double* fold = nullptr;
   pedn_sim::Stage* fold_stage = nullptr;   // host actions read in place by node_kernel of the first sub-step (stage_in_place)
   if (actions) {
-    const bool stand_alone_tf = s->v.n_trow > 0 && s->tp_ready != t;
+    const bool stand_alone_tf = s->v.n_trow > 0 && s->marks.tp_ready != t;
     if (s->rl_fold && !stand_alone_tf) {
       HIP_TRY(s, hipSetDevice(s->device));
       if (on_device) fold = actions;
@@ -2206,7 +2142,7 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
   // (45_intersections x 2048: 25.0 -> 22.x us per env step).  Only when nothing of this call runs on the engine's stream alone: the
   // actions are applied inside node_kernel (or there are none) and the observations ride in the second launch.
   // (actions from the host go through the engine's own action buffer, which the other chain's previous step may still be reading)
-  if (t - 1 > s->valid_hi) {   // skipping ahead after a lazy reset
+  if (t - 1 > s->marks.valid_hi) {   // skipping ahead after a lazy reset
     join_forked(s);
     if ((rc = catch_up(s, t - 1)) != PEDN_OK) return rc;
   }
@@ -2215,7 +2151,7 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
   // everything must then be ordered by the engine's stream alone
   const int term = t + action_gap - 1 >= s->v.T1 - 1 ? 1 : 0;   // pz_pednet_env.py:592
   const bool two = !s->norm.on && on_device != 2 && (s->rl_chains == 2 || (s->rl_chains == 0 && by_batch)) && s->warmed_chains >= 2 && s->v.RS >= 256 && s->fuse_obs && (!actions || (fold != nullptr && on_device)) && !obs && !rewards &&
-                   s->link_pending < 0 && !(s->v.n_trow > 0 && !s->fuse_tp);
+                   s->marks.link_pending < 0 && !(s->v.n_trow > 0 && !s->fuse_tp);
   if (!two) join_forked(s);
   else if (!s->forked) {
     if ((rc = fork_chains(s, 2)) != PEDN_OK) return rc;
@@ -2227,13 +2163,15 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
     // (always two launches per env step: the observations are a second launch either way, and with the rows of t + 1 riding in it the
     // two launches are shorter than the single-launch / owner-wave plans -- profiles/r04_rl_small_batches.txt, r04_rl_owner.txt)
     const CtrlView* ck = last ? cv : nullptr;
+    pedn_plan::StepRequest rq = step_request(t + k, false, -1, two ? 2 : 1);
+    rq.observe = k > 0 ? 1 : 0;
+    rq.fold = k == 0 ? fold : nullptr;
+    rq.ctrl = ck;
     if (two) {
-      s->run_chains = 2;
-      for (int c = 0; c < 2; ++c) launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, c, false, ck);
-      s->run_chains = 1;
+      for (rq.chain = 0; rq.chain < 2; ++rq.chain) launch_step(s, rq, nullptr, &observed);
       if ((last && (obs || rewards)) || !observed) join_forked(s);
     } else {
-      if ((rc = launch_step(s, t + k, nullptr, k > 0 ? 1 : 0, &observed, k == 0 ? fold : nullptr, -1, false, ck)) != PEDN_OK) return rc;
+      if ((rc = launch_step(s, rq, nullptr, &observed)) != PEDN_OK) return rc;
     }
     if (k == 0 && fold_stage && (rc = stage_commit(s, fold_stage)) != PEDN_OK) return rc;   // its only reader has been launched
     HIP_TRY(s, hipGetLastError());
@@ -2252,19 +2190,12 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
 static int clock_end(pedn_sim* s) {
   if (!s->clocked) return PEDN_OK;
   s->clocked = false;
-  no_quiet(s);
   // the clocked steps may sit on a caller's stream (or in a graph replayed on one): everything on the device first
   HIP_TRY(s, hipDeviceSynchronize());
   int32_t h[4] = {0, 0, 0, 0};
   HIP_TRY(s, hipMemcpy(h, s->d_clock, sizeof(h), hipMemcpyDeviceToHost));
-  const int t_now = h[0];
-  if (t_now > s->clock_t0) {   // steps clock_t0 .. t_now - 1 ran
-    s->last_t = t_now - 1;
-    s->step_epoch += t_now - s->clock_t0;
-    s->tp_ready = (s->v.n_trow > 0 && t_now <= s->v.T1 - 1) ? t_now : -1;   // link_turn_kernel(t_now - 1) left the fractions of t_now
-    s->link_pending = -1;
-  }
-  s->valid_hi = s->v.valid_hi = h[2];
+  pedn_plan::clock_ended(s->marks, step_caps(s), s->clock_t0, h[0], h[2]);
+  mirror_marks(s);
   return PEDN_OK;
 }
 
@@ -2277,18 +2208,17 @@ int pedn_rl_clock_begin(pedn_sim* s, int32_t t) {
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);   // (ends a clocked section that is still open)
   int rc;
-  if (t - 1 > s->valid_hi && (rc = catch_up(s, t - 1)) != PEDN_OK) return rc;
+  if (t - 1 > s->marks.valid_hi && (rc = catch_up(s, t - 1)) != PEDN_OK) return rc;
   // The fractions of step t must be in place: the stand-alone launch that would compute them reads the gate widths AFTER the actions of
   // step t are applied (capacity fallback, path_finder.py:575-576) -- only the ordinary pedn_rl_step can order that.  True for every
   // step but the first one after a reset or a setter.
-  if (s->v.n_trow > 0 && s->tp_ready != t)
+  if (s->v.n_trow > 0 && s->marks.tp_ready != t)
     return fail(s, PEDN_E_ARG, "turning fractions of step " + std::to_string(t) + " are not prepared: run this step with pedn_rl_step first");
-  hipLaunchKernelGGL(set_clock_kernel, dim3(1), dim3(64), 0, s->stream, s->d_clock, t, s->valid_hi);
+  hipLaunchKernelGGL(set_clock_kernel, dim3(1), dim3(64), 0, s->stream, s->d_clock, t, s->marks.valid_hi);
   HIP_TRY(s, hipGetLastError());
   s->clocked = true;
   s->clock_t0 = t;
-  s->zhw64 = s->zhw32 = 0x7fffffff;   // zero elision: the host does not see which rows the clocked steps write (until the next full reset)
-  s->dl_off = true;                   // ... and no dead-link plan
+  pedn_plan::foreign_write(s->marks, true, true);   // the host does not see which rows the clocked steps write: no zero gate, no dead-link plan
   return PEDN_OK;
 }
 
@@ -2363,7 +2293,7 @@ int pedn_rl_clock_end(pedn_sim* s, int32_t* t) {
   HIP_TRY(s, hipSetDevice(s->device));
   const int rc = clock_end(s);
   if (rc != PEDN_OK) return rc;
-  if (t) *t = s->last_t + 1;
+  if (t) *t = s->marks.last_t + 1;
   return PEDN_OK;
 }
 

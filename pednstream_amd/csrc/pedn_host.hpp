@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "pedn_kernels.hpp"
+#include "pedn_plan.hpp"
 
 static thread_local std::string g_last_error;
 
@@ -65,36 +66,23 @@ struct pedn_sim {
   int32_t* d_clock = nullptr;
   bool clocked = false;
   int clock_t0 = 0;   // step the clock was set to by pedn_rl_clock_begin
-  int valid_hi = 0x7fffffff;   // lazy reset: history rows above this index are neither written nor cleared (DevView.valid_hi)
-  int link_pending = -1;  // owner-wave plan: step whose link update has not been performed yet, -1 none
+  // The marks: what the host knows of the device's state between two launches.  Read by the step planner, advanced by its commits and
+  // transitions alone (pedn_plan.hpp); marks.valid_hi is mirrored into v.valid_hi (mirror_marks).
+  pedn_plan::StepState marks;
   // Quiet corridors (DevView.quiet): node_kernel<LU> launches store the words (PEDN_QUIET=0|1, default wherever link_owner is chosen);
-  // quiet_valid = the step whose words every replica group has, from a node_kernel<LU> launch on each chain with no change of a history
-  // row since -- the next LU launch may use them; -1 none.  Cleared by everything that could break that (no_quiet).
+  // which step's words may be used: marks.quiet_valid
   int quiet = 0;
-  int quiet_valid = -1;
   int quiet_lean = 1;   // PEDN_QUIET_LEAN=0|1 (default on): those launches skip the node work that all-zero flows fix (DevView.quiet_lean)
   uint32_t* d_quiet = nullptr;
-  // Zero elision (DevView.zg64 / zg32; PEDN_ZERO_ELIDE=0|1, default on): zhw64 = the highest row of inflow / outflow / cumulative_inflow /
-  // cumulative_outflow, zhw32 = of num_pedestrians / density / link_flow, that may hold anything but +0.0 -- -1 after a full reset (which
-  // leaves every row at +0.0), kept by the lazy reset (the old episode's rows stay), INT_MAX when something the host does not follow may write them
-  // (a zero-copy pointer, the clocked steps) until the next full reset.  A launch that writes row x of a group gets the gate iff
-  // x > the group's mark; the mark is raised to x once the step is enqueued (both chains of a step decide from the marks before it).
-  // Only zeros are ever written below the marks' back (clear_rows, catch_up), so they need not raise them.
-  int zero_elide = 1;
-  int zhw64 = 0x7fffffff, zhw32 = 0x7fffffff;
-  int zgated = 0;   // node-kernel launches with a gate open since the last reset of either kind (pedn_plan_info info[7])
+  int zero_elide = 1;   // zero elision (DevView.zg64 / zg32; PEDN_ZERO_ELIDE=0|1, default on): the marks are marks.zhw64 / zhw32
   // Dead links (pedn_partition.hpp; PEDN_DEAD_LINKS=0|1, default on): in a two-chain range of pedn_run the nodes that provably never see
   // a pedestrian are stepped by dead_link_kernel -- one launch per step for the whole batch on the engine's stream (dead_streams = 2: one
   // per half on the two chain streams) -- and node_kernel<LU> runs over a second packing of the other (live) nodes only, for the whole
   // batch, on a third stream (launch_split_step).
   //   dl_dirty  an input of the proof has changed (or nothing was computed yet): dl_refresh recomputes before the next split range
-  //   dl_grow   nothing has run since the last FULL reset: the recomputed set replaces the old one; otherwise it is intersected with it
-  //             (rows above valid_hi may hold a previous episode's values, and a link that ever carried someone holds them anywhere)
-  //   dl_off    something the host does not follow may have written a state or history field (a zero-copy pointer, the clocked steps):
-  //             no split until the next full reset -- the events that set zhw64 / zhw32 to INT_MAX
-  //   quiet_pack  which packing's quiet words quiet_valid speaks of: 0 the full bin set (d_quiet), 1 the live bins (d_quiet_live)
+  //   (marks.dl_grow, marks.dl_off: whether a recomputed set may grow, whether the plan is off until the next full reset)
   int dead_links = 1;
-  bool dl_dirty = true, dl_grow = true, dl_off = false;
+  bool dl_dirty = true;
   std::vector<char> dl_node;           // [nodes] 1: stepped by dead_link_kernel
   // what the earlier proofs since the last full reset took for sources and found reachable: pedestrians that entered under them are
   // still walking when a demand row is zeroed or a turn closed behind them, so both stay sources of every later proof (dl_refresh)
@@ -105,7 +93,6 @@ struct pedn_sim {
   std::vector<int32_t> h_pack_order;   // nodes in the order the bins were packed in (pedn_compile::Tables::pack_order; dl_refresh repacks in it)
   std::vector<int32_t> h_link_sep, h_link_tau_sw, h_link_rev, h_node_kind, h_slot_in, h_slot_out;
   int n_dead_links = 0, n_dead_pos = 0, n_live_blocks = 0, live_npos = 0;
-  int split_steps = 0;                 // steps launched by launch_split_step since the last reset of either kind (pedn_plan_info info[10])
   size_t node_lds_live = 0;
   SlotRec* d_live_rec = nullptr;       // the live packing's slot records (capacity: the full packing's)
   SlotRec* d_dead_rec = nullptr;       // the records of the slots dead_link_kernel steps (copies, in work-list order): dead_prep_kernel's input
@@ -117,7 +104,6 @@ struct pedn_sim {
   int dead_waves = 5;
   int dead_streams = 1;                // PEDN_DEAD_STREAMS=1|2: one lean launch per step for the whole batch, or one per half on the chain streams
   uint32_t* d_quiet_live = nullptr;
-  int quiet_pack = 0;
   hipStream_t stream3 = nullptr;       // the live bins' stream; null: not seen to overlap with the chains (no split)
   hipEvent_t ev_join3 = nullptr;
   int fuse_obs = 1;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
@@ -130,14 +116,10 @@ struct pedn_sim {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int warmed_chains = 1;  // chains whose streams exist and were probed to overlap
   int chains = 1;         // plan of pedn_run for long ranges: 1 or 2 chains of launches (two_streams = chains > 1)
-  int run_chains = 1;     // chains of the range being launched (launch_step / flush_links: the last chain does the bookkeeping)
   int stream_probe_attempts = 0;   // warm_chain_streams: probes run until the chains' streams were seen to overlap
   float stream_probe_ms = 0.0f;
   int two_streams = 0;    // pedn_run launches the two halves of the batch on two streams (replicas are independent)
-  int second_launch = 0;  // launch_step: a launch followed node_kernel
   int fuse_tp = 0;     // the link update and the next step's turn probabilities share one launch (launch_step)
-  int tp_ran = 0;      // launch_step launched the stand-alone turn_frac_kernel (pedn_profile_step)
-  int tp_ready = -1;   // step whose turning fractions are in tfd[step & 1] (written by link_turn_kernel of the step before), -1: none
   std::vector<int32_t> node_turn_ptr, node_demand_row;
   std::vector<int32_t> h_up_od_ptr, h_upod_od, h_pair_upod;  // route-choice tables needed to re-tabulate P(od | up)
   std::vector<double> h_od_w;
@@ -170,10 +152,8 @@ struct pedn_sim {
   int* d_max_tau = nullptr;
   int n_pair = 0, n_up = 0, n_over = 0;
   int n_tf_heavy_quads = 0;  // leading workgroups of turn_frac_body with long chains (more than PEDN_TF_HEAVY_GROUPS softmax groups in a row)
-  long step_epoch = 1;  // counts launched steps; h_tf_set_epoch[node] == step_epoch: fractions imposed since the last step
-  std::vector<long> h_tf_set_epoch;
+  std::vector<long> h_tf_set_epoch;   // [nodes] marks.step_epoch when fractions were last imposed on the node
   int rows64[7], rows32[6];  // history rows of every field (T+1, or the size of its ring in recent-history mode)
-  int last_t = -1;     // last step launched (pedn_get_turning_fractions: which buffer holds a dynamic node's fractions)
   std::vector<void*> allocs;
   // host <-> device staging: two slots used in turn, each a pinned host buffer + a device buffer + the event recorded behind
   // the slot's last consumer, so that an upload neither waits for the stream nor borrows caller memory beyond the call
@@ -189,12 +169,19 @@ struct pedn_sim {
   ReplayState rp;
 };
 
-// the quiet words of the last step may not be used by the next launch (pedn_sim.quiet_valid)
-static inline void no_quiet(pedn_sim* s) { s->quiet_valid = -1; }
-
-// zero elision: may a launch that writes row `row` of a group whose mark is `hw` skip its +0.0 stores (pedn_sim.zhw64 / zhw32)?
-// (recent-history mode: ring rows are reused, never)
-static inline int32_t zero_gate(const pedn_sim* s, int hw, int row) { return s->zero_elide && !s->v.hist && row > hw ? 1 : 0; }
+// what the step planner reads of the handle (pedn_plan.hpp)
+static inline pedn_plan::StepCaps step_caps(const pedn_sim* s) {
+  pedn_plan::StepCaps c;
+  c.node_lp = s->node_lp; c.inline_tf = s->inline_tf != 0; c.inline_help = s->inline_help != 0;
+  c.quiet = s->quiet != 0; c.quiet_lean = s->quiet_lean != 0;
+  c.fuse_tp = s->fuse_tp != 0; c.fuse_obs = s->fuse_obs != 0; c.rl_ready = s->rl_ready;
+  c.zero_elide = s->zero_elide != 0; c.hist = s->v.hist != 0; c.pr = s->v.pr != 0;
+  c.trow = s->v.n_trow > 0; c.links = s->v.n_pairs_corr > 0; c.live = s->n_live_blocks > 0;
+  c.T1 = s->v.T1;
+  return c;
+}
+// DevView.valid_hi follows the marks: behind every commit or transition that may move marks.valid_hi
+static inline void mirror_marks(pedn_sim* s) { s->v.valid_hi = s->marks.valid_hi; }
 
 static int fail(pedn_sim* s, int code, const std::string& msg) {
   g_last_error = msg;

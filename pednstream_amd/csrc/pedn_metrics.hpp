@@ -282,8 +282,8 @@ int pedn_metrics_begin(pedn_sim* s, const int32_t* link_flags, const int32_t* or
 
 // highest row of a history field that holds what pedn_read would return for it (rows above read as zero); the ring check of pedn_read
 static int metrics_hi(const pedn_sim* s) {
-  int hi = std::min(s->valid_hi, s->v.T1 - 1);
-  if (s->v.hist) hi = std::min(hi, std::max(s->last_t, 0));   // a ring row above the newest step holds an older time index
+  int hi = std::min(s->marks.valid_hi, s->v.T1 - 1);
+  if (s->v.hist) hi = std::min(hi, std::max(s->marks.last_t, 0));   // a ring row above the newest step holds an older time index
   return hi;
 }
 
@@ -298,7 +298,7 @@ int pedn_metrics_accumulate(pedn_sim* s, int32_t t0, int32_t t1) {
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);   // (also ends a clocked section, so that last_t is the host's again)
   const int hi = metrics_hi(s);
-  const int newest = std::max(s->last_t, 0);
+  const int newest = std::max(s->marks.last_t, 0);
   for (int g : {G_TT, G_N, G_K}) {
     const int rows = s->rows32[g];
     if (rows < v.T1 && t0 < std::min(t1, hi + 1) && t0 <= newest - rows)
