@@ -122,7 +122,7 @@ struct Tables {
   std::vector<int32_t> pair_row;     // [n_pair] DevView.pair_row
   int n_multi = 0, n_trow = 0, n_over = 0;   // n_over: rows of ent_p, for probabilities beyond a workgroup's LDS rows
   int n_tf_heavy_quads = 0;
-  bool inline_tf_ok = false;         // every device-computed row is short enough for the single-launch plan (pedn_sim.inline_tf_ok)
+  bool inline_tf_ok = false;         // every device-computed row is short enough for the single-launch plan (pedn_plan::PlanInputs.inline_tf_ok)
   std::vector<char> demand_nz;       // [max(n_demand, 1)] the row holds something else than +0.0
   std::vector<int32_t> pack_order;   // nodes in the order the bins were packed in
   int packed_by = 1;                 // 0 by degree, 1 by the static load estimate, 2 by measured cost

@@ -1,5 +1,5 @@
 // pedn_hip.hip -- the core of the host side of the MI355X (gfx950) engine for PedNStream's network_loading hot path: uploads of the compiled model
-// (pedn_compile.hpp) and plan choice (pedn_create), the setters and reads, the step path (launch_step, pedn_step, pedn_run, rl_step and the clocked step) and
+// (pedn_compile.hpp) and the choice of the static plan (pedn_create, through pedn_plan.hpp: choose), the setters and reads, the step path (launch_step, pedn_step, pedn_run, rl_step and the clocked step) and
 // the agent set (pedn_rl_configure) of the C-ABI of include/pedn.h.  The kernels live in pedn_kernels.hpp, the device data structures in
 // pedn_types.hpp, the bit-exact arithmetic primitives in pedn_math.hpp, the handle and the shared host helpers in pedn_host.hpp.
 // Every training-side feature (controllers, running normalisation, rollout and replay stores, stacked actors, SAC targets, PPO evaluation, evaluation
@@ -12,6 +12,8 @@
 // segment, and the data-dependent look-backs gather between rows of the same column.
 //
 // Compile with -ffp-contract=off: results must match the reference bit for bit.
+#include <memory>
+
 #include "pedn_kernels.hpp"
 #include "pedn_host.hpp"
 #include "pedn_partition.hpp"
@@ -57,9 +59,7 @@ static int probe_overlap(pedn_sim* s, float* ms, int n = 2) {
 // falls back to one chain).  (Four chains were built and measured no faster: profiles/r04_four_chains.txt.)
 static int warm_chain_streams(pedn_sim* s, int* got) {
   *got = 1;
-  bool probe = true;
-  if (const char* f = getenv("PEDN_STREAM_PROBE")) probe = atoi(f) != 0;
-  if (!probe) { *got = 2; return PEDN_OK; }
+  if (!s->plan.stream_probe) { *got = 2; return PEDN_OK; }
   std::vector<hipStream_t> rejected;
   int rc = PEDN_OK, attempts = 0;
   for (int attempt = 0; attempt < 10 && rc == PEDN_OK; ++attempt) {
@@ -84,9 +84,8 @@ static int warm_chain_streams(pedn_sim* s, int* got) {
 // probed against the engine's; left null when no candidate does: the plan then stays off (the live launch behind a chain's launches
 // would only lengthen that chain).
 static int warm_third_stream(pedn_sim* s) {
-  if (s->stream3 || !s->dead_links || s->chains < 2) return PEDN_OK;
-  bool probe = true;
-  if (const char* f = getenv("PEDN_STREAM_PROBE")) probe = atoi(f) != 0;
+  if (s->stream3 || !s->plan.dead_links || s->chains < 2) return PEDN_OK;
+  const bool probe = s->plan.stream_probe;
   std::vector<hipStream_t> rejected;
   int rc = PEDN_OK;
   bool ok = false;
@@ -340,11 +339,33 @@ int pedn_abi_version(void) { return PEDN_ABI_VERSION; }
 
 const char* pedn_last_error(const pedn_sim* sim) { return sim ? sim->err.c_str() : g_last_error.c_str(); }
 
+// the half-built handle of pedn_create: every early return destroys it (streams, events, every device allocation made so far); the
+// message of the failure stays the thread's last error
+namespace {
+struct UnbuiltSim {
+  void operator()(pedn_sim* s) const {
+    const std::string keep = g_last_error;
+    pedn_destroy(s);
+    g_last_error = keep;
+  }
+};
+}  // namespace
+
+// was a request for `bytes` of dynamic LDS granted for the single-launch node kernel the handle selects, with / without per-replica
+// link parameters?  (which of node_kernel<LU, TF> and node_kernel_h that is: s->plan.inline_help)
+static bool node_tf_lds_granted(pedn_sim* s, int pr, size_t bytes) {
+  const int keep = s->v.pr;
+  s->v.pr = pr;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(node_kernel_for(s, true, true)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  s->v.pr = keep;
+  return e == hipSuccess;
+}
+
 int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_offset, uint64_t seed, int32_t rng_mode,
                 int32_t device, pedn_sim** out) {
   if (!m || !out) return fail(nullptr, PEDN_E_ARG, "null argument");
   *out = nullptr;
-  // ---- the model compiler (pedn_compile.hpp): every refusal of the description itself, and the static tables; no device, no handle yet
+  // ---- 1. the model compiler (pedn_compile.hpp): every refusal of the description itself, and the static tables; no device, no handle yet
   pedn_compile::Tables tab;
   {
     std::string err;
@@ -356,7 +377,8 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
   const int n_slots = m->node_slot_ptr[N];
 
   HIP_TRY(nullptr, hipSetDevice(device));
-  pedn_sim* s = new pedn_sim();
+  std::unique_ptr<pedn_sim, UnbuiltSim> guard(new pedn_sim());
+  pedn_sim* const s = guard.get();
   s->device = device;
   DevView& v = s->v;
   v.L = L;
@@ -379,11 +401,30 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
   v.meanfield = rng_mode == PEDN_RNG_MEANFIELD;
   v.n_grp = m->n_grp;
   if (const char* d = getenv("PEDN_TF_GENERAL")) v.tf_general = atoi(d);  // diagnostics: 1 general softmax path, 2 general row-sum path
+  v.n_pair = m->n_pair;
+  v.n_multi = tab.n_multi;
+  v.n_trow = tab.n_trow;
+  v.n_turns = m->n_turns;
+  v.n_pairs_corr = (int)tab.corr.size();
+  v.pairs_adj = tab.pairs_adj;
+  if (const char* f = getenv("PEDN_PAIRS_ADJ")) if (atoi(f) == 0) v.pairs_adj = 0;   // diagnostic: always through the record
   s->n_nodes = N; s->n_turns = m->n_turns; s->n_demand = m->n_demand; s->n_od = m->n_od; s->n_ent = m->n_ent;
+  s->n_pair = m->n_pair;
+  s->n_up = m->n_up;
+  s->n_over = tab.n_over;
+  s->n_tf_heavy_quads = tab.n_tf_heavy_quads;
+  s->packed_by = tab.packed_by;
+  s->n_blocks = tab.full.n_blocks;
+  s->max_degree = tab.max_degree;
   s->node_turn_ptr.assign(m->node_turn_ptr, m->node_turn_ptr + N + 1);
   s->h_node_slot_ptr.assign(m->node_slot_ptr, m->node_slot_ptr + N + 1);
   s->h_tf_set_epoch.assign(N, 0);
   s->node_demand_row.assign(m->node_demand_row, m->node_demand_row + N);
+  s->h_up_od_ptr.assign(m->up_od_ptr, m->up_od_ptr + m->n_up + 1);
+  s->h_upod_od.assign(m->upod_od, m->upod_od + m->n_upod);
+  s->h_pair_upod.assign(m->pair_upod, m->pair_upod + m->n_pair);
+  s->h_od_w.assign(m->od_w, m->od_w + (size_t)m->n_od * v.T1);
+  s->h_turn_pair_ptr.assign(m->turn_pair_ptr, m->turn_pair_ptr + m->n_turns + 1);
   {  // dead links (pedn_partition.hpp): the host's copy of what the proof reads
     s->h_node_kind.assign(m->node_kind, m->node_kind + N);
     s->h_slot_in.assign(m->slot_in_link, m->slot_in_link + n_slots);
@@ -392,26 +433,47 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     s->h_link_sep.assign(m->link_sep, m->link_sep + L);
     s->h_link_tau_sw.assign(m->link_tau_sw, m->link_tau_sw + L);
     s->h_demand_nz = std::move(tab.demand_nz);
-    if (const char* f = getenv("PEDN_DEAD_LINKS")) s->dead_links = atoi(f) != 0;
-    // PEDN_DEAD_WAVES=3..8: waves per SIMD the lean kernel may hold (see pedn_sim.dead_waves); PEDN_DEAD_STREAMS=1|2: its launches per step
-    if (const char* f = getenv("PEDN_DEAD_WAVES")) s->dead_waves = std::max(3, std::min(atoi(f), 8));
-    if (const char* f = getenv("PEDN_DEAD_STREAMS")) s->dead_streams = atoi(f) == 1 ? 1 : 2;
   }
 
-#define TRY(expr) do { int _rc = (expr); if (_rc != PEDN_OK) { std::string keep = g_last_error; pedn_destroy(s); g_last_error = keep; return _rc; } } while (0)
+  // ---- 2. the plan (pedn_plan.hpp: choose -- the rules, the PEDN_* knobs and the numbers behind each default are there).  Its two device
+  // facts are asked for only where they can matter; a request that is refused turns the fact off and the plan is chosen again.
+  {
+    pedn_plan::PlanInputs in;
+    in.RS = v.RS; in.N = N; in.L = L; in.n_trow = v.n_trow;
+    in.node_lp = m->node_model == PEDN_NODE_OPTIMAL; in.hist = v.hist != 0;
+    in.inline_tf_ok = tab.inline_tf_ok; in.n_blocks = tab.full.n_blocks; in.tiles = tab.full.tiles; in.n_rec = (int)tab.full.rec.size();
+    in.tf_wave_lds = PEDN_TF_INL_LDS;
+    const pedn_plan::Knobs knobs = pedn_plan::knobs_from_env();
+    const size_t lds_tf = pedn_plan::node_lds_tf_bytes(in);
+    if (pedn_plan::inline_candidate(in) && lds_tf > pedn_plan::LDS_DEFAULT) {   // (s->plan.inline_help is still off: node_kernel<LU, TF>)
+      in.lds_tf = node_tf_lds_granted(s, 0, lds_tf) && node_tf_lds_granted(s, 1, lds_tf);
+      (void)hipGetLastError();
+    }
+    s->plan = pedn_plan::choose(in, knobs);
+    if (s->plan.inline_help && lds_tf > pedn_plan::LDS_DEFAULT) {   // node_kernel_h
+      in.lds_h = node_tf_lds_granted(s, 0, lds_tf) && node_tf_lds_granted(s, 1, lds_tf);
+      (void)hipGetLastError();
+      if (!in.lds_h) s->plan = pedn_plan::choose(in, knobs);
+    }
+    s->chains = s->plan.chains;
+    v.tf_lds_off = s->plan.tf_lds_off;
+  }
+  const pedn_plan::EnginePlan& plan = s->plan;
+
+  // ---- 3. streams and events
   {
     hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete s; return fail(nullptr, PEDN_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(nullptr, PEDN_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e));
     // a null stream2 would be the legacy default stream (it synchronises with everything): every handle is checked
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
+    e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join3, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreate(&s->ev0);
     if (e == hipSuccess) e = hipEventCreate(&s->ev1);
-    if (e != hipSuccess) { pedn_destroy(s); return fail(nullptr, PEDN_E_DEVICE, std::string("second stream / events: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(nullptr, PEDN_E_DEVICE, std::string("second stream / events: ") + hipGetErrorString(e));
   }
-  // ---- memory budget
+  // ---- 4. memory budget
   {
     size_t RS = v.RS, T1 = v.T1;
     size_t need = (size_t)(m->n_demand) * T1 * RS * 8 + (size_t)(3 * m->n_turns + 3 * L) * RS * 8;
@@ -419,195 +481,84 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     for (int g = 0; g < 6; ++g) need += (size_t)s->rows32[g] * L * RS * 4;
     size_t free_b = 0, total_b = 0;
     const hipError_t mi = hipMemGetInfo(&free_b, &total_b);
-    if (mi != hipSuccess) {
-      std::string msg = std::string("hipMemGetInfo: ") + hipGetErrorString(mi);
-      pedn_destroy(s);
-      return fail(nullptr, PEDN_E_DEVICE, msg);
-    }
-    if (need + (256u << 20) > free_b) {
-      std::string msg = "not enough HBM: need " + std::to_string(need >> 20) + " MiB, free " + std::to_string(free_b >> 20) + " MiB";
-      pedn_destroy(s);
-      return fail(nullptr, PEDN_E_NOMEM, msg);
-    }
+    if (mi != hipSuccess) return fail(nullptr, PEDN_E_DEVICE, std::string("hipMemGetInfo: ") + hipGetErrorString(mi));
+    if (need + (256u << 20) > free_b)
+      return fail(nullptr, PEDN_E_NOMEM, "not enough HBM: need " + std::to_string(need >> 20) + " MiB, free " + std::to_string(free_b >> 20) + " MiB");
   }
-  // ---- static tables
-  TRY(upload(s, tab.lp.data(), tab.lp.size(), &v.lp));
-  TRY(upload(s, m->node_kind, N, &v.node_kind));
-  TRY(upload(s, m->node_slot_ptr, N + 1, &v.node_slot_ptr));
-  TRY(upload(s, m->node_turn_ptr, N + 1, &v.node_turn_ptr));
-  TRY(upload(s, m->node_demand_row, N, &v.node_demand_row));
-  TRY(upload(s, m->node_dyn, N, &v.node_dyn));
-  TRY(upload(s, m->slot_in_link, n_slots, &v.slot_in));
-  TRY(upload(s, m->slot_out_link, n_slots, &v.slot_out));
-  s->h_up_od_ptr.assign(m->up_od_ptr, m->up_od_ptr + m->n_up + 1);
-  s->h_upod_od.assign(m->upod_od, m->upod_od + m->n_upod);
-  s->h_pair_upod.assign(m->pair_upod, m->pair_upod + m->n_pair);
-  s->h_od_w.assign(m->od_w, m->od_w + (size_t)m->n_od * v.T1);
-  s->n_pair = m->n_pair;
-  s->n_up = m->n_up;
-  v.n_pair = m->n_pair;
-  s->h_turn_pair_ptr.assign(m->turn_pair_ptr, m->turn_pair_ptr + m->n_turns + 1);
-  v.n_multi = tab.n_multi;
-  v.n_trow = tab.n_trow;
-  v.n_turns = m->n_turns;
-  s->n_over = tab.n_over;
-  s->n_tf_heavy_quads = tab.n_tf_heavy_quads;
-  s->inline_tf_ok = tab.inline_tf_ok;
-  TRY(upload(s, tab.trow_words.data(), tab.trow_words.size(), &v.trow_words));
-  TRY(upload(s, tab.tgrp_words.data(), tab.tgrp_words.size(), &v.tgrp_words));
-  TRY(upload(s, tab.pair_row.data(), tab.pair_row.size(), &v.pair_row));
+  // ---- 5. uploads and allocations: the static tables, what the plan names, the dynamic state; then reset and warm
+  int rc;
+  if ((rc = upload(s, tab.lp.data(), tab.lp.size(), &v.lp)) || (rc = upload(s, m->node_kind, N, &v.node_kind)) ||
+      (rc = upload(s, m->node_slot_ptr, N + 1, &v.node_slot_ptr)) || (rc = upload(s, m->node_turn_ptr, N + 1, &v.node_turn_ptr)) ||
+      (rc = upload(s, m->node_demand_row, N, &v.node_demand_row)) || (rc = upload(s, m->node_dyn, N, &v.node_dyn)) ||
+      (rc = upload(s, m->slot_in_link, n_slots, &v.slot_in)) || (rc = upload(s, m->slot_out_link, n_slots, &v.slot_out)) ||
+      (rc = upload(s, tab.trow_words.data(), tab.trow_words.size(), &v.trow_words)) ||
+      (rc = upload(s, tab.tgrp_words.data(), tab.tgrp_words.size(), &v.tgrp_words)) ||
+      (rc = upload(s, tab.pair_row.data(), tab.pair_row.size(), &v.pair_row)) || (rc = upload(s, m->od_w, (size_t)m->n_od * v.T1, &v.od_w)) ||
+      (rc = upload(s, tab.corr.data(), tab.corr.size(), &v.corr_rec)))
+    return rc;
   s->h_pair_const = std::move(tab.pair_const);
   s->h_turn_mode = std::move(tab.turn_mode);
   s->h_slot_dyn = std::move(tab.slot_dyn);
   s->h_slot_trow = std::move(tab.slot_trow);
-  TRY(upload(s, m->od_w, (size_t)m->n_od * v.T1, &v.od_w));
-  v.n_pairs_corr = (int)tab.corr.size();
-  v.pairs_adj = tab.pairs_adj;
-  if (const char* f = getenv("PEDN_PAIRS_ADJ")) if (atoi(f) == 0) v.pairs_adj = 0;   // diagnostic: always through the record
-  TRY(upload(s, tab.corr.data(), tab.corr.size(), &v.corr_rec));
-  {  // the plan, from the compiled tables
-    s->h_slot_rec = std::move(tab.full.rec);
+  s->h_pack_order = std::move(tab.pack_order);
+  s->h_slot_rec = std::move(tab.full.rec);
+  {  // what the plan names
     const std::vector<SlotRec>& rec = s->h_slot_rec;
-    s->packed_by = tab.packed_by;
-    s->h_pack_order = std::move(tab.pack_order);
-    s->n_blocks = tab.full.n_blocks;
-    s->max_degree = tab.max_degree;
-    // LDS of node_kernel: 8 (LP: 16) rows of 64 doubles + the m*m tiles of the fullest block
-    s->node_lds = (size_t)((m->node_model == PEDN_NODE_OPTIMAL ? 16 : 8) + tab.full.tiles) * 64 * sizeof(double);
-    // (register budget of the node kernels: node_kernel_waves() in pedn_kernels.hpp)
-    // The link update of t and the turning fractions of t+1 share one launch (both only read what node_kernel(t) and earlier
-    // launches wrote); PEDN_FUSE_TP=0 gives the fractions a launch of their own in front of node_kernel(t+1).
-    s->fuse_tp = 1;
-    if (const char* f = getenv("PEDN_FUSE_TP")) s->fuse_tp = atoi(f) != 0;
-    if (const char* f = getenv("PEDN_FUSE_OBS")) s->fuse_obs = atoi(f) != 0;
-    // two chains of launches (one per half of the replicas) in pedn_run; PEDN_STREAMS=1|2, pedn_set_streams.  Default from 640
-    // replicas: one chain's launch leaves wave places empty while it fills and drains, and the other half's launches use them
-    // (delft x 1024: 51.7 -> 45.3 us per step in round 2; round 5, melbourne / delft: x 640 25.8 -> 23.6 / 36.2 -> 34.3, x 768 27.1 -> 24.8,
-    // x 896 31.3 -> 27.5 / 45.3 -> 40.7; x 512 19.2 either way).  The halves are whole 128-replica segments (view_of): 640 = 384 + 256.
-    s->chains = v.RS >= 640 ? 2 : 1;
-    if (const char* f = getenv("PEDN_STREAMS")) s->chains = atoi(f) == 2 ? 2 : 1;
-    s->two_streams = s->chains > 1;
-    // Owner-wave plan of pedn_run (launch_step: lazy): node_kernel<LU>(t + 1) performs the link update of t, one launch per step.  The
-    // default for models whose second launch is the link update alone (no turning fractions computed on the device): melbourne x 1024
-    // 37.4 -> 32.7-33.7 us per step on one chain, 34.6 -> 30.3 on two (profiles/r04_owner_wave.txt).  With dynamic rows the second launch
-    // stays (node_kernel(t + 1) needs the fractions that need node_kernel(t)'s flows) and the longer node_kernel costs more than the
-    // link-update workgroups that leave it save (delft x 1024: 42.1-42.6 -> 44.2).  PEDN_LINK_OWNER=0|1 overrides.
-    s->link_owner = v.n_trow == 0 && m->node_model != PEDN_NODE_OPTIMAL;
-    if (const char* f = getenv("PEDN_LINK_OWNER")) s->link_owner = atoi(f) != 0;
-    // Single-launch plan with dynamic turning fractions: the rows computed inside node_kernel<LU, TF> by the slot waves themselves.  That
-    // instantiation is built for 2 waves per SIMD (1 block per CU): only where the whole grid is one generation of them -- small
-    // batches, which are chains of latencies and gain a whole launch (nine_intersections x 256: 17.2 -> ... us per step).
-    s->node_lds_tf = s->node_lds + (size_t)8 * PEDN_TF_INL_LDS * sizeof(double);
-    v.tf_lds_off = (int32_t)(s->node_lds / sizeof(double));
-    bool inl_possible = s->inline_tf_ok && m->node_model != PEDN_NODE_OPTIMAL && s->node_lds_tf <= 160 * 1024;
-    if (inl_possible && s->node_lds_tf > 64 * 1024) {   // more dynamic LDS than a kernel gets by default: ask for it (gfx950: 160 KB per CU)
-      for (int pr = 0; pr < 2 && inl_possible; ++pr) {
-        DevView& vv = s->v;
-        const int keep = vv.pr;
-        vv.pr = pr;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(node_kernel_for(s, true, true)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->node_lds_tf) != hipSuccess)
-          inl_possible = false;
-        vv.pr = keep;
-      }
-      (void)hipGetLastError();
-    }
-    // ... by HELPER waves (node_kernel_h: sixteen waves per workgroup at 128 VGPRs, still one workgroup per CU): the row (~5 us) and the
-    // slot wave's own chain (~5 us) side by side -- nine_intersections x 256 16.2 -> 12.5 us per step, 45_intersections x 1024 (272
-    // workgroups) 17.9 -> 13.6, x 1280 (340) 20.4 -> 14.7 under pedn_run's two chains and 20.5 -> 19.1 step by step; x 1536 (408) still
-    // wins under pedn_run (21.3 -> 17.5) but not step by step (22.3 -> 23.1), at 544 (x 2048) two launches per step are faster either
-    // way (22.9 against 23.7).  The default up to 352 workgroups; PEDN_INLINE_TF=0 two launches, 1 the slot waves' own rows, 2 helper
-    // waves (forced whatever the grid).  profiles/r04_inline_helpers.txt
-    s->inline_tf = inl_possible && (size_t)(v.RS / 64) * (size_t)s->n_blocks <= 352;
-    s->inline_help = s->inline_tf;
-    if (const char* f = getenv("PEDN_INLINE_TF")) { s->inline_tf = atoi(f) != 0 && inl_possible; s->inline_help = atoi(f) == 2 && inl_possible; }
-    if (s->inline_help && s->node_lds_tf > 64 * 1024) {
-      for (int pr = 0; pr < 2; ++pr) {
-        DevView& vv = s->v;
-        const int keep = vv.pr;
-        vv.pr = pr;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(node_kernel_for(s, true, true)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->node_lds_tf) != hipSuccess)
-          s->inline_help = 0;
-        vv.pr = keep;
-      }
-      (void)hipGetLastError();
-    }
-    if (s->inline_tf) s->link_owner = 1;
-    // quiet corridors: the owner-wave launches skip the loads of corridors that are empty in all 64 replicas of a group (node_step)
-    s->quiet = s->link_owner && m->node_model != PEDN_NODE_OPTIMAL;
-    if (const char* f = getenv("PEDN_QUIET")) s->quiet = atoi(f) != 0;
-    if (const char* f = getenv("PEDN_QUIET_LEAN")) s->quiet_lean = atoi(f) != 0;
-    // zero elision: the node kernels skip +0.0 stores into rows that hold +0.0 since the last full reset (zero_gate)
-    if (const char* f = getenv("PEDN_ZERO_ELIDE")) s->zero_elide = atoi(f) != 0;
-    // 0 = by batch: two chains where the step is not a pure chain of latencies any more -- from 4096 envs, and from 1024 with per-env
-    // scenarios (45_intersections: 2048 envs plain 24.8-25.2 -> 24.7-25.7 us per env step, randomised 27.5-27.9 -> 25.6-26.0;
-    // 4096 envs 40.6 -> 35.9; profiles/r04_rl_chains.txt); PEDN_RL_CHAINS=1|2 forces
-    s->rl_chains = 0;
-    if (const char* f = getenv("PEDN_RL_CHAINS")) s->rl_chains = atoi(f) == 2 ? 2 : 1;
-    s->node_lp = m->node_model == PEDN_NODE_OPTIMAL;
-    if (s->node_lp) {  // tableau workspace: one per (regular node, replica group), sized for the largest such node
+    if (plan.node_lp) {  // tableau workspace: one per (regular node, replica group), sized for the largest such node
       const int n_lp = tab.full.n_lp, max_m = tab.full.lp_max_m;
       const int E = max_m * (max_m - 1), rows = 2 * max_m + E, cols = 3 * E + 2 * max_m;
       v.lp_stride = (size_t)(rows + 1) * (cols + 1) * 64;
       v.lp_bstride = (size_t)rows * 64;
       const size_t waves = (size_t)std::max(n_lp, 1) * (v.RS / 64);
-      TRY(dalloc(s, waves * v.lp_stride, &v.lp_ws));
-      TRY(dalloc(s, waves * v.lp_bstride, &v.lp_basis));
+      if ((rc = dalloc(s, waves * v.lp_stride, &v.lp_ws)) || (rc = dalloc(s, waves * v.lp_bstride, &v.lp_basis))) return rc;
     }
-    TRY(upload(s, rec.data(), rec.size(), &v.slot_rec));
+    if ((rc = upload(s, rec.data(), rec.size(), &v.slot_rec))) return rc;
     s->d_slot_rec = const_cast<SlotRec*>(v.slot_rec);
     v.quiet_npos = (int32_t)rec.size();
-    if (s->quiet) {   // [2][slot positions][RS / 64][own | inbox]: melbourne x 1024 ~ 0.3 MB
-      const size_t nq = (size_t)2 * rec.size() * (size_t)(v.RS / 64) * 2;
-      // (node_step indexes the words of one step, nq / 2, in 32 bits)
-      if (nq / 2 >= ((size_t)1 << 31)) TRY(fail(s, PEDN_E_ARG, "too many quiet words"));
-      TRY(dalloc(s, nq, &s->d_quiet));
-      HIP_TRY(s, hipMemset(s->d_quiet, 0, nq * sizeof(uint32_t)));
+    if (plan.quiet) {
+      // (node_step indexes the words of one step, half of them, in 32 bits)
+      if (plan.quiet_words / 2 >= ((size_t)1 << 31)) return fail(s, PEDN_E_ARG, "too many quiet words");
+      if ((rc = dalloc(s, plan.quiet_words, &s->d_quiet))) return rc;
+      HIP_TRY(s, hipMemset(s->d_quiet, 0, plan.quiet_words * sizeof(uint32_t)));
     }
-    if (s->dead_links && s->quiet && s->link_owner && !s->inline_tf && !v.hist && m->node_model != PEDN_NODE_OPTIMAL && v.n_trow == 0 && L > 0) {
-      // dead links: room for a packing of the live nodes alone (at most one bin per node, one idle block behind them), its quiet words,
-      // and the records of every slot dead_link_kernel may step (dl_refresh fills them)
-      const size_t cap = ((size_t)N + 1) * 8, nq = (size_t)2 * cap * (size_t)(v.RS / 64) * 2;
-      if (nq / 2 < ((size_t)1 << 31)) {
-        TRY(dalloc(s, cap, &s->d_live_rec));
-        TRY(dalloc(s, rec.size(), &s->d_dead_rec));
-        TRY(dalloc(s, rec.size(), &s->d_dead_drec));
-        TRY(dalloc(s, nq, &s->d_quiet_live));
-        HIP_TRY(s, hipMemset(s->d_quiet_live, 0, nq * sizeof(uint32_t)));
-      }
+    if (plan.dead_capable) {   // the live packing at its capacity, its quiet words, the records of every slot dead_link_kernel may step (dl_refresh fills them)
+      if ((rc = dalloc(s, pedn_plan::live_rec_capacity(N), &s->d_live_rec)) || (rc = dalloc(s, rec.size(), &s->d_dead_rec)) ||
+          (rc = dalloc(s, rec.size(), &s->d_dead_drec)) || (rc = dalloc(s, plan.quiet_words_live, &s->d_quiet_live)))
+        return rc;
+      HIP_TRY(s, hipMemset(s->d_quiet_live, 0, plan.quiet_words_live * sizeof(uint32_t)));
     }
   }
-  // ---- dynamic state
-  {
+  {  // dynamic state
     size_t RS = v.RS, T1 = v.T1;
-    for (int f = 0; f < 7; ++f) TRY(dalloc(s, (size_t)s->rows64[f] * (f < 4 ? v.Lall : L) * RS, &v.f64[f]));
-    for (int g = 0; g < 6; ++g) TRY(dalloc(s, (size_t)s->rows32[g] * L * RS, &v.f32[g]));
-    TRY(dalloc(s, (size_t)L * RS, &v.rsum));
-    TRY(dalloc(s, (size_t)L * RS, &v.front));
-    TRY(dalloc(s, (size_t)L * RS, &v.back));
-    TRY(dalloc(s, (size_t)L * RS, &v.sepw));
-    TRY(dalloc(s, (size_t)L * RS, &v.sepnp));
+    for (int f = 0; f < 7; ++f)
+      if ((rc = dalloc(s, (size_t)s->rows64[f] * (f < 4 ? v.Lall : L) * RS, &v.f64[f]))) return rc;
+    for (int g = 0; g < 6; ++g)
+      if ((rc = dalloc(s, (size_t)s->rows32[g] * L * RS, &v.f32[g]))) return rc;
+    if ((rc = dalloc(s, (size_t)L * RS, &v.rsum)) || (rc = dalloc(s, (size_t)L * RS, &v.front)) || (rc = dalloc(s, (size_t)L * RS, &v.back)) ||
+        (rc = dalloc(s, (size_t)L * RS, &v.sepw)) || (rc = dalloc(s, (size_t)L * RS, &v.sepnp)))
+      return rc;
     HIP_TRY(s, hipMemset(v.sepnp, 0, std::max<size_t>((size_t)L * RS, 1) * sizeof(double)));
-    TRY(dalloc(s, (size_t)m->n_turns * RS, &v.tf));
-    TRY(dalloc(s, (size_t)m->n_demand * T1 * RS, &v.demand));
-    TRY(dalloc(s, (size_t)std::max(s->n_over, 1) * RS, &v.ent_p));  // probabilities that do not fit a node's LDS rows
-    for (int k = 0; k < 2; ++k) TRY(dalloc(s, (size_t)std::max(m->n_turns, 1) * RS, &v.tfd[k]));
-    TRY(dalloc(s, (size_t)m->n_pair * T1, &s->d_pair_pod));
+    if ((rc = dalloc(s, (size_t)m->n_turns * RS, &v.tf)) || (rc = dalloc(s, (size_t)m->n_demand * T1 * RS, &v.demand)) ||
+        (rc = dalloc(s, (size_t)std::max(s->n_over, 1) * RS, &v.ent_p)))  // probabilities that do not fit a node's LDS rows
+      return rc;
+    for (int k = 0; k < 2; ++k)
+      if ((rc = dalloc(s, (size_t)std::max(m->n_turns, 1) * RS, &v.tfd[k]))) return rc;
+    if ((rc = dalloc(s, (size_t)m->n_pair * T1, &s->d_pair_pod))) return rc;
     v.pair_pod = s->d_pair_pod;
-    TRY(dalloc(s, (size_t)std::max(m->n_turns, 1) * T1, &s->d_turn_tab));
+    if ((rc = dalloc(s, (size_t)std::max(m->n_turns, 1) * T1, &s->d_turn_tab))) return rc;
     v.turn_tab = s->d_turn_tab;
     HIP_TRY(s, hipMemset(s->d_turn_tab, 0, (size_t)std::max(m->n_turns, 1) * T1 * sizeof(double)));
-    TRY(dalloc(s, RS, &v.flags));
-    TRY(dalloc(s, 4, &s->d_clock));
+    if ((rc = dalloc(s, RS, &v.flags)) || (rc = dalloc(s, 4, &s->d_clock))) return rc;
     HIP_TRY(s, hipMemset(s->d_clock, 0, 4 * sizeof(int32_t)));
     v.clock = s->d_clock;
   }
-  // initial widths, turning fractions, demand (broadcast to every replica)
-  {
+  {  // initial widths, turning fractions, demand (broadcast to every replica)
     const double* w0[3] = {m->front_gate0, m->back_gate0, m->sep_width0};
     double* dst[3] = {v.front, v.back, v.sepw};
-    for (int k = 0; k < 3; ++k) TRY(push_rows(s, dst[k], w0[k], L, 0, 1, PEDN_ALL));
-    TRY(push_rows(s, v.tf, m->tf_init, m->n_turns, 0, 1, PEDN_ALL));
-    TRY(push_rows(s, v.demand, m->demand, m->n_demand * v.T1, 0, 1, PEDN_ALL));
+    for (int k = 0; k < 3; ++k)
+      if ((rc = push_rows(s, dst[k], w0[k], L, 0, 1, PEDN_ALL))) return rc;
+    if ((rc = push_rows(s, v.tf, m->tf_init, m->n_turns, 0, 1, PEDN_ALL)) || (rc = push_rows(s, v.demand, m->demand, m->n_demand * v.T1, 0, 1, PEDN_ALL)))
+      return rc;
     HIP_TRY(s, hipMemsetAsync(v.ent_p, 0, (size_t)std::max(s->n_over, 1) * v.RS * 8, s->stream));
     for (int k = 0; k < 2; ++k) HIP_TRY(s, hipMemsetAsync(v.tfd[k], 0, (size_t)std::max(m->n_turns, 1) * v.RS * 8, s->stream));
     // replica-uniform shortcuts: everything starts uniform; dynamic nodes always use their per-replica rows
@@ -619,28 +570,20 @@ int pedn_create(const pedn_model_desc* m, int32_t n_replicas, int32_t replica_of
     for (int n = 0; n < N; ++n)
       if (m->node_dyn[n])
         for (int k = m->node_turn_ptr[n]; k < m->node_turn_ptr[n + 1]; ++k) s->h_tf_u[k] = qnan;
-    TRY(dalloc(s, (size_t)L, &s->d_front_u));
-    TRY(dalloc(s, (size_t)L, &s->d_back_u));
-    TRY(dalloc(s, (size_t)m->n_turns, &s->d_tf_u));
+    if ((rc = dalloc(s, (size_t)L, &s->d_front_u)) || (rc = dalloc(s, (size_t)L, &s->d_back_u)) || (rc = dalloc(s, (size_t)m->n_turns, &s->d_tf_u))) return rc;
     v.front_u = s->d_front_u; v.back_u = s->d_back_u; v.tf_u = s->d_tf_u;
-    TRY(push_uniform(s));
-    TRY(tabulate_pair_pod(s));
+    if ((rc = push_uniform(s)) || (rc = tabulate_pair_pod(s))) return rc;
   }
-  {
-    int rc = reset_state(s);
-    if (rc != PEDN_OK) { std::string keep = g_last_error; pedn_destroy(s); g_last_error = keep; return rc; }
-  }
+  if ((rc = reset_state(s))) return rc;
   HIP_TRY(s, hipStreamSynchronize(s->stream));
-  if (s->chains > 1) {
+  if (s->chains > 1) {   // the chains the plan wants: as far as their streams are seen to overlap
     int got = 1;
-    TRY(warm_chain_streams(s, &got));
+    if ((rc = warm_chain_streams(s, &got))) return rc;
     s->chains = s->warmed_chains = got;
-    s->two_streams = s->chains > 1;
-    if (s->d_live_rec) TRY(warm_third_stream(s));
+    if (s->d_live_rec && (rc = warm_third_stream(s))) return rc;
     prewarm_chains(s);
   }
-#undef TRY
-  *out = s;
+  *out = guard.release();
   return PEDN_OK;
 }
 
@@ -1009,8 +952,8 @@ static step_kernel_fn node_kernel_for(const pedn_sim* s, bool lu, bool tf) {
   const bool d6 = s->max_degree <= 6;  // loops and the row of turning fractions unrolled for 6 instead of 8 corridors per node
 #define PEDN_NK(PR_, LP_, LU_, TF_) (h ? (d6 ? node_kernel<PR_, LP_, true, 6, LU_, TF_> : node_kernel<PR_, LP_, true, 8, LU_, TF_>) \
                                        : (d6 ? node_kernel<PR_, LP_, false, 6, LU_, TF_> : node_kernel<PR_, LP_, false, 8, LU_, TF_>))
-  if (s->node_lp) return s->v.pr ? PEDN_NK(true, true, false, false) : PEDN_NK(false, true, false, false);
-  if (lu && tf && s->inline_help) {   // helper waves compute the rows: sixteen waves per workgroup
+  if (s->plan.node_lp) return s->v.pr ? PEDN_NK(true, true, false, false) : PEDN_NK(false, true, false, false);
+  if (lu && tf && s->plan.inline_help) {   // helper waves compute the rows: sixteen waves per workgroup
     if (s->v.pr) return h ? (d6 ? node_kernel_h<true, true, 6> : node_kernel_h<true, true, 8>) : (d6 ? node_kernel_h<true, false, 6> : node_kernel_h<true, false, 8>);
     return h ? (d6 ? node_kernel_h<false, true, 6> : node_kernel_h<false, true, 8>) : (d6 ? node_kernel_h<false, false, 6> : node_kernel_h<false, false, 8>);
   }
@@ -1149,20 +1092,20 @@ static void prewarm_chains(pedn_sim* s) {
   sel.pr = 0;   // (what is warmed are the instantiations without per-replica parameters, whatever the engine holds)
   for (int c = 0; c < s->chains; ++c) {
     hipStream_t st = chain_stream(s, c);
-    for (int lu = 0; lu < 2; ++lu) hipLaunchKernelGGL(node_kernel_for(s, lu != 0, false), dim3(1, 1), dim3(512), s->node_lds, st, v, 2);
-    if (s->inline_tf) hipLaunchKernelGGL(node_kernel_for(s, true, true), dim3(1, 1), dim3(s->inline_help ? 1024 : 512), s->node_lds_tf, st, v, 2);
+    for (int lu = 0; lu < 2; ++lu) hipLaunchKernelGGL(node_kernel_for(s, lu != 0, false), dim3(1, 1), dim3(512), s->plan.node_lds, st, v, 2);
+    if (s->plan.inline_tf) hipLaunchKernelGGL(node_kernel_for(s, true, true), dim3(1, 1), dim3(s->plan.inline_help ? 1024 : 512), s->plan.node_lds_tf, st, v, 2);
     hipLaunchKernelGGL(link_turn_kernel_for(sel, false, false), dim3(1), dim3(256), 0, st, vl, 1, 0u, 0u, 0u, q, 0);
     hipLaunchKernelGGL(link_kernel_1r_for(sel), dim3(1), dim3(256), 0, st, vl, 1);
     if (s->stream3) hipLaunchKernelGGL(dead_link_kernel, dim3(1), dim3(256), 0, st, v, 2, (const DeadRec*)s->d_dead_drec, 0);   // (no slot: its waves leave)
   }
   if (s->stream3) {   // the live bins' stream of the dead-link plan
-    hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3(1, 1), dim3(512), s->node_lds, s->stream3, v, 2);
+    hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3(1, 1), dim3(512), s->plan.node_lds, s->stream3, v, 2);
     hipStreamSynchronize(s->stream3);
   }
   for (int c = s->chains - 1; c >= 0; --c) hipStreamSynchronize(chain_stream(s, c));
 }
 
-// ---- Dead links (pedn_partition.hpp, dead_link_kernel; pedn_sim.dead_links)
+// ---- Dead links (pedn_partition.hpp, dead_link_kernel; EnginePlan.dead_links in pedn_plan.hpp)
 // The proof, from what the host knows now, and the two things built from it: the records of the dead nodes' slots (dead_link_kernel's
 // work list) and a second packing of the live nodes alone for node_kernel<LU>.  Between full resets the set only
 // shrinks (dl_grow), and the proof's sources only grow (dl_src, dl_reach).  A live slot whose corridor's other end is a dead slot mirrors ITSELF: its own quiet word fills its inbox -- the
@@ -1189,7 +1132,7 @@ static int dl_refresh(pedn_sim* s) {
   pm.n_nodes = N; pm.n_links = L;
   pm.node_slot_ptr = s->h_node_slot_ptr.data(); pm.node_turn_ptr = s->node_turn_ptr.data(); pm.node_kind = s->h_node_kind.data();
   pm.node_demand_row = s->node_demand_row.data(); pm.slot_in = s->h_slot_in.data(); pm.slot_out = s->h_slot_out.data();
-  pm.link_rev = s->h_link_rev.data(); pm.slot_dyn = s->h_slot_dyn.data(); pm.node_lp = s->node_lp;
+  pm.link_rev = s->h_link_rev.data(); pm.slot_dyn = s->h_slot_dyn.data(); pm.node_lp = s->plan.node_lp;
   // once a step has run, the sources of the earlier proofs stay sources: their pedestrians may still be on the way
   if (s->marks.dl_grow || s->dl_src.size() != s->h_demand_nz.size() || s->dl_reach.size() != (size_t)std::max(L, 1)) {
     s->dl_src = s->h_demand_nz;
@@ -1250,12 +1193,11 @@ static int dl_refresh(pedn_sim* s) {
 }
 
 // Does a two-chain range of pedn_run take the split plan now?  Everything the proof and dead_link_kernel do not cover keeps the plan
-// off: recent-history mode, the node LP, rows of fractions computed on the device, per-replica link parameters, an agent set, no
-// third stream that overlaps, a state the host does not follow (dl_off) -- and a model without a dead link.
+// off: recent-history mode, the node LP, rows of fractions computed on the device (all three: plan.dead_capable, pedn_plan.hpp),
+// per-replica link parameters, an agent set, no third stream that overlaps, a state the host does not follow (dl_off) -- and a model
+// without a dead link.
 static bool dl_split_ok(pedn_sim* s) {
-  if (!s->dead_links || !s->d_live_rec || !s->stream3 || s->marks.dl_off || s->chains < 2 || !s->link_owner || !s->quiet || s->node_lp || s->inline_tf ||
-      s->v.hist || s->v.pr || s->rl_ready || s->v.n_trow > 0 || s->v.n_pairs_corr == 0)
-    return false;
+  if (!s->plan.dead_capable || !s->stream3 || s->marks.dl_off || s->chains < 2 || s->v.pr || s->rl_ready || s->v.n_pairs_corr == 0) return false;
   if (s->dl_dirty && dl_refresh(s) != PEDN_OK) return false;
   return s->n_dead_links > 0;
 }
@@ -1290,8 +1232,8 @@ static inline pedn_plan::StepRequest step_request(int t, bool lazy, int chain = 
 //   * the error flags are OR-ed atomically by both; the live waves read them only to decide their quiet word, which selects between
 //     two paths that give the same bits.
 static void launch_split_step(pedn_sim* s, int t) {
-  const pedn_plan::SplitPlan p = pedn_plan::plan_split_step(step_caps(s), s->marks, step_request(t, true, -1, s->dead_streams));
-  const size_t lds = dead_lds_bytes(s->dead_waves);   // the lean kernel's share of the wave places
+  const pedn_plan::SplitPlan p = pedn_plan::plan_split_step(step_caps(s), s->marks, step_request(t, true, -1, s->plan.dead_streams));
+  const size_t lds = dead_lds_bytes(s->plan.dead_waves);   // the lean kernel's share of the wave places
   for (int c = 0; c < p.lean_launches; ++c) {
     hipStream_t stream;
     DevView vd = view_of(s, p.lean_launches == 1 ? -1 : c, &stream);
@@ -1346,7 +1288,7 @@ static int launch_step(pedn_sim* s, const pedn_plan::StepRequest& rq, hipEvent_t
   };
   const StepGrid g(s, v, p.link ? link_blocks(v, p.one_r) : 0u, p.fused, p.obs);
   if (p.tf_alone) launch(turn_frac_kernel_for(v), dim3(g.tf_blocks(v)), dim3(256), 0, v, t);
-  const size_t nlds = p.inl ? s->node_lds_tf : s->node_lds;
+  const size_t nlds = p.inl ? s->plan.node_lds_tf : s->plan.node_lds;
   const dim3 nblock(p.helpers ? 1024 : 512);   // helper waves: sixteen per workgroup
   if (rq.profiled) hipExtLaunchKernelGGL(node_kernel_for(s, p.lu, p.inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, ev[2], ev[3], 0, vn, t);
   else hipLaunchKernelGGL(node_kernel_for(s, p.lu, p.inl), dim3(g.rgroups, (unsigned)s->n_blocks), nblock, nlds, stream, vn, t);
@@ -1382,8 +1324,8 @@ int pedn_step(pedn_sim* s, int32_t t) {
   if (!two) join_forked(s);
   // owner-wave plan: this step's link update stays pending -- the next step's node kernel performs it, or whatever call looks at
   // or changes the state first (pending_links_first)
-  bool lazy = s->link_owner != 0;
-  if (lazy && s->inline_tf) {   // (without device-computed rows both plans are two launches per step for such a caller)
+  bool lazy = s->plan.link_owner;
+  if (lazy && s->plan.inline_tf) {   // (without device-computed rows both plans are two launches per step for such a caller)
     s->touch_streak = s->touched ? std::min(s->touch_streak + 1, 2) : std::max(s->touch_streak - 1, 0);
     if (s->touch_streak >= 2) lazy = false;
   }
@@ -1465,7 +1407,7 @@ int pedn_run(pedn_sim* s, int32_t t0, int32_t t1) {
   // several steps take this plan; everything else (single steps, RL steps, profiling) stays on the one stream.
   // Owner-wave plan (link_owner): one launch per step for models without dynamic turning fractions -- node_kernel<LU>(t) performs the
   // link update of t - 1 -- plus one link_kernel for the last step of the range.
-  const bool lazy = s->link_owner != 0;
+  const bool lazy = s->plan.link_owner;
   int rc = clock_end(s);
   if (rc != PEDN_OK) return rc;
   join_forked(s);
@@ -1479,7 +1421,7 @@ int pedn_run(pedn_sim* s, int32_t t0, int32_t t1) {
     const bool split = nch == 2 && lazy && dl_split_ok(s);
     int t = t0;
     if (split && (rc = launch_step(s, step_request(t++, lazy))) != PEDN_OK) return rc;
-    const int idle = split && s->dead_streams == 1 ? 1 : -1;
+    const int idle = split && s->plan.dead_streams == 1 ? 1 : -1;
     if ((rc = fork_chains(s, split ? 3 : nch, idle)) != PEDN_OK) return rc;
     for (; t < t1; ++t) {
       if (split) launch_split_step(s, t);
@@ -1497,16 +1439,17 @@ int pedn_run(pedn_sim* s, int32_t t0, int32_t t1) {
 
 int pedn_plan_info(pedn_sim* s, int32_t* info, int32_t n) {
   if (!s || !info || n < 4) return fail(s, PEDN_E_ARG, "pedn_plan_info: null argument or fewer than 4 entries");
+  const pedn_plan::PlanReport r = pedn_plan::report(s->plan, s->v.n_pairs_corr > 0);
   info[0] = s->chains;
-  info[1] = s->link_owner && !s->node_lp && s->v.n_pairs_corr > 0;   // (with device-computed rows: the single-launch plan, inline_tf)
+  info[1] = r.owner_wave;   // (with device-computed rows: the single-launch plan, inline_tf)
   info[2] = s->stream_probe_attempts;
   info[3] = (int32_t)(s->stream_probe_ms * 1000.0f + 0.5f);
   if (n >= 5) info[4] = s->packed_by;   // bins of node_kernel packed by 0 degree, 1 the static load estimate, 2 measured node cost
-  if (n >= 6) info[5] = s->quiet && info[1];   // the owner-wave launches keep and use the quiet-corridor words (PEDN_QUIET)
-  if (n >= 7) info[6] = s->zero_elide && !s->v.hist;   // the node kernels may skip +0.0 stores into clean rows (PEDN_ZERO_ELIDE)
+  if (n >= 6) info[5] = r.quiet;   // the owner-wave launches keep and use the quiet-corridor words (PEDN_QUIET)
+  if (n >= 7) info[6] = r.zero_elide;   // the node kernels may skip +0.0 stores into clean rows (PEDN_ZERO_ELIDE)
   if (n >= 8) info[7] = s->marks.zgated;   // ... and this many node-kernel launches had a gate open since the last reset
-  if (n >= 9) info[8] = s->quiet_lean && s->quiet && info[1];   // the quiet-corridor launches take the lean path (PEDN_QUIET_LEAN)
-  if (n >= 10) info[9] = dl_split_ok(s) ? s->n_dead_links : 0;   // links that dead_link_kernel steps in a two-chain range (PEDN_DEAD_LINKS)
+  if (n >= 9) info[8] = r.quiet_lean;   // the quiet-corridor launches take the lean path (PEDN_QUIET_LEAN)
+  if (n >= 10) info[9] = r.dead_links && dl_split_ok(s) ? s->n_dead_links : 0;   // links that dead_link_kernel steps in a two-chain range (PEDN_DEAD_LINKS)
   if (n >= 11) info[10] = s->marks.split_steps;   // ... and the steps that were launched that way since the last reset
   return PEDN_OK;
 }
@@ -1525,7 +1468,6 @@ int pedn_set_streams(pedn_sim* s, int32_t n) {
   }
   const int before = s->chains;
   s->chains = n > 1 ? std::min<int>(n, std::max(s->warmed_chains, 1)) : 1;
-  s->two_streams = s->chains > 1;
   if (s->chains > 1 && s->d_live_rec && (rc = warm_third_stream(s)) != PEDN_OK) return rc;
   if (s->chains > before) prewarm_chains(s);   // (every chain's stream: hipSetDevice above)
   return PEDN_OK;
@@ -1538,7 +1480,7 @@ struct ProfRow { int t, chain, kind; float start, end; };
 static int profile_range(pedn_sim* s, int t0, int t1, std::vector<ProfRow>& rows, int* chains) {
   const int halves = chains_for(s, t0, t1), n = (t1 - t0) * halves;
   const bool two = halves > 1;
-  const bool lazy = s->link_owner != 0;   // pedn_run's plan
+  const bool lazy = s->plan.link_owner;   // pedn_run's plan
   struct Events {  // destroyed on every way out of the function
     std::vector<hipEvent_t> e;
     ~Events() { for (hipEvent_t x : e) if (x) hipEventDestroy(x); }
@@ -2150,8 +2092,8 @@ static int rl_step(pedn_sim* s, const double* actions, int32_t on_device, int32_
   // on_device == 2: the caller chains this call between its own streams and pedn_stream() with events (no host synchronisation):
   // everything must then be ordered by the engine's stream alone
   const int term = t + action_gap - 1 >= s->v.T1 - 1 ? 1 : 0;   // pz_pednet_env.py:592
-  const bool two = !s->norm.on && on_device != 2 && (s->rl_chains == 2 || (s->rl_chains == 0 && by_batch)) && s->warmed_chains >= 2 && s->v.RS >= 256 && s->fuse_obs && (!actions || (fold != nullptr && on_device)) && !obs && !rewards &&
-                   s->marks.link_pending < 0 && !(s->v.n_trow > 0 && !s->fuse_tp);
+  const bool two = !s->norm.on && on_device != 2 && (s->plan.rl_chains == 2 || (s->plan.rl_chains == 0 && by_batch)) && s->warmed_chains >= 2 && s->v.RS >= 256 && s->plan.fuse_obs && (!actions || (fold != nullptr && on_device)) && !obs && !rewards &&
+                   s->marks.link_pending < 0 && !(s->v.n_trow > 0 && !s->plan.fuse_tp);
   if (!two) join_forked(s);
   else if (!s->forked) {
     if ((rc = fork_chains(s, 2)) != PEDN_OK) return rc;
@@ -2203,7 +2145,7 @@ int pedn_rl_clock_begin(pedn_sim* s, int32_t t) {
   if (!s) return fail(nullptr, PEDN_E_ARG, "null handle");
   if (!s->rl_ready) return fail(s, PEDN_E_ARG, "pedn_rl_configure has not been called");
   if (t < 1 || t > s->v.T1 - 1) return fail(s, PEDN_E_ARG, "time step outside 1..T");
-  if (!s->fuse_obs || !s->fuse_tp || s->v.n_pairs_corr == 0 || s->node_lp)
+  if (!s->plan.fuse_obs || !s->plan.fuse_tp || s->v.n_pairs_corr == 0 || s->plan.node_lp)
     return fail(s, PEDN_E_ARG, "the clocked step needs the fused second launch (PEDN_FUSE_OBS / PEDN_FUSE_TP), physical links and the classic node model");
   HIP_TRY(s, hipSetDevice(s->device));
   pending_links_first(s);   // (ends a clocked section that is still open)
@@ -2245,7 +2187,7 @@ int pedn_rl_step_clocked(pedn_sim* s, const double* actions, int32_t action_gap,
   for (int k = 0; k < action_gap; ++k) {
     DevView vn = v;
     vn.rl_actions = k == 0 ? fold : nullptr;
-    hipLaunchKernelGGL(clocked_node_kernel_for(s), dim3(g.rgroups, (unsigned)s->n_blocks), dim3(512), s->node_lds, st, vn, -1);
+    hipLaunchKernelGGL(clocked_node_kernel_for(s), dim3(g.rgroups, (unsigned)s->n_blocks), dim3(512), s->plan.node_lds, st, vn, -1);
     const int acc = k > 0 ? 1 : 0;
     hipLaunchKernelGGL(link_turn_kernel_for(v, true, true), g.second(), dim3(256), 0, st, v, -1, g.nlb, g.ntb, g.nth, q, acc);
   }
@@ -2274,7 +2216,7 @@ uint64_t pedn_rl_clock_signature(pedn_sim* s) {
   // its padding keeps the image it was created with; a spurious difference would cost one more capture, never a stale graph)
   mix(&v, sizeof v);
   mix(&s->rl, sizeof s->rl);
-  const int64_t sel[8] = {s->rl_fold, s->n_tf_heavy_quads, s->n_blocks, (int64_t)s->node_lds, s->max_degree, s->node_lp, s->fuse_tp, s->fuse_obs};
+  const int64_t sel[8] = {s->rl_fold, s->n_tf_heavy_quads, s->n_blocks, (int64_t)s->plan.node_lds, s->max_degree, s->plan.node_lp, s->plan.fuse_tp, s->plan.fuse_obs};
   mix(sel, sizeof sel);
   const int64_t on = s->norm.on;   // the normalisation launch and its view (zeroed while off; configure fills every byte it hashes)
   mix(&on, sizeof on);

@@ -42,24 +42,17 @@ struct pedn_sim {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int device = 0;
   int n_nodes = 0, n_turns = 0, n_demand = 0, n_od = 0, n_blocks = 0, n_ent = 0;
-  int link_owner = 0;  // pedn_run: node_kernel(t + 1)'s slot waves perform the link update of t (one launch per step), PEDN_LINK_OWNER
+  // The static plan: which plan the engine steps under at all (pedn_plan.hpp: choose).  Assigned by pedn_create and by nothing else.
+  pedn_plan::EnginePlan plan;
   int packed_by = 1;   // (from the model compiler, pedn_compile.hpp) how nodes were binned into node_kernel's blocks: 0 by degree, 1 by the static load estimate, 2 by measured cost
-  // Single-launch plan of small batches with dynamic turning fractions (inline_tf): every device-computed row is short enough for ONE
-  // wave and its probabilities fit PEDN_TF_INL_ROWS LDS rows (inline_tf_ok), and the whole node_kernel grid is one generation at 4 waves
-  // per SIMD: the slot waves of node_kernel<LU, TF> compute their own rows, a step is one launch.
-  bool inline_tf_ok = false;
-  int inline_tf = 0;
-  int inline_help = 0;      // ... with helper waves: node_kernel_h, sixteen waves per workgroup (PEDN_INLINE_TF=2)
   // A caller that looks at the state after EVERY step (a controller reading densities, an output handler) makes every pending link
   // update a launch of its own and every next step start from stand-alone turning fractions: three launches per step where the plain plan
   // has two.  pedn_step notices (touched: something settled the pending state since the last step) and steps such a caller under the
   // plain plan until two steps in a row go untouched (nine_intersections, step + two reads: 76.0 -> 71 us per step).
   int touched = 0, touch_streak = 0;
   int step_streak = 0;   // consecutive pedn_step(t), pedn_step(t + 1), ... calls with nothing looking at the state in between (see pedn_step)
-  size_t node_lds_tf = 0;   // dynamic LDS of node_kernel<.., TF>
   std::vector<int32_t> h_slot_trow;
-  int rl_chains = 0;   // pedn_rl_step steps the two halves of the envs as two chains that stay forked ACROSS calls (PEDN_RL_CHAINS)
-  int forked = 0;      // stream2 holds work of such a chain that the engine's stream does not order yet (join_forked)
+  int forked = 0;      // stream2 holds work of a chain of pedn_rl_step / pedn_step that the engine's stream does not order yet (join_forked)
   // Device-resident step clock (DevView.clock; pedn_rl_clock_begin .. pedn_rl_clock_end): while `clocked`, env steps are enqueued with
   // constant arguments (pedn_rl_step_clocked) and the host does not know the step the device is at -- every other entry point that
   // steps, reads or changes state first ends the clocked section (clock_end: synchronises and takes the bookkeeping back).
@@ -69,19 +62,10 @@ struct pedn_sim {
   // The marks: what the host knows of the device's state between two launches.  Read by the step planner, advanced by its commits and
   // transitions alone (pedn_plan.hpp); marks.valid_hi is mirrored into v.valid_hi (mirror_marks).
   pedn_plan::StepState marks;
-  // Quiet corridors (DevView.quiet): node_kernel<LU> launches store the words (PEDN_QUIET=0|1, default wherever link_owner is chosen);
-  // which step's words may be used: marks.quiet_valid
-  int quiet = 0;
-  int quiet_lean = 1;   // PEDN_QUIET_LEAN=0|1 (default on): those launches skip the node work that all-zero flows fix (DevView.quiet_lean)
-  uint32_t* d_quiet = nullptr;
-  int zero_elide = 1;   // zero elision (DevView.zg64 / zg32; PEDN_ZERO_ELIDE=0|1, default on): the marks are marks.zhw64 / zhw32
-  // Dead links (pedn_partition.hpp; PEDN_DEAD_LINKS=0|1, default on): in a two-chain range of pedn_run the nodes that provably never see
-  // a pedestrian are stepped by dead_link_kernel -- one launch per step for the whole batch on the engine's stream (dead_streams = 2: one
-  // per half on the two chain streams) -- and node_kernel<LU> runs over a second packing of the other (live) nodes only, for the whole
-  // batch, on a third stream (launch_split_step).
+  uint32_t* d_quiet = nullptr;   // the quiet-corridor words of the full packing (plan.quiet)
+  // Dead links (pedn_partition.hpp; plan.dead_capable): the host's side of the split plan of launch_split_step.
   //   dl_dirty  an input of the proof has changed (or nothing was computed yet): dl_refresh recomputes before the next split range
   //   (marks.dl_grow, marks.dl_off: whether a recomputed set may grow, whether the plan is off until the next full reset)
-  int dead_links = 1;
   bool dl_dirty = true;
   std::vector<char> dl_node;           // [nodes] 1: stepped by dead_link_kernel
   // what the earlier proofs since the last full reset took for sources and found reachable: pedestrians that entered under them are
@@ -97,29 +81,19 @@ struct pedn_sim {
   SlotRec* d_live_rec = nullptr;       // the live packing's slot records (capacity: the full packing's)
   SlotRec* d_dead_rec = nullptr;       // the records of the slots dead_link_kernel steps (copies, in work-list order): dead_prep_kernel's input
   DeadRec* d_dead_drec = nullptr;      // ... and what the lean waves read: their slot-uniform results (dead_prep_kernel, launched by dl_refresh)
-  // The live launch is a chain of latencies whose waves share the CUs with the lean kernel's: beside 8 lean waves per SIMD it took 20 us,
-  // against 12 us alone (profiles/EXPERIMENTS.md #84; what the lean waves take from it is cache more than issue slots, #85).
-  // dead_waves = workgroups of four waves per CU = waves per SIMD the lean kernel may hold (PEDN_DEAD_WAVES=3..8; 8: no limit), through
-  // dynamic LDS that it does not use (dead_lds_bytes in pedn_hip.hip: the size leaves the rest of the CU's LDS to the live workgroups).
-  int dead_waves = 5;
-  int dead_streams = 1;                // PEDN_DEAD_STREAMS=1|2: one lean launch per step for the whole batch, or one per half on the chain streams
   uint32_t* d_quiet_live = nullptr;
   hipStream_t stream3 = nullptr;       // the live bins' stream; null: not seen to overlap with the chains (no split)
   hipEvent_t ev_join3 = nullptr;
-  int fuse_obs = 1;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
   // (The link update as a launch of its own runs one replica per lane -- link_kernel_1r: 42-47 VGPRs, 8 waves per SIMD; melbourne x 1024
   // 12.3-12.6 against 12.7-13.1 us with two replicas per lane, profiles/r03_link_kernel_variants.txt; inside link_turn_kernel, whose
   // budget is set by the turning fractions, it keeps two replicas per lane: half the workgroups.)
   int max_degree = 0;     // largest number of incident corridors of a node
-  size_t node_lds = 0;    // dynamic LDS bytes of node_kernel
-  hipStream_t stream2 = nullptr;   // second half of the replicas in pedn_run (two_streams)
+  hipStream_t stream2 = nullptr;   // second half of the replicas in pedn_run (chains > 1)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int warmed_chains = 1;  // chains whose streams exist and were probed to overlap
-  int chains = 1;         // plan of pedn_run for long ranges: 1 or 2 chains of launches (two_streams = chains > 1)
+  int chains = 1;         // plan of pedn_run for long ranges: 1 or 2 chains of launches (plan.chains, as far as the streams were seen to overlap; pedn_set_streams)
   int stream_probe_attempts = 0;   // warm_chain_streams: probes run until the chains' streams were seen to overlap
   float stream_probe_ms = 0.0f;
-  int two_streams = 0;    // pedn_run launches the two halves of the batch on two streams (replicas are independent)
-  int fuse_tp = 0;     // the link update and the next step's turn probabilities share one launch (launch_step)
   std::vector<int32_t> node_turn_ptr, node_demand_row;
   std::vector<int32_t> h_up_od_ptr, h_upod_od, h_pair_upod;  // route-choice tables needed to re-tabulate P(od | up)
   std::vector<double> h_od_w;
@@ -130,7 +104,6 @@ struct pedn_sim {
   // rule-based controllers (pedn_ctrl_*, pedn_ctrl.hpp): device rows of next actions and episode sums, moving-average buffers
   CtrlState ctrl;
   bool rl_ready = false;
-  bool node_lp = false;   // PEDN_NODE_OPTIMAL: the node LP instead of the classic rule
   bool rl_fold = false;   // gater-only agent set: pedn_rl_step lets node_kernel apply the actions (no launch of rl_apply_kernel)
   std::vector<SlotRec> h_slot_rec;
   SlotRec* d_slot_rec = nullptr;
@@ -171,11 +144,8 @@ struct pedn_sim {
 
 // what the step planner reads of the handle (pedn_plan.hpp)
 static inline pedn_plan::StepCaps step_caps(const pedn_sim* s) {
-  pedn_plan::StepCaps c;
-  c.node_lp = s->node_lp; c.inline_tf = s->inline_tf != 0; c.inline_help = s->inline_help != 0;
-  c.quiet = s->quiet != 0; c.quiet_lean = s->quiet_lean != 0;
-  c.fuse_tp = s->fuse_tp != 0; c.fuse_obs = s->fuse_obs != 0; c.rl_ready = s->rl_ready;
-  c.zero_elide = s->zero_elide != 0; c.hist = s->v.hist != 0; c.pr = s->v.pr != 0;
+  pedn_plan::StepCaps c = pedn_plan::static_caps(s->plan);
+  c.rl_ready = s->rl_ready; c.pr = s->v.pr != 0;
   c.trow = s->v.n_trow > 0; c.links = s->v.n_pairs_corr > 0; c.live = s->n_live_blocks > 0;
   c.T1 = s->v.T1;
   return c;

@@ -3,12 +3,18 @@
 // names, and by tests/plan_prog.cpp on its own (host sanitizers).
 //
 //   StepState    the marks: what the host knows of the device's state between two launches (ONE member of pedn_sim, `marks`)
-//   StepCaps     what a plan reads and a step never changes (pedn_sim fills it: step_caps in pedn_host.hpp)
+//   StepCaps     what a plan reads and a step never changes (static_caps of the engine's plan + what pedn_sim adds: step_caps in pedn_host.hpp)
 //   StepRequest  what a caller asks for: the step, the plan family, the chain
 //   plan_step / commit_step, plan_split_step / commit_split_step
 //                pure decision from (caps, state, request); the commit advances every mark, once per step
 //   transitions  one per event outside a step that touches the marks; nothing else assigns them
+//   Knobs / PlanInputs / EnginePlan, choose, static_caps, report
+//                the plan chooser: which plan an engine steps under at all, decided once at creation (ONE member of pedn_sim, `plan`)
 #pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+
 #include <algorithm>
 
 struct CtrlView;   // (pedn_types.hpp) a request only carries the pointer
@@ -47,7 +53,7 @@ struct StepState {
   int tp_ran = 0;            // a launch_step launched the stand-alone turn_frac_kernel since the caller cleared this (the profiling entry points)
 };
 
-struct StepCaps {
+struct StepCaps {   // (what the engine's plan fixes: static_caps(EnginePlan); rl_ready, pr, trow, links, live, T1: step_caps in pedn_host.hpp)
   bool node_lp = false;      // PEDN_NODE_OPTIMAL: no owner-wave plan
   bool inline_tf = false;    // single-launch plan: node_kernel<LU, TF> computes the device-computed rows
   bool inline_help = false;  // ... by helper waves (node_kernel_h)
@@ -69,7 +75,7 @@ struct StepRequest {
   const double* fold = nullptr; // gater actions that node_kernel applies itself (the first sub-step of an env step)
   const CtrlView* ctrl = nullptr;   // the observing launch is the controller twin
   int chain = -1;               // -1: the whole batch on the engine's stream; else this chain's share of the replicas on its stream
-  int n_chains = 1;             // chains of the step (a split step: its lean launches, pedn_sim.dead_streams)
+  int n_chains = 1;             // chains of the step (a split step: its lean launches, EnginePlan.dead_streams)
   bool profiled = false;        // the launches are bracketed by the caller's events
 };
 
@@ -247,6 +253,201 @@ static inline void clock_ended(StepState& st, const StepCaps& c, int t0, int t_n
     st.link_pending = -1;
   }
   st.valid_hi = valid_hi;
+}
+
+// ---- the plan chooser: which plan an engine steps under at all.  pedn_create calls it once (twice where a device fact turns out
+// false: choose is a pure function, calling it again with a fact turned off changes nothing but what hangs on that fact), the result is
+// pedn_sim::plan and nothing assigns it afterwards.  What moves after creation lives beside it: pedn_sim::chains / warmed_chains (the
+// stream probe, pedn_set_streams), rl_fold (pedn_rl_configure).
+
+// The PEDN_* knobs of the step plan as the environment gives them when an engine is created; -1: unset (which is not 0: the default of
+// some depends on the model or on an earlier decision).
+struct Knobs {
+  int fuse_tp = -1;        // PEDN_FUSE_TP=0|1
+  int fuse_obs = -1;       // PEDN_FUSE_OBS=0|1
+  int streams = -1;        // PEDN_STREAMS=1|2 (anything but 2 is 1)
+  int link_owner = -1;     // PEDN_LINK_OWNER=0|1
+  int inline_tf = -1;      // PEDN_INLINE_TF=0|1|2 (any other value is 1)
+  int quiet = -1;          // PEDN_QUIET=0|1
+  int quiet_lean = -1;     // PEDN_QUIET_LEAN=0|1
+  int zero_elide = -1;     // PEDN_ZERO_ELIDE=0|1
+  int rl_chains = -1;      // PEDN_RL_CHAINS=1|2 (anything but 2 is 1)
+  int dead_links = -1;     // PEDN_DEAD_LINKS=0|1
+  int dead_waves = -1;     // PEDN_DEAD_WAVES, clamped to 3..8
+  int dead_streams = -1;   // PEDN_DEAD_STREAMS=1|2 (anything but 1 is 2)
+  int stream_probe = -1;   // PEDN_STREAM_PROBE=0|1
+};
+
+// the one place that reads them
+static inline Knobs knobs_from_env() {
+  Knobs k;
+  const auto flag = [](const char* name, int* out) { if (const char* f = getenv(name)) *out = atoi(f) != 0; };
+  flag("PEDN_FUSE_TP", &k.fuse_tp); flag("PEDN_FUSE_OBS", &k.fuse_obs); flag("PEDN_LINK_OWNER", &k.link_owner);
+  flag("PEDN_QUIET", &k.quiet); flag("PEDN_QUIET_LEAN", &k.quiet_lean); flag("PEDN_ZERO_ELIDE", &k.zero_elide);
+  flag("PEDN_DEAD_LINKS", &k.dead_links); flag("PEDN_STREAM_PROBE", &k.stream_probe);
+  if (const char* f = getenv("PEDN_STREAMS")) k.streams = atoi(f) == 2 ? 2 : 1;
+  if (const char* f = getenv("PEDN_INLINE_TF")) k.inline_tf = atoi(f) == 2 ? 2 : atoi(f) != 0;
+  if (const char* f = getenv("PEDN_RL_CHAINS")) k.rl_chains = atoi(f) == 2 ? 2 : 1;
+  if (const char* f = getenv("PEDN_DEAD_WAVES")) k.dead_waves = std::max(3, std::min(atoi(f), 8));
+  if (const char* f = getenv("PEDN_DEAD_STREAMS")) k.dead_streams = atoi(f) == 1 ? 1 : 2;
+  return k;
+}
+
+// What the decision reads of the description and of the compiled tables (pedn_compile::Tables), and two facts of the device.
+struct PlanInputs {
+  int RS = 128;            // replicas rounded up to a multiple of 128
+  int N = 0, L = 0;        // nodes, physical links
+  int n_trow = 0;          // rows of turning fractions computed on the device
+  bool node_lp = false;    // the node model is PEDN_NODE_OPTIMAL
+  bool hist = false;       // recent-history mode
+  bool inline_tf_ok = false;   // every device-computed row is short enough for ONE wave and its probabilities fit PEDN_TF_INL_ROWS LDS rows
+  int n_blocks = 0;        // workgroups per replica group of the full packing
+  int tiles = 0;           // doubles / 64 of the m * m tiles of its fullest block
+  int n_rec = 0;           // its slot records (the idle block included)
+  int tf_wave_lds = 0;     // doubles of LDS that each of the eight slot waves of node_kernel<.., TF> has for its own row (PEDN_TF_INL_LDS)
+  // The device facts: was the request for more dynamic LDS than a kernel gets by default (64 KB; gfx950 has 160 KB per CU) granted for
+  // node_kernel<LU, TF>, and for node_kernel_h?  pedn_create asks (hipFuncSetAttribute) only where the answer can matter -- lds_tf where
+  // inline_candidate and node_lds_tf > 64 KB, lds_h where the plan chosen with lds_h = true has inline_help and node_lds_tf > 64 KB -- and
+  // leaves the fact at true otherwise: choose reads neither anywhere else.
+  bool lds_tf = true, lds_h = true;
+};
+
+struct EnginePlan {
+  bool node_lp = false;    // PEDN_NODE_OPTIMAL: the node LP instead of the classic rule; no owner-wave plan
+  bool hist = false;       // recent-history mode (of the inputs): ring rows are reused -- no zero gate, no dead-link plan
+  bool fuse_tp = true;     // the link update and the next step's turn probabilities share one launch (launch_step)
+  bool fuse_obs = true;    // pedn_rl_step: observations / rewards ride in the link update's launch (PEDN_FUSE_OBS=0: own launch)
+  int chains = 1;          // chains of launches WANTED for long ranges of pedn_run, 1 or 2; pedn_sim::chains is what the stream probe left of it
+  bool link_owner = false; // pedn_run: node_kernel(t + 1)'s slot waves perform the link update of t (one launch per step)
+  // Single-launch plan of small batches with dynamic turning fractions: every device-computed row is short enough for ONE wave
+  // (inline_tf_ok) and the whole node_kernel grid is one generation: the slot waves of node_kernel<LU, TF> compute their own rows, a
+  // step is one launch.
+  bool inline_tf = false;
+  bool inline_help = false;   // ... with helper waves: node_kernel_h, sixteen waves per workgroup
+  bool quiet = false;      // quiet corridors (DevView.quiet): node_kernel<LU> launches store the words; which step's may be used: marks.quiet_valid
+  bool quiet_lean = true;  // ... and skip the node work that all-zero flows fix (DevView.quiet_lean)
+  bool zero_elide = true;  // zero elision (DevView.zg64 / zg32): the marks are marks.zhw64 / zhw32
+  int rl_chains = 0;       // pedn_rl_step steps the two halves of the envs as two chains that stay forked ACROSS calls: 0 by batch, 1 | 2 forced
+  size_t node_lds = 0;     // dynamic LDS bytes of node_kernel
+  size_t node_lds_tf = 0;  // ... of node_kernel<.., TF> and node_kernel_h
+  int32_t tf_lds_off = 0;  // DevView.tf_lds_off: node_lds in doubles
+  // Dead links (pedn_partition.hpp): in a two-chain range of pedn_run the nodes that provably never see a pedestrian are stepped by
+  // dead_link_kernel -- one launch per step for the whole batch on the engine's stream (dead_streams = 2: one per half on the two chain
+  // streams) -- and node_kernel<LU> runs over a second packing of the other (live) nodes only, for the whole batch, on a third stream
+  // (launch_split_step).
+  bool dead_links = true;
+  // The live launch is a chain of latencies whose waves share the CUs with the lean kernel's: beside 8 lean waves per SIMD it took 20 us,
+  // against 12 us alone (profiles/EXPERIMENTS.md #84; what the lean waves take from it is cache more than issue slots, #85).
+  // dead_waves = workgroups of four waves per CU = waves per SIMD the lean kernel may hold (3..8; 8: no limit), through dynamic LDS that
+  // it does not use (dead_lds_bytes in pedn_hip.hip: the size leaves the rest of the CU's LDS to the live workgroups).
+  int dead_waves = 5;
+  int dead_streams = 1;    // 1 | 2: one lean launch per step for the whole batch, or one per half on the chain streams
+  bool dead_capable = false;   // the dead-link plan can be taken at all: its buffers are allocated (pedn_sim::d_live_rec and what goes with it)
+  // 32-bit words of [2][slot positions][RS / 64][own | inbox] for the full packing (0: no quiet words; melbourne x 1024 ~ 0.3 MB) and
+  // for the live packing at its capacity (0: not dead_capable)
+  size_t quiet_words = 0, quiet_words_live = 0;
+  bool stream_probe = true;   // PEDN_STREAM_PROBE=0: the chains' streams are taken to overlap without being timed (warm_chain_streams)
+};
+
+constexpr size_t LDS_DEFAULT = 64 * 1024, LDS_PER_CU = 160 * 1024;
+
+// LDS of node_kernel: 8 (LP: 16) rows of 64 doubles + the m * m tiles of the fullest block; <.., TF>: + the eight slot waves' own rows
+// (register budget of the node kernels: node_kernel_waves() in pedn_kernels.hpp)
+static inline size_t node_lds_bytes(const PlanInputs& in) { return (size_t)((in.node_lp ? 16 : 8) + in.tiles) * 64 * sizeof(double); }
+static inline size_t node_lds_tf_bytes(const PlanInputs& in) { return node_lds_bytes(in) + (size_t)8 * in.tf_wave_lds * sizeof(double); }
+// could the single-launch plan be taken if the device grants the LDS it needs?
+static inline bool inline_candidate(const PlanInputs& in) { return in.inline_tf_ok && !in.node_lp && node_lds_tf_bytes(in) <= LDS_PER_CU; }
+// slot records the live packing of the dead-link plan may need: at most one bin per node, one idle block behind them
+static inline size_t live_rec_capacity(int n_nodes) { return ((size_t)n_nodes + 1) * 8; }
+
+static inline EnginePlan choose(const PlanInputs& in, const Knobs& k) {
+  EnginePlan p;
+  p.node_lp = in.node_lp;
+  p.hist = in.hist;
+  p.node_lds = node_lds_bytes(in);
+  p.node_lds_tf = node_lds_tf_bytes(in);
+  p.tf_lds_off = (int32_t)(p.node_lds / sizeof(double));
+  // The link update of t and the turning fractions of t+1 share one launch (both only read what node_kernel(t) and earlier
+  // launches wrote); PEDN_FUSE_TP=0 gives the fractions a launch of their own in front of node_kernel(t+1).
+  if (k.fuse_tp >= 0) p.fuse_tp = k.fuse_tp != 0;
+  if (k.fuse_obs >= 0) p.fuse_obs = k.fuse_obs != 0;
+  // two chains of launches (one per half of the replicas) in pedn_run; PEDN_STREAMS=1|2, pedn_set_streams.  Default from 640
+  // replicas: one chain's launch leaves wave places empty while it fills and drains, and the other half's launches use them
+  // (delft x 1024: 51.7 -> 45.3 us per step in round 2; round 5, melbourne / delft: x 640 25.8 -> 23.6 / 36.2 -> 34.3, x 768 27.1 -> 24.8,
+  // x 896 31.3 -> 27.5 / 45.3 -> 40.7; x 512 19.2 either way).  The halves are whole 128-replica segments (view_of): 640 = 384 + 256.
+  p.chains = k.streams >= 0 ? k.streams : in.RS >= 640 ? 2 : 1;
+  // Owner-wave plan of pedn_run (launch_step: lazy): node_kernel<LU>(t + 1) performs the link update of t, one launch per step.  The
+  // default for models whose second launch is the link update alone (no turning fractions computed on the device): melbourne x 1024
+  // 37.4 -> 32.7-33.7 us per step on one chain, 34.6 -> 30.3 on two (profiles/r04_owner_wave.txt).  With dynamic rows the second launch
+  // stays (node_kernel(t + 1) needs the fractions that need node_kernel(t)'s flows) and the longer node_kernel costs more than the
+  // link-update workgroups that leave it save (delft x 1024: 42.1-42.6 -> 44.2).  PEDN_LINK_OWNER=0|1 overrides.
+  p.link_owner = k.link_owner >= 0 ? k.link_owner != 0 : in.n_trow == 0 && !in.node_lp;
+  // Single-launch plan with dynamic turning fractions: the rows computed inside node_kernel<LU, TF> by the slot waves themselves.  That
+  // instantiation is built for 2 waves per SIMD (1 block per CU): only where the whole grid is one generation of them -- small
+  // batches, which are chains of latencies and gain a whole launch (nine_intersections x 256: 17.2 -> ... us per step).
+  const bool large = p.node_lds_tf > LDS_DEFAULT;
+  const bool possible = inline_candidate(in) && (!large || in.lds_tf);
+  // ... by HELPER waves (node_kernel_h: sixteen waves per workgroup at 128 VGPRs, still one workgroup per CU): the row (~5 us) and the
+  // slot wave's own chain (~5 us) side by side -- nine_intersections x 256 16.2 -> 12.5 us per step, 45_intersections x 1024 (272
+  // workgroups) 17.9 -> 13.6, x 1280 (340) 20.4 -> 14.7 under pedn_run's two chains and 20.5 -> 19.1 step by step; x 1536 (408) still
+  // wins under pedn_run (21.3 -> 17.5) but not step by step (22.3 -> 23.1), at 544 (x 2048) two launches per step are faster either
+  // way (22.9 against 23.7).  The default up to 352 workgroups; PEDN_INLINE_TF=0 two launches, 1 the slot waves' own rows, 2 helper
+  // waves (forced whatever the grid).  profiles/r04_inline_helpers.txt
+  p.inline_tf = possible && (size_t)(in.RS / 64) * (size_t)in.n_blocks <= 352;
+  p.inline_help = p.inline_tf;
+  if (k.inline_tf >= 0) { p.inline_tf = k.inline_tf != 0 && possible; p.inline_help = k.inline_tf == 2 && possible; }
+  if (large && !in.lds_h) p.inline_help = false;
+  if (p.inline_tf) p.link_owner = true;
+  // quiet corridors: the owner-wave launches skip the loads of corridors that are empty in all 64 replicas of a group (node_step)
+  p.quiet = k.quiet >= 0 ? k.quiet != 0 : p.link_owner && !in.node_lp;
+  if (k.quiet_lean >= 0) p.quiet_lean = k.quiet_lean != 0;
+  // zero elision: the node kernels skip +0.0 stores into rows that hold +0.0 since the last full reset (zero_gate)
+  if (k.zero_elide >= 0) p.zero_elide = k.zero_elide != 0;
+  // 0 = by batch: two chains where the step is not a pure chain of latencies any more -- from 4096 envs, and from 1024 with per-env
+  // scenarios (45_intersections: 2048 envs plain 24.8-25.2 -> 24.7-25.7 us per env step, randomised 27.5-27.9 -> 25.6-26.0;
+  // 4096 envs 40.6 -> 35.9; profiles/r04_rl_chains.txt); PEDN_RL_CHAINS=1|2 forces
+  if (k.rl_chains >= 0) p.rl_chains = k.rl_chains;
+  if (k.dead_links >= 0) p.dead_links = k.dead_links != 0;
+  if (k.dead_waves >= 0) p.dead_waves = k.dead_waves;
+  if (k.dead_streams >= 0) p.dead_streams = k.dead_streams;
+  if (k.stream_probe >= 0) p.stream_probe = k.stream_probe != 0;
+  const size_t groups = (size_t)(in.RS / 64);
+  if (p.quiet) p.quiet_words = (size_t)2 * (size_t)in.n_rec * groups * 2;
+  // dead links: room for a packing of the live nodes alone, its quiet words (node_step indexes the words of one step, half of them, in
+  // 32 bits), and the records of every slot dead_link_kernel may step
+  const size_t live_words = (size_t)2 * live_rec_capacity(in.N) * groups * 2;
+  p.dead_capable = p.dead_links && p.quiet && p.link_owner && !p.inline_tf && !in.hist && !in.node_lp && in.n_trow == 0 && in.L > 0 &&
+                   live_words / 2 < ((size_t)1 << 31);
+  if (p.dead_capable) p.quiet_words_live = live_words;
+  return p;
+}
+
+// the part of StepCaps that the engine's plan fixes
+static inline StepCaps static_caps(const EnginePlan& p) {
+  StepCaps c;
+  c.node_lp = p.node_lp; c.inline_tf = p.inline_tf; c.inline_help = p.inline_help;
+  c.quiet = p.quiet; c.quiet_lean = p.quiet_lean;
+  c.fuse_tp = p.fuse_tp; c.fuse_obs = p.fuse_obs;
+  c.zero_elide = p.zero_elide; c.hist = p.hist;
+  return c;
+}
+
+// What pedn_plan_info reports of the plan; links: the model has physical links (n_pairs_corr > 0).
+struct PlanReport {
+  int owner_wave;    // [1] steps take the owner-wave family (with device-computed rows: the single-launch plan, inline_tf)
+  int quiet;         // [5] ... and its launches keep and use the quiet-corridor words
+  int zero_elide;    // [6] the node kernels may skip +0.0 stores into clean rows
+  int quiet_lean;    // [8] the quiet-corridor launches take the lean path
+  int dead_links;    // [9] may be other than 0: the split plan is not ruled out for good (the rest: dl_split_ok, pedn_hip.hip)
+};
+static inline PlanReport report(const EnginePlan& p, bool links) {
+  PlanReport r;
+  r.owner_wave = p.link_owner && !p.node_lp && links;
+  r.quiet = p.quiet && r.owner_wave;
+  r.zero_elide = p.zero_elide && !p.hist;
+  r.quiet_lean = p.quiet_lean && r.quiet;
+  r.dead_links = p.dead_capable && links;
+  return r;
 }
 
 }  // namespace pedn_plan

@@ -1,5 +1,6 @@
-"""Plumbing of tests/test_step_plan_host.py and tests/test_gpu_step_plan.py: the stand-alone driver of the step planner (tests/plan_prog.cpp over
-pednstream_amd/csrc/pedn_plan.hpp), the event scripts it reads -- the library's entry points restated as the events they make of a call --
+"""Plumbing of tests/test_step_plan_host.py, tests/test_gpu_step_plan.py and tests/test_gpu_engine_plan.py: the stand-alone driver of the step
+planner and the plan chooser (tests/plan_prog.cpp over pednstream_amd/csrc/pedn_plan.hpp), the grids the chooser is run over, the event scripts
+the planner reads -- the library's entry points restated as the events they make of a call --
 and Shadow, a restatement of what the KERNELS need of a sequence of launches: a shadow of device memory per half of the replicas, written
 from the kernels' reads and writes, not from the planner's text."""
 import os
@@ -44,6 +45,66 @@ def run_prog(exe, scripts, path):
             launches.append((tok[0], _kv(tok[1:])))
     assert len(out) == len(scripts) and all(len(o) == len(s[1]) for o, s in zip(out, scripts))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the plan chooser
+TF_WAVE_LDS = (8 + 8 - 1) * 64          # PEDN_TF_INL_LDS (pedn_kernels.hpp): (PEDN_TF_INL_ROWS + PEDN_MAX_DEGREE - 1) rows of 64 doubles
+KNOBS = dict(fuse_tp=(-1, 0, 1), fuse_obs=(-1, 0, 1), streams=(-1, 1, 2), link_owner=(-1, 0, 1), inline_tf=(-1, 0, 1, 2), quiet=(-1, 0, 1),
+             quiet_lean=(-1, 0, 1), zero_elide=(-1, 0, 1), rl_chains=(-1, 1, 2), dead_links=(-1, 0, 1), dead_waves=(-1, 3, 5, 8), dead_streams=(-1, 1, 2),
+             stream_probe=(-1, 0, 1))          # every knob unset (-1) and at each value knobs_from_env can give it (dead_waves: the ends and the default)
+# The knobs that another decision reads (link_owner: the default of quiet, dead_capable; inline_tf: link_owner; quiet and dead_links:
+# dead_capable) are crossed with each other and with every input; each of the others only sets its own field of the plan, so a point
+# draws their values from a hash of its index (all 13 crossed with the inputs would be 10^10 points).
+CROSSED_KNOBS = ("link_owner", "inline_tf", "quiet", "dead_links")
+# The inputs at their edges.  grid: n_blocks such that (RS / 64) * n_blocks is 352, and the smallest product above it that RS allows (353
+# itself only for RS / 64 = 1); lds_tf_min: tiles such that node_lds_tf is exactly 64 KB / 160 KB, and one tile (512 B, the formula's
+# step) above.  inline_tf_ok comes with n_trow > 0 only (pedn_compile.hpp: no row, nothing to inline), so that half is left out below.
+GRID_INPUTS = dict(RS=(128, 576, 640, 704), grid=(352, 353), lds_tf_min=(64 << 10, (64 << 10) + 8, 160 << 10, (160 << 10) + 8), lds_tf=(0, 1), lds_h=(0, 1),
+                   inline_tf_ok=(0, 1), node_lp=(0, 1), hist=(0, 1), n_trow=(0, 4), L=(0, 5))
+GRID_FIXED = dict(N=10, n_rec=24, tf_wave_lds=TF_WAVE_LDS)
+
+
+def run_choose(exe, spec, path):
+    """spec: [(key, values)] in the driver's order (a key that starts with ~ is drawn, not crossed); {column: int64 array over the points}"""
+    with open(path, "w") as f:
+        f.write("".join(f"{k}={','.join(str(int(v)) for v in (vals if isinstance(vals, (tuple, list)) else (vals,)))}\n" for k, vals in spec))
+    r = subprocess.run([exe, "--choose", str(path)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]          # the sanitizers stayed silent
+    header, _, body = r.stdout.partition("\n")
+    cols = header.split()
+    table = np.fromstring(body, dtype=np.int64, sep=" ").reshape(-1, len(cols))
+    return {c: table[:, i] for i, c in enumerate(cols)}
+
+
+def grid_spec():
+    return (list(GRID_FIXED.items()) + list(GRID_INPUTS.items()) + [("k_" + k, KNOBS[k]) for k in CROSSED_KNOBS]
+            + [("~k_" + k, v) for k, v in KNOBS.items() if k not in CROSSED_KNOBS] + [("~links", (0, 1))])          # (links: only the report reads it)
+
+
+def choose_one(exe, inputs, knobs, path):
+    """the plan, static caps (c_*) and report (r_*) of one engine: {column: int}"""
+    out = run_choose(exe, list(inputs.items()) + [("k_" + k, v) for k, v in knobs.items()], path)
+    assert len(out["RS"]) == 1
+    return {k: int(v[0]) for k, v in out.items()}
+
+
+def compiled_inputs(compiled, model, n_replicas):
+    """PlanInputs from what tests/compile_prog.cpp printed for the model (compile_model.run_prog) -- and, beside them, `links` and `packed_by`"""
+    info, full = compiled["info"][0], compiled["full_info"][0]
+    inputs = dict(RS=(n_replicas + 127) // 128 * 128, N=int(model["n_nodes"]), L=int(model["n_links"]), n_trow=int(info[1]),
+                  node_lp=int(model.get("node_model", 0)), hist=int(model.get("history_mode", 0)), inline_tf_ok=int(info[4]), n_blocks=int(full[0]),
+                  tiles=int(full[1]), n_rec=int(full[4]), tf_wave_lds=TF_WAVE_LDS, links=int(len(compiled["corr"][0]) > 0))
+    return inputs, int(info[5])
+
+
+def knobs_of(environ):
+    """knobs_from_env restated for the values the tests set: 0 / 1 / 2 as text, unset"""
+    return {k: int(environ["PEDN_" + k.upper()]) for k in KNOBS if "PEDN_" + k.upper() in environ}
+
+
+def caps_of(plan, **runtime):
+    """the StepCaps of an engine under `plan` (a row of run_choose): static_caps + the run-time entries"""
+    return dict({k: plan["c_" + k] for k in ("node_lp", "inline_tf", "inline_help", "quiet", "quiet_lean", "fuse_tp", "fuse_obs", "zero_elide", "hist")}, **runtime)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the library's calls as events

@@ -15,6 +15,15 @@
 //   foreign f64=.. f32=.. a zero-copy pointer was handed out (pedn_device_ptr: behind flush_all)
 //   clock t=.. k=..       pedn_rl_clock_begin(t), k clocked steps, clock_end -- `refused` where the fractions of t are not prepared
 //   set k=v ...           marks set directly
+//
+//   plan_prog --choose SPEC   the plan chooser (choose / static_caps / report) over a grid.  SPEC has one `key=v1,v2,...` per line: the
+//                         cross product of all lines is enumerated, the first line slowest; a line `~key=v1,v2,...` is not crossed -- each
+//                         point draws its value from a hash of the point's index.  Keys: the fields of PlanInputs, `links`, the fields of
+//                         Knobs as k_<name> (-1: unset), and two that stand for an input they set from the others:
+//                           grid=G           n_blocks = the fewest blocks whose (RS / 64) * n_blocks is at least G
+//                           lds_tf_min=B     tiles = the fewest tiles whose node_lds_tf is at least B bytes
+//                         Prints a header line of column names, then one line of integers per point: the inputs, the knobs, the plan,
+//                         static_caps as c_<name>, report as r_<name>.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,6 +32,7 @@
 #include <map>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "../pednstream_amd/csrc/pedn_plan.hpp"
 
@@ -115,8 +125,85 @@ static void clocked(const Args& a) {
   clock_ended(g_st, g_caps, t, t + k, vhi);
 }
 
+// ---- the plan chooser over a grid
+static const char* const CHOOSE_KEYS[] = {"RS", "N", "L", "n_trow", "node_lp", "hist", "inline_tf_ok", "n_blocks", "tiles", "n_rec", "tf_wave_lds", "lds_tf", "lds_h", "links",
+                                          "k_fuse_tp", "k_fuse_obs", "k_streams", "k_link_owner", "k_inline_tf", "k_quiet", "k_quiet_lean", "k_zero_elide", "k_rl_chains",
+                                          "k_dead_links", "k_dead_waves", "k_dead_streams", "k_stream_probe", "grid", "lds_tf_min"};
+enum { K_RS, K_N, K_L, K_TROW, K_LP, K_HIST, K_OK, K_BLOCKS, K_TILES, K_REC, K_WAVE_LDS, K_LDS_TF, K_LDS_H, K_LINKS, K_KNOB0, K_GRID = K_KNOB0 + 13, K_LDS_MIN, K_COUNT };
+struct Dim { int key; std::vector<long> values; bool crossed; };
+
+static int choose_grid(const char* path) {
+  std::ifstream f(path);
+  if (!f) { fprintf(stderr, "cannot read %s\n", path); return 2; }
+  std::vector<Dim> dims;
+  std::string line;
+  while (std::getline(f, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    Dim d;
+    d.crossed = line[0] != '~';
+    const size_t eq = line.find('='), k0 = d.crossed ? 0 : 1;
+    if (eq == std::string::npos) { fprintf(stderr, "bad line %s\n", line.c_str()); return 2; }
+    for (d.key = 0; d.key < K_COUNT && line.compare(k0, eq - k0, CHOOSE_KEYS[d.key]) != 0; ++d.key) {}
+    if (d.key == K_COUNT) { fprintf(stderr, "unknown key in %s\n", line.c_str()); return 2; }
+    std::istringstream vals(line.substr(eq + 1));
+    std::string tok;
+    while (std::getline(vals, tok, ',')) d.values.push_back(atol(tok.c_str()));
+    if (d.values.empty()) { fprintf(stderr, "no value in %s\n", line.c_str()); return 2; }
+    dims.push_back(d);
+  }
+  size_t n_points = 1;
+  for (const Dim& d : dims) if (d.crossed) n_points *= d.values.size();
+  for (int k = 0; k < K_GRID; ++k) printf("%s ", CHOOSE_KEYS[k]);
+  printf("fuse_tp fuse_obs chains link_owner inline_tf inline_help quiet quiet_lean zero_elide rl_chains node_lds node_lds_tf tf_lds_off "
+         "dead_links dead_waves dead_streams dead_capable quiet_words quiet_words_live stream_probe inline_candidate "
+         "c_node_lp c_inline_tf c_inline_help c_quiet c_quiet_lean c_fuse_tp c_fuse_obs c_zero_elide c_hist "
+         "r_owner_wave r_quiet r_zero_elide r_quiet_lean r_dead_links\n");
+  std::string out;
+  const auto put = [&out](long long x) { char b[24]; out.append(b, (size_t)snprintf(b, sizeof b, "%lld ", x)); };
+  for (size_t i = 0; i < n_points; ++i) {
+    long a[K_COUNT];
+    const long dflt[K_COUNT] = {128, 0, 0, 0, 0, 0, 0, 0, 0, 8, 0, 1, 1, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+    std::copy(dflt, dflt + K_COUNT, a);
+    size_t rest = i;
+    for (size_t j = dims.size(); j-- > 0;) {
+      const Dim& d = dims[j];
+      if (d.crossed) { a[d.key] = d.values[rest % d.values.size()]; rest /= d.values.size(); }
+      else {   // (splitmix64 of the point and the line)
+        uint64_t z = (uint64_t)i * 64 + j + 0x9e3779b97f4a7c15ull;
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull; z ^= z >> 31;
+        a[d.key] = d.values[z % d.values.size()];
+      }
+    }
+    PlanInputs in;
+    in.RS = (int)a[K_RS]; in.N = (int)a[K_N]; in.L = (int)a[K_L]; in.n_trow = (int)a[K_TROW];
+    in.node_lp = a[K_LP] != 0; in.hist = a[K_HIST] != 0; in.inline_tf_ok = a[K_OK] != 0;
+    in.n_blocks = (int)a[K_BLOCKS]; in.tiles = (int)a[K_TILES]; in.n_rec = (int)a[K_REC];
+    in.tf_wave_lds = (int)a[K_WAVE_LDS]; in.lds_tf = a[K_LDS_TF] != 0; in.lds_h = a[K_LDS_H] != 0;
+    if (a[K_GRID] >= 0) in.n_blocks = (int)((a[K_GRID] + in.RS / 64 - 1) / (in.RS / 64));
+    while ((long)node_lds_tf_bytes(in) < a[K_LDS_MIN]) ++in.tiles;
+    a[K_BLOCKS] = in.n_blocks; a[K_TILES] = in.tiles;
+    Knobs k;
+    int* const knob[13] = {&k.fuse_tp, &k.fuse_obs, &k.streams, &k.link_owner, &k.inline_tf, &k.quiet, &k.quiet_lean, &k.zero_elide, &k.rl_chains, &k.dead_links,
+                           &k.dead_waves, &k.dead_streams, &k.stream_probe};
+    for (int j = 0; j < 13; ++j) *knob[j] = (int)a[K_KNOB0 + j];
+    const EnginePlan p = choose(in, k);
+    const StepCaps c = static_caps(p);
+    const PlanReport r = report(p, a[K_LINKS] != 0);
+    for (int j = 0; j < K_GRID; ++j) put(a[j]);
+    const long long plan[] = {p.fuse_tp, p.fuse_obs, p.chains, p.link_owner, p.inline_tf, p.inline_help, p.quiet, p.quiet_lean, p.zero_elide, p.rl_chains, (long long)p.node_lds,
+                              (long long)p.node_lds_tf, p.tf_lds_off, p.dead_links, p.dead_waves, p.dead_streams, p.dead_capable, (long long)p.quiet_words,
+                              (long long)p.quiet_words_live, p.stream_probe, inline_candidate(in), c.node_lp, c.inline_tf, c.inline_help, c.quiet, c.quiet_lean, c.fuse_tp,
+                              c.fuse_obs, c.zero_elide, c.hist, r.owner_wave, r.quiet, r.zero_elide, r.quiet_lean, r.dead_links};
+    for (long long x : plan) put(x);
+    out += '\n';
+    if (out.size() > (1 << 20) || i + 1 == n_points) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: plan_prog SCRIPT\n"); return 2; }
+  if (argc >= 3 && strcmp(argv[1], "--choose") == 0) return choose_grid(argv[2]);
+  if (argc < 2) { fprintf(stderr, "usage: plan_prog SCRIPT | plan_prog --choose SPEC\n"); return 2; }
   std::ifstream f(argv[1]);
   if (!f) { fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
   std::string line;
