@@ -544,6 +544,28 @@ int pedn_sac_td_target(const float* next_states, const float* rewards, const flo
  * 0 <= tau <= 1): the reference's soft_update of every target critic at once.  One launch on `stream`, capturable like the above. */
 int pedn_sac_soft_update(float* target, const float* online, int64_t n_floats, double tau, void* stream);
 
+/* ---- SAC critic gradients and Adam steps of all agents (rl/agents/SAC.py:320-341, the critic half of SACAgent.update) -----------------------
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 18 (tests/sac_critic_model.py restates it in numpy).
+ *   states       f32 [batch][stack_size][n_obs], actions f32 [batch][n_actions] (what the critics see: the stored actions), td_target f32
+ *                [batch][n_agents] (pedn_sac_td_target's)
+ *   table, critic_table   as for pedn_sac_td_target
+ *   online_params, grads, exp_avg, exp_avg_sq   f32 [pack_floats] each, one layout (pedn_sac_td_target's target_params), 16-byte aligned;
+ *                pack_floats a multiple of 4; the padding between the critics is +0.0 and stays so
+ *   workspace    f32 [ceil(batch / 32)][pack_floats + 2 * n_agents rounded up to 4], zeroed by the caller once, 16-byte aligned
+ *   q            f32 [2][batch][n_agents]: q1, q2; losses f32 [n_agents][2]: mean((q - td_target)^2) of critic 1 and critic 2
+ *   adam_state   int64 [4], set by the caller once: 0 the step count (0), 1 the ticket of the launch's workgroups (0), 2 and 3 the
+ *                doubles beta1^t and beta2^t (1.0)
+ * Two launches on `stream`: the tiles' partial gradients of both MSE losses (tiles of 32 rows, rows ascending), then their sum (tiles
+ * ascending) into grads and losses and, if do_adam is not 0, one torch.optim.Adam step (no weight decay, no amsgrad) of exp_avg, exp_avg_sq
+ * and online_params in place, which advances adam_state.  With do_adam = 0 nothing but grads, losses, q and the workspace is written.
+ * 0 <= lr, eps < inf, 0 <= beta < 1; hidden_size must be 64.  No allocation, no synchronisation, no event query, constant arguments: safe
+ * under stream capture. */
+int pedn_sac_critic_update(const float* states, const float* actions, const float* td_target, const int32_t* table, const int32_t* critic_table,
+                           float* online_params, float* grads, float* exp_avg, float* exp_avg_sq, float* workspace, float* q, float* losses,
+                           int64_t* adam_state, int64_t pack_floats, int32_t batch, int32_t stack_size, int32_t n_obs, int32_t n_actions,
+                           int32_t n_agents, int32_t hidden_size, double lr, double beta1, double beta2, double eps, int32_t do_adam,
+                           void* stream);
+
 /* ---- PPO's value critics and old log-probabilities of a whole rollout (rl/agents/PPO_org.py:175-197 StackedValueNetwork, :543-577) -------
  * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 16 (tests/ppo_eval_model.py restates it in numpy).
  *   obs          f32 [T + 1][N][n_obs]: every observation once (array 4 of pedn_rollout_device_ptr behind pedn_rollout_finish).  The state

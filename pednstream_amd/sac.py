@@ -13,7 +13,12 @@ section 15, tests/sac_target_model.py restates it in numpy.
     ...                                           # critic / actor / alpha losses and optimiser steps in torch, on the bound modules
     sac.soft_update()
 
-``SacTargets`` is the constructor on a ``StackedActors`` (no env).  Backward passes and the optimisers stay in torch.
+``SacTargets`` is the constructor on a ``StackedActors`` (no env).
+
+The critic step of the gradient half runs on the device too (pednstream_amd/csrc/pedn_critic.hpp; the contract is DESIGN section 18,
+tests/sac_critic_model.py restates it in numpy): ``sac.critic_update(s, critic_actions, td)`` between ``td_target`` and ``soft_update`` computes
+q1, q2, both MSE losses, their gradients and one Adam step of every online critic in two launches.  The actor and alpha losses, their
+backward passes and optimisers stay in torch, on the bound modules.
 """
 import ctypes as C
 import math
@@ -28,6 +33,8 @@ WHICH = ("critic_1", "critic_2", "target_critic_1", "target_critic_2")
 ACTION_OUTPUTS = ("mu", "std", "eps", "logp", "next_actions")
 AGENT_OUTPUTS = ("entropy", "q1", "q2", "td_target")
 TILE = 8                        # rows per workgroup of sac_target_kernel (PEDN_SAC_TILE)
+CRITIC_TILE = 32                # rows per workgroup of critic_grad_kernel (PEDN_CRITIC_TILE): part of section 18's order of sums
+ADAM_STATE_INIT = (0, 0, 0x3FF0000000000000, 0x3FF0000000000000)      # the step count, the ticket, the doubles beta1^0 and beta2^0
 
 
 def critic_shapes(obs_w, act_w, stack_size, hidden_size=HIDDEN):
@@ -89,6 +96,9 @@ class SacTargets:
         self._dev = None                # the device tensors, allocated once (a captured graph owns their addresses)
         self._out = {}                  # batch size -> (out_actions [5, B, n_actions], out_agents [4, B, n_agents])
         self._last = None
+        self._cdev = None               # the critic step's device tensors, allocated by its first use
+        self._cout = {}                 # batch size -> (workspace [tiles, stride], q [2, B, n_agents])
+        self._clast = None
 
     # ------------------------------------------------------------------------------------------------ parameters
     def _index(self, agent_id):
@@ -219,6 +229,124 @@ class SacTargets:
                                           C.c_void_p(int(stream)) if stream else None)
         if rc != 0:
             raise (ValueError if rc == -1 else RuntimeError)(f"pedn_sac_soft_update failed ({rc}): {lib.pedn_last_error(None).decode()}")
+
+    # ------------------------------------------------------------------------------------------------ the critic step
+    def critic_workspace_shape(self, batch):
+        """(tiles, floats per tile) of the workspace of a batch size: per tile of ``CRITIC_TILE`` rows a partial gradient in the layout of
+        the pack and, behind it, the [n_agents][2] partial sums of squares, rounded up to 4 floats."""
+        if int(batch) < 1:
+            raise ValueError("the batch size must be positive")
+        return -(-int(batch) // CRITIC_TILE), self.pack_size + -(-2 * self.n_agents // 4) * 4
+
+    def _critic_device(self):
+        if self._cdev is None:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            z = lambda: torch.zeros(self.pack_size, dtype=torch.float32, device=dev)
+            self._cdev = {"grads": z(), "exp_avg": z(), "exp_avg_sq": z(), "losses": torch.zeros(self.n_agents, 2, dtype=torch.float32, device=dev),
+                          "adam": torch.tensor(ADAM_STATE_INIT, dtype=torch.int64, device=dev)}
+        return self._cdev
+
+    @staticmethod
+    def _adam_arguments(lr, betas, eps):
+        try:
+            lr, eps, (b1, b2) = float(lr), float(eps), (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise ValueError("lr and eps must be numbers and betas a pair of numbers") from None
+        if not (math.isfinite(lr) and lr >= 0.0):
+            raise ValueError(f"lr must be finite and not negative, got {lr}")
+        if not (math.isfinite(eps) and eps >= 0.0):
+            raise ValueError(f"eps must be finite and not negative, got {eps}")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must be in [0, 1), got {(b1, b2)}")
+        return lr, b1, b2, eps
+
+    def _critic_launch(self, states, actions, td_target, lr, betas, eps, do_adam):
+        import torch
+
+        lr, b1, b2, eps = self._adam_arguments(lr, betas, eps)
+        if not isinstance(td_target, torch.Tensor) or td_target.dim() != 2 or td_target.shape[0] < 1:
+            raise ValueError("td_target must be a torch tensor of shape [B, n_agents]")
+        B = int(td_target.shape[0])
+        packs.check_tensor("td_target", td_target, self.device, (B, self.n_agents))
+        packs.check_tensor("states", states, self.device, (B, self.stack_size, self.n_obs))
+        packs.check_tensor("actions", actions, self.device, (B, self.n_actions))
+        missing = [(self.agent_ids[i], w) for i in range(self.n_agents) for w in WHICH[:2] if (i, w) not in self._loaded]
+        if missing:
+            raise ValueError(f"no critics were loaded for {missing}: load_state_dict() or bind() first")
+        d, cd = self._device(), self._critic_device()
+        out = self._cout.get(B)
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = self._cout[B] = (torch.zeros(*self.critic_workspace_shape(B), dtype=torch.float32, device=dev),
+                                   torch.zeros(2, B, self.n_agents, dtype=torch.float32, device=dev))
+        self._clast = out
+        p = lambda t: C.c_void_p(t.data_ptr())
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        lib = _engine.lib()
+        with torch.cuda.device(self.device):
+            rc = lib.pedn_sac_critic_update(p(states), p(actions), p(td_target), p(self.actors._device()["table"]), p(d["ctable"]), p(d["online"]),
+                                            p(cd["grads"]), p(cd["exp_avg"]), p(cd["exp_avg_sq"]), p(out[0]), p(out[1]), p(cd["losses"]), p(cd["adam"]),
+                                            self.pack_size, B, self.stack_size, self.n_obs, self.n_actions, self.n_agents, HIDDEN, lr, b1, b2, eps,
+                                            1 if do_adam else 0, C.c_void_p(int(stream)) if stream else None)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"pedn_sac_critic_update failed ({rc}): {lib.pedn_last_error(None).decode()}")
+
+    def critic_update(self, states, actions, td_target, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        """The critic half of the reference's ``update`` for every agent: q1 and q2 of ``states`` [B, stack_size, n_obs] and ``actions``
+        [B, n_actions] (what the critics see: the stored actions, the delta when ``delta_actions`` is on), the two losses
+        mean((q - td_target)^2) against ``td_target`` [B, n_agents], their gradients and one Adam step (torch's defaults otherwise) of
+        every online critic, in place in the ``online`` pack.  float32 contiguous CUDA tensors.  Two launches on the current torch stream;
+        no allocation after the first call of a batch size, no synchronisation: capturable.  The step count lives on the device."""
+        self._critic_launch(states, actions, td_target, lr, betas, eps, True)
+
+    def critic_gradients(self, states, actions, td_target):
+        """The launches of ``critic_update`` with the Adam step switched off: writes the gradients, the losses and q
+        (``critic_outputs``); no parameter and no optimiser state changes."""
+        self._critic_launch(states, actions, td_target, 0.0, (0.0, 0.0), 0.0, False)
+
+    class _CriticOutputs:
+        def __init__(self, owner, q):
+            self.q1, self.q2, self.losses, self._owner = q[0], q[1], owner._cdev["losses"], owner
+
+        def grads(self, agent_id, which):
+            """{key: float32 CUDA tensor} in ``nn.Linear`` shapes, the keys of ``parameters()``: views of the gradient pack."""
+            o = self._owner
+            pack_name, c = o._which(which)
+            if pack_name != "online":
+                raise ValueError("only the online critics have gradients")
+            return packs.views(o._cdev["grads"], o.offsets[o._index(agent_id)][c])
+
+    @property
+    def critic_outputs(self):
+        """What the last ``critic_update`` / ``critic_gradients`` wrote, float32: ``q1``, ``q2`` [B, n_agents], ``losses`` [n_agents, 2]
+        and ``grads(agent_id, which)``."""
+        if self._clast is None:
+            raise ValueError("critic_update() has not run")
+        return self._CriticOutputs(self, self._clast[1])
+
+    def adam_state(self, agent_id, which):
+        """({key: exp_avg}, {key: exp_avg_sq}) of an online critic: views of the optimiser's two packs."""
+        i = self._index(agent_id)
+        pack_name, c = self._which(which)
+        if pack_name != "online":
+            raise ValueError("only the online critics have an optimiser")
+        cd = self._critic_device()
+        return packs.views(cd["exp_avg"], self.offsets[i][c]), packs.views(cd["exp_avg_sq"], self.offsets[i][c])
+
+    def adam_steps(self):
+        """How many Adam steps ``critic_update`` has made (the device counter; waits for the device)."""
+        return int(self._critic_device()["adam"][0].item())
+
+    def reset_adam(self):
+        """Zero exp_avg, exp_avg_sq and the step count."""
+        import torch
+
+        cd = self._critic_device()
+        cd["exp_avg"].zero_()
+        cd["exp_avg_sq"].zero_()
+        cd["adam"].copy_(torch.tensor(ADAM_STATE_INIT, dtype=torch.int64))
 
     def draws(self):
         """How many launches have drawn noise (the device counter; waits for the device)."""
