@@ -566,6 +566,32 @@ int pedn_sac_critic_update(const float* states, const float* actions, const floa
                            int32_t n_agents, int32_t hidden_size, double lr, double beta1, double beta2, double eps, int32_t do_adam,
                            void* stream);
 
+/* ---- SAC actor and temperature gradients and Adam steps of all agents (rl/agents/SAC.py:347-370, the actor half of SACAgent.update) -------
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 19 (tests/sac_actor_model.py restates it in numpy).
+ *   states       f32 [batch][stack_size][n_obs]; noise f32 [batch][n_actions] used as eps, or NULL: drawn (Philox stream 0x75, counter
+ *                draw_state[0], row = the batch row)
+ *   table, critic_table   as for pedn_sac_td_target
+ *   actor_params, grads, exp_avg, exp_avg_sq   f32 [pack_floats] each, pedn_actor_forward's SAC-kind pack and three of its layout, 16-byte
+ *                aligned; the padding between the actors is +0.0 and stays so.  online_params: the online critics' pack, read only
+ *   log_alpha    f32 [n_agents], stepped in place; target_entropy f32 [n_agents]; alpha_moments f32 [2][n_agents]: exp_avg, exp_avg_sq
+ *   workspace    f32 [ceil(batch / 32)][pack_floats rounded up to 4 + 2 * n_agents rounded up to 4], zeroed by the caller once
+ *   out_actions  f32 [9][batch][n_actions]: mu, std, eps, logp, new_actions, z (the pre-softplus value), t = tanh(mu + std * eps), d_mu and
+ *                d_z (the loss' gradients by mu and by z); out_agents f32 [3][batch][n_agents]: entropy, q1, q2
+ *   scalars      f32 [3][n_agents]: actor_loss = mean(-alpha * entropy - min(q1, q2)), alpha_loss, alpha_grad = alpha * mean(entropy -
+ *                target_entropy)
+ *   adam_state   int64 [4] as for pedn_sac_critic_update, the actor's and the temperature's own; draw_state int64 [2] (zeros)
+ * Two launches on `stream`: the tiles' partial gradients (tiles of 32 rows, rows ascending), then their sum (tiles ascending) into grads
+ * and scalars and, if do_adam is not 0, one torch.optim.Adam step of actor_params with actor_lr and of log_alpha with alpha_lr, in
+ * place, which advances adam_state.  With do_adam = 0 nothing but grads, scalars, the outputs, the workspace and (drawing) draw_state is
+ * written.  0 <= lr, eps < inf, 0 <= beta < 1; hidden_size must be 64.  No allocation, no synchronisation, constant arguments: safe under
+ * stream capture. */
+int pedn_sac_actor_update(const float* states, const float* noise, const int32_t* table, const int32_t* critic_table, float* actor_params,
+                          const float* online_params, float* log_alpha, const float* target_entropy, float* grads, float* exp_avg,
+                          float* exp_avg_sq, float* alpha_moments, float* workspace, float* out_actions, float* out_agents, float* scalars,
+                          int64_t* adam_state, int64_t* draw_state, int64_t pack_floats, int32_t batch, int32_t stack_size, int32_t n_obs,
+                          int32_t n_actions, int32_t n_agents, int32_t hidden_size, double max_delta, double actor_lr, double alpha_lr,
+                          double beta1, double beta2, double eps, uint64_t seed, int32_t do_adam, void* stream);
+
 /* ---- PPO's value critics and old log-probabilities of a whole rollout (rl/agents/PPO_org.py:175-197 StackedValueNetwork, :543-577) -------
  * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 16 (tests/ppo_eval_model.py restates it in numpy).
  *   obs          f32 [T + 1][N][n_obs]: every observation once (array 4 of pedn_rollout_device_ptr behind pedn_rollout_finish).  The state

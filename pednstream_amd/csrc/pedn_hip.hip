@@ -25,6 +25,7 @@
 #include "pedn_actor.hpp"
 #include "pedn_sac.hpp"
 #include "pedn_critic.hpp"
+#include "pedn_actor_grad.hpp"
 #include "pedn_ppo.hpp"
 #include "pedn_lstm.hpp"
 #include "pedn_metrics.hpp"

@@ -10,15 +10,20 @@ section 15, tests/sac_target_model.py restates it in numpy.
         sac.bind(aid, critic_1[aid], critic_2[aid], target_1[aid], target_2[aid], log_alpha=log_alpha[aid])
     s, a, r, ns, d, idx = buf.sample(256)
     td = sac.td_target(r, ns, d)                  # [256, n_agents], detached by construction
-    ...                                           # critic / actor / alpha losses and optimiser steps in torch, on the bound modules
+    sac.critic_update(s, a.float(), td)           # or the losses and optimiser steps in torch, on the bound modules
+    sac.actor_update(s)
     sac.soft_update()
 
 ``SacTargets`` is the constructor on a ``StackedActors`` (no env).
 
 The critic step of the gradient half runs on the device too (pednstream_amd/csrc/pedn_critic.hpp; the contract is DESIGN section 18,
 tests/sac_critic_model.py restates it in numpy): ``sac.critic_update(s, critic_actions, td)`` between ``td_target`` and ``soft_update`` computes
-q1, q2, both MSE losses, their gradients and one Adam step of every online critic in two launches.  The actor and alpha losses, their
-backward passes and optimisers stay in torch, on the bound modules.
+q1, q2, both MSE losses, their gradients and one Adam step of every online critic in two launches.
+
+So does the actor half (pednstream_amd/csrc/pedn_actor_grad.hpp; the contract is DESIGN section 19, tests/sac_actor_model.py restates it
+in numpy): ``sac.actor_update(s)`` behind ``critic_update`` computes the actor loss through both stepped online critics, its gradient, one
+Adam step of every actor in the ``StackedActors`` pack, and the temperature loss with one Adam step of every ``log_alpha``, in two
+launches.  sample -> td_target -> critic_update -> actor_update -> soft_update is a whole SAC update with no torch module in it.
 """
 import ctypes as C
 import math
@@ -32,6 +37,8 @@ from .policy import HIDDEN, StackedActors
 WHICH = ("critic_1", "critic_2", "target_critic_1", "target_critic_2")
 ACTION_OUTPUTS = ("mu", "std", "eps", "logp", "next_actions")
 AGENT_OUTPUTS = ("entropy", "q1", "q2", "td_target")
+ACTOR_ACTION_OUTPUTS = ("mu", "std", "eps", "logp", "new_actions", "z", "t", "d_mu", "d_z")      # z: the pre-softplus value; t = tanh(mu + std * eps); d_*: the loss' gradients
+ACTOR_AGENT_OUTPUTS = ("entropy", "q1", "q2")
 TILE = 8                        # rows per workgroup of sac_target_kernel (PEDN_SAC_TILE)
 CRITIC_TILE = 32                # rows per workgroup of critic_grad_kernel (PEDN_CRITIC_TILE): part of section 18's order of sums
 ADAM_STATE_INIT = (0, 0, 0x3FF0000000000000, 0x3FF0000000000000)      # the step count, the ticket, the doubles beta1^0 and beta2^0
@@ -99,6 +106,10 @@ class SacTargets:
         self._cdev = None               # the critic step's device tensors, allocated by its first use
         self._cout = {}                 # batch size -> (workspace [tiles, stride], q [2, B, n_agents])
         self._clast = None
+        self._adev = None               # the actor step's device tensors, allocated by its first use
+        self._aout = {}                 # batch size -> (workspace [tiles, stride], actions' outputs [5, B, n_actions], agents' outputs [3, B, n_agents])
+        self._alast = None
+        self._tent = None               # the target entropies on the device, as the host last set them
 
     # ------------------------------------------------------------------------------------------------ parameters
     def _index(self, agent_id):
@@ -351,6 +362,152 @@ class SacTargets:
     def draws(self):
         """How many launches have drawn noise (the device counter; waits for the device)."""
         return int(self._device()["state"][0].item())
+
+    # ------------------------------------------------------------------------------------------------ the actor and temperature step
+    def actor_workspace_shape(self, batch):
+        """(tiles, floats per tile) of the actor step's workspace of a batch size: per tile of ``CRITIC_TILE`` rows a partial gradient in
+        the layout of the actors' pack, rounded up to 4 floats, and behind it the [n_agents][2] partial sums of ``-alpha * entropy -
+        min_q`` and of ``entropy - target_entropy``, rounded up to 4 floats."""
+        if int(batch) < 1:
+            raise ValueError("the batch size must be positive")
+        return -(-int(batch) // CRITIC_TILE), -(-self.actors.pack_size // 4) * 4 + -(-2 * self.n_agents // 4) * 4
+
+    def _actor_device(self):
+        if self._adev is None:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+            n = max(1, self.actors.pack_size)
+            self._adev = {"grads": z(n), "exp_avg": z(n), "exp_avg_sq": z(n), "alpha_moments": z(2, self.n_agents), "scalars": z(3, self.n_agents),
+                          "target_entropy": z(self.n_agents), "adam": torch.tensor(ADAM_STATE_INIT, dtype=torch.int64, device=dev),
+                          "state": torch.zeros(2, dtype=torch.int64, device=dev)}
+            self._tent = None
+        return self._adev
+
+    def _target_entropy(self, target_entropy):
+        """float32 [n_agents] on the host: ``None`` is -act_w of each agent (what the reference's trainer passes), a number serves all."""
+        if target_entropy is None:
+            return np.array([-float(aw) for (_, _, _, aw) in self.agents], dtype=np.float32)
+        try:
+            te = np.asarray(target_entropy, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("target_entropy must be a number or one number per agent") from None
+        if te.ndim == 0:
+            te = np.full(self.n_agents, float(te))
+        if te.shape != (self.n_agents,):
+            raise ValueError(f"target_entropy must be a number or {self.n_agents} numbers, got shape {te.shape}")
+        if not np.isfinite(te).all():
+            raise ValueError(f"target_entropy must be finite, got {te.tolist()}")
+        return te.astype(np.float32)
+
+    def _actor_launch(self, states, noise, actor_lr, alpha_lr, target_entropy, betas, eps, do_adam):
+        import torch
+
+        actor_lr, b1, b2, eps = self._adam_arguments(actor_lr, betas, eps)
+        alpha_lr = self._adam_arguments(alpha_lr, betas, eps)[0]
+        te = self._target_entropy(target_entropy)
+        if not isinstance(states, torch.Tensor) or states.dim() != 3 or states.shape[0] < 1:
+            raise ValueError("states must be a torch tensor of shape [B, stack_size, n_obs]")
+        B = int(states.shape[0])
+        packs.check_tensor("states", states, self.device, (B, self.stack_size, self.n_obs))
+        if noise is not None:
+            packs.check_tensor("noise", noise, self.device, (B, self.n_actions))
+        missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self.actors._loaded]
+        if missing:
+            raise ValueError(f"no actor parameters were loaded for {missing}: StackedActors.load_state_dict() or bind() first")
+        missing = [(self.agent_ids[i], w) for i in range(self.n_agents) for w in WHICH[:2] if (i, w) not in self._loaded]
+        if missing:
+            raise ValueError(f"no critics were loaded for {missing}: load_state_dict() or bind() first")
+        d, ad, pd = self._device(), self._actor_device(), self.actors._device()
+        if self._tent is None or not np.array_equal(self._tent, te):      # (a copy outside any capture: the values are the caller's constants)
+            ad["target_entropy"].copy_(torch.as_tensor(te))
+            self._tent = te
+        out = self._aout.get(B)
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            out = self._aout[B] = (torch.zeros(*self.actor_workspace_shape(B), dtype=torch.float32, device=dev),
+                                   torch.zeros(len(ACTOR_ACTION_OUTPUTS), B, self.n_actions, dtype=torch.float32, device=dev),
+                                   torch.zeros(len(ACTOR_AGENT_OUTPUTS), B, self.n_agents, dtype=torch.float32, device=dev))
+        self._alast = out
+        p = lambda t: C.c_void_p(t.data_ptr())
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        lib = _engine.lib()
+        with torch.cuda.device(self.device):
+            rc = lib.pedn_sac_actor_update(p(states), p(noise) if noise is not None else None, p(pd["table"]), p(d["ctable"]), p(pd["pack"]),
+                                           p(d["online"]), p(d["log_alpha"]), p(ad["target_entropy"]), p(ad["grads"]), p(ad["exp_avg"]),
+                                           p(ad["exp_avg_sq"]), p(ad["alpha_moments"]), p(out[0]), p(out[1]), p(out[2]), p(ad["scalars"]),
+                                           p(ad["adam"]), p(ad["state"]), self.actors.pack_size, B, self.stack_size, self.n_obs, self.n_actions,
+                                           self.n_agents, HIDDEN, self.max_delta, actor_lr, alpha_lr, b1, b2, eps, self.seed,
+                                           1 if do_adam else 0, C.c_void_p(int(stream)) if stream else None)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"pedn_sac_actor_update failed ({rc}): {lib.pedn_last_error(None).decode()}")
+
+    def actor_update(self, states, noise=None, actor_lr=3e-4, alpha_lr=3e-4, target_entropy=None, betas=(0.9, 0.999), eps=1e-8):
+        """The actor half of the reference's ``update`` for every agent, behind ``critic_update``: the actor's forward on ``states``
+        [B, stack_size, n_obs], the squashed sample and its log-probability, both ONLINE critics on (states, new_actions), the loss
+        mean(-alpha * entropy - min(q1, q2)), its gradient through the critics' action inputs and the actor, one Adam step (torch's
+        defaults otherwise) of every actor in place in the ``StackedActors`` pack, and the temperature's loss mean((entropy -
+        target_entropy) * alpha) with one Adam step of every ``log_alpha`` element.  The critics are read, not written.  ``noise``
+        [B, n_actions] float32 replaces the draw; ``target_entropy``: a number, one per agent, or ``None`` for -act_w.  Two launches on
+        the current torch stream; no allocation after the first call of a batch size, no synchronisation: capturable (a new
+        ``target_entropy`` is copied to the device by the call that brings it, so pass the same one while capturing and replaying).  The
+        step count and the draw counter live on the device."""
+        self._actor_launch(states, noise, actor_lr, alpha_lr, target_entropy, betas, eps, True)
+
+    def actor_gradients(self, states, noise=None, target_entropy=None):
+        """The launches of ``actor_update`` with both Adam steps switched off: writes the gradients, the losses and the forward's
+        outputs (``actor_outputs``); no parameter and no optimiser state changes (a draw advances ``actor_draws()``)."""
+        self._actor_launch(states, noise, 0.0, 0.0, target_entropy, (0.0, 0.0), 0.0, False)
+
+    class _ActorOutputs:
+        def __init__(self, owner, out):
+            for i, k in enumerate(ACTOR_ACTION_OUTPUTS):
+                setattr(self, k, out[1][i])
+            for i, k in enumerate(ACTOR_AGENT_OUTPUTS):
+                setattr(self, k, out[2][i])
+            sc = owner._adev["scalars"]
+            self.actor_loss, self.alpha_loss, self.alpha_grad, self._owner = sc[0], sc[1], sc[2], owner
+
+        def grads(self, agent_id):
+            """{key: float32 CUDA tensor} in ``nn.Linear`` shapes, the keys of ``StackedActors.parameters()``: views of the gradient pack."""
+            o = self._owner
+            return packs.views(o._adev["grads"], o.actors.offsets[o._index(agent_id)])
+
+    @property
+    def actor_outputs(self):
+        """What the last ``actor_update`` / ``actor_gradients`` wrote, float32: ``mu``, ``std``, ``eps``, ``logp``, ``new_actions``
+        (and ``z``, ``t``, ``d_mu``, ``d_z``: the pre-softplus value, tanh(mu + std * eps) and the loss' gradients by mu and z) [B, n_actions]; ``entropy``, ``q1``, ``q2`` [B, n_agents]; ``actor_loss``, ``alpha_loss``, ``alpha_grad`` [n_agents]; and
+        ``grads(agent_id)``."""
+        if self._alast is None:
+            raise ValueError("actor_update() has not run")
+        return self._ActorOutputs(self, self._alast)
+
+    def actor_adam_state(self, agent_id):
+        """({key: exp_avg}, {key: exp_avg_sq}) of an actor: views of the optimiser's two packs, with the agent's ``log_alpha`` moments
+        (one element each) under the key ``"log_alpha"``."""
+        i = self._index(agent_id)
+        ad = self._actor_device()
+        m, v = packs.views(ad["exp_avg"], self.actors.offsets[i]), packs.views(ad["exp_avg_sq"], self.actors.offsets[i])
+        m["log_alpha"], v["log_alpha"] = ad["alpha_moments"][0, i:i + 1], ad["alpha_moments"][1, i:i + 1]
+        return m, v
+
+    def actor_adam_steps(self):
+        """How many Adam steps ``actor_update`` has made (the device counter; waits for the device)."""
+        return int(self._actor_device()["adam"][0].item())
+
+    def reset_actor_adam(self):
+        """Zero the actors' and the temperatures' exp_avg, exp_avg_sq and the step count."""
+        import torch
+
+        ad = self._actor_device()
+        for k in ("exp_avg", "exp_avg_sq", "alpha_moments"):
+            ad[k].zero_()
+        ad["adam"].copy_(torch.tensor(ADAM_STATE_INIT, dtype=torch.int64))
+
+    def actor_draws(self):
+        """How many ``actor_update`` / ``actor_gradients`` launches have drawn noise (the device counter; waits for the device)."""
+        return int(self._actor_device()["state"][0].item())
 
 
 def for_env(env, actors, gamma=0.99, tau=0.005, seed=0):
