@@ -613,6 +613,38 @@ int pedn_ppo_evaluate(const float* obs, const void* actions, const int32_t* tabl
                       int32_t stack_size, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size, int32_t actions_f64,
                       double min_std, double max_std, void* stream);
 
+/* ---- one epoch of PPO's clipped-loss update of all agents (rl/agents/PPO_org.py:579-629 and the KL early stop) ---------------------------
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 20 (tests/ppo_update_model.py restates it in numpy).
+ *   obs, actions, table, value_table, actor_params, value_params, min_std, max_std   as for pedn_ppo_evaluate; both packs are stepped in place
+ *   old_log_probs  f32 [T][N][n_actions]; advantages, td_target f32 [T][N][n_agents] (an agent's advantage serves its act_w columns)
+ *   *_grads, *_raw_grads, *_exp_avg, *_exp_avg_sq   f32, the layout of their network's pack: the clipped and the unclipped gradients and
+ *                Adam's moments; 16-byte aligned like the packs; the padding is +0.0 and stays so
+ *   workspace    f32 [min(ceil(T * N / 32), groups)][actor_pack_floats rounded up to 4 + value_pack_floats + 8 * n_agents]: a slab per group of
+ *                tiles, bounded by `groups` whatever T * N is; need not be zeroed
+ *   norm_parts   f64 [n_agents][2][16]; log_probs f32 [T][N][n_actions]; values f32 [T][N][n_agents]
+ *   tail_out     f32 [3][T][N][n_actions], or NULL: not written: std and the actor loss' gradients by mu and by the pre-softplus value
+ *   scalars      f32 [7][n_agents]: actor_loss, critic_loss, approx_kl = mean(log_probs - old_log_probs), the actor's and the value network's
+ *                total gradient norm, and their clip coefficients min(max_grad_norm / (norm + 1e-6), 1)
+ *   adam_state   int64 [n_agents][4], set by the caller once: per agent the step count (0), a ticket (0), the doubles beta1^t, beta2^t (1.0)
+ *   stop_flags   int32 [n_agents]: an agent whose flag is not 0 is skipped whole (nothing of it is read or written).  With do_adam the
+ *                flag is set behind the step of an epoch whose approx_kl > 1.5 * kl_tolerance; pedn_ppo_begin_update clears the flags
+ * Three launches on `stream`: the groups' partial gradients (tiles of 32 rows, rows ascending; group g takes tiles g, g + G, ..), their sum
+ * (g ascending) with the losses and the norms' parts, then clip_grad_norm_ and, if do_adam is not 0, one torch.optim.Adam step of each
+ * network (actor_lr, critic_lr).  With do_adam = 0 no parameter, moment, count or flag changes.  0 <= lr, eps < inf, 0 <= beta < 1, 0 <
+ * clip_eps, max_grad_norm < inf, kl_tolerance not NaN, 1 <= groups <= 65535; hidden_size must be 64.  No allocation, no synchronisation,
+ * constant arguments: safe under stream capture. */
+int pedn_ppo_epoch_update(const float* obs, const void* actions, const float* old_log_probs, const float* advantages, const float* td_target,
+                          const int32_t* table, const int32_t* value_table, float* actor_params, float* value_params, float* actor_grads,
+                          float* value_grads, float* actor_raw_grads, float* value_raw_grads, float* actor_exp_avg, float* value_exp_avg,
+                          float* actor_exp_avg_sq, float* value_exp_avg_sq, float* workspace, double* norm_parts, float* log_probs, float* values,
+                          float* tail_out, float* scalars, int64_t* adam_state, int32_t* stop_flags, int64_t actor_pack_floats, int64_t value_pack_floats,
+                          int32_t T, int32_t N, int32_t stack_size, int32_t n_obs, int32_t n_actions, int32_t n_agents, int32_t hidden_size,
+                          int32_t actions_f64, int32_t groups, double min_std, double max_std, double actor_lr, double critic_lr,
+                          double clip_eps, double max_grad_norm, double kl_tolerance, double beta1, double beta2, double eps, int32_t do_adam,
+                          void* stream);
+/* stop_flags[0 .. n_agents) = 0, one small launch on `stream`: capturable. */
+int pedn_ppo_begin_update(int32_t* stop_flags, int32_t n_agents, void* stream);
+
 /* ---- the reference's stateful LSTM PPO agents (rl/agents/PPO_org.py:20-138 LSTMPolicyNetwork / LSTMValueNetwork, :470-516, :543-577) ----
  * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 17 (tests/lstm_model.py restates it in numpy).  One
  * nn.LSTM layer of 64 units (hidden_size must be 64, num_layers 1), gate rows i, f, g, o; an agent's input is the single frame's columns

@@ -27,6 +27,7 @@
 #include "pedn_critic.hpp"
 #include "pedn_actor_grad.hpp"
 #include "pedn_ppo.hpp"
+#include "pedn_ppo_grad.hpp"
 #include "pedn_lstm.hpp"
 #include "pedn_metrics.hpp"
 

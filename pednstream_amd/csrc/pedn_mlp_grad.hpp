@@ -52,3 +52,33 @@ __device__ __forceinline__ void mlp_grad_store(const float* sG, float* gw, int K
     if (kk < kmax) gw[(unsigned)(o * K + c0 + kk)] = sG[o * PEDN_GRAD_PAD + kk];
   }
 }
+
+// LayerNorm(64) over the wave's lanes as pedn_mlp.hpp's mlp_layer_norm computes it, operation for operation, with what its backward needs
+// kept: xh[r] = (x - mean) / sd[r], sd[r] = sqrt(var + 1e-5); acc[r] = xh[r] * g + b.
+template <int R>
+__device__ __forceinline__ void mlp_layer_norm_keep(float (&acc)[R], float (&xh)[R], float (&sd)[R], float g, float b) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const float mean = mlp_tree_sum(acc[r]) / 64.0f;
+    const float c = acc[r] - mean;
+    const float var = mlp_tree_sum(c * c) / 64.0f;
+    sd[r] = sqrtf(var + 1e-5f);
+    xh[r] = c / sd[r];
+    acc[r] = xh[r] * g + b;
+  }
+}
+
+// LayerNorm's backward, a lane per neuron, the 64 lanes summed with the forward's balanced tree: from d[r] = dL / dy of this lane's
+// neuron, dxh = d * g, m1 = tree(dxh) / 64, m2 = tree(dxh * xh) / 64, dL / dx = ((dxh - m1) - xh * m2) / sd, every product, difference
+// and quotient one rounded float32 operation in that order.  (The weight's and the bias' gradients are sums over rows: dW[k] += d[r][k] *
+// xh[r][k], db[k] += d[r][k], rows ascending, which the caller forms like any bias gradient.)
+template <int R>
+__device__ __forceinline__ void mlp_layer_norm_grad(float (&d)[R], const float (&xh)[R], const float (&sd)[R], float g) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const float dxh = d[r] * g;
+    const float m1 = mlp_tree_sum(dxh) / 64.0f;
+    const float m2 = mlp_tree_sum(dxh * xh[r]) / 64.0f;
+    d[r] = ((dxh - m1) - xh[r] * m2) / sd[r];
+  }
+}
