@@ -1100,6 +1100,7 @@ static void prewarm_chains(pedn_sim* s) {
     hipLaunchKernelGGL(link_turn_kernel_for(sel, false, false), dim3(1), dim3(256), 0, st, vl, 1, 0u, 0u, 0u, q, 0);
     hipLaunchKernelGGL(link_kernel_1r_for(sel), dim3(1), dim3(256), 0, st, vl, 1);
     if (s->stream3) hipLaunchKernelGGL(dead_link_kernel, dim3(1), dim3(256), 0, st, v, 2, (const DeadRec*)s->d_dead_drec, 0);   // (no slot: its waves leave)
+    if (s->stream3) hipLaunchKernelGGL(lean_block_kernel, dim3(1), dim3(256), 0, st, v, 2, 1, 0u, 0u, (const DeadRec*)s->d_dead_drec, 0);
   }
   if (s->stream3) {   // the live bins' stream of the dead-link plan
     hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3(1, 1), dim3(512), s->plan.node_lds, s->stream3, v, 2);
@@ -1233,7 +1234,24 @@ static inline pedn_plan::StepRequest step_request(int t, bool lazy, int chain = 
 //     construction), a dead slot takes the inflow / cumulative_inflow that a live slot writes into it as +0.0 without reading them --
 //     the link is outside REACH (pedn_partition.hpp), so the node model can only produce +0.0 for it;
 //   * the error flags are OR-ed atomically by both; the live waves read them only to decide their quiet word, which selects between
-//     two paths that give the same bits.
+//     two paths that give the same bits;
+//   * a block of steps in one lean launch (launch_split_block) reads of its own stream's earlier output only rows that EARLIER launches
+//     wrote -- the running sum and receiving_flow[t0 - 2] of the launch before it on its stream (or of the full step in front of the
+//     fork), travel_time[t - 1 - W] of a launch before it because a block has at most W steps (pedn_plan::dead_block_len) -- so nothing
+//     here depends on which step either stream is in: neither list of obligations above names a step.
+static void launch_split_live(pedn_sim* s, const pedn_plan::SplitPlan& p, int t) {
+  if (!p.live) return;
+  DevView vn = s->v;
+  vn.slot_rec = s->d_live_rec;
+  vn.quiet = s->d_quiet_live;
+  vn.quiet_npos = s->live_npos;
+  vn.quiet_use = p.quiet_use;
+  vn.quiet_lean = p.quiet_lean ? 1 : 0;
+  vn.rl_actions = nullptr;
+  vn.zg64 = p.zg64; vn.zg32 = p.zg32;
+  row_bases(vn, t);
+  hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3((unsigned)(vn.RS / 64), (unsigned)s->n_live_blocks), dim3(512), s->node_lds_live, s->stream3, vn, t);
+}
 static void launch_split_step(pedn_sim* s, int t) {
   const pedn_plan::SplitPlan p = pedn_plan::plan_split_step(step_caps(s), s->marks, step_request(t, true, -1, s->plan.dead_streams));
   const size_t lds = dead_lds_bytes(s->plan.dead_waves);   // the lean kernel's share of the wave places
@@ -1245,20 +1263,41 @@ static void launch_split_step(pedn_sim* s, int t) {
     const unsigned waves = (unsigned)s->n_dead_pos * (unsigned)(vd.subRS / 64);
     if (waves > 0) hipLaunchKernelGGL(dead_link_kernel, dim3((waves + 3) / 4), dim3(256), lds, stream, vd, t, (const DeadRec*)s->d_dead_drec, s->n_dead_pos);
   }
-  if (p.live) {
-    DevView vn = s->v;
-    vn.slot_rec = s->d_live_rec;
-    vn.quiet = s->d_quiet_live;
-    vn.quiet_npos = s->live_npos;
-    vn.quiet_use = p.quiet_use;
-    vn.quiet_lean = p.quiet_lean ? 1 : 0;
-    vn.rl_actions = nullptr;
-    vn.zg64 = p.zg64; vn.zg32 = p.zg32;
-    row_bases(vn, t);
-    hipLaunchKernelGGL(node_kernel_for(s, true, false), dim3((unsigned)(vn.RS / 64), (unsigned)s->n_live_blocks), dim3(512), s->node_lds_live, s->stream3, vn, t);
-  }
+  launch_split_live(s, p, t);
   pedn_plan::commit_split_step(s->marks, p);
   mirror_marks(s);
+}
+
+// Steps t .. t + n - 1 of a split range (2 <= n <= min(dead_block, W, PEDN_DEAD_BLOCK_MAX)): ONE launch of lean_block_kernel for all of
+// them (dead_streams = 2: one per half) in front of the block's n live launches, which go out step by step exactly as launch_split_step
+// sends them.  The planner still plans and commits every STEP: the gates of the lean launch -- bit k: those of step t + k -- are the
+// plans' own, taken from a dry run of the same plan / commit pair on a copy of the marks, so that the lean launch can go out first.
+static void launch_split_block(pedn_sim* s, int t, int n) {
+  const pedn_plan::StepCaps caps = step_caps(s);
+  uint32_t zg64m = 0, zg32m = 0;
+  int lean_launches = 1;
+  pedn_plan::StepState dry = s->marks;
+  for (int k = 0; k < n; ++k) {
+    const pedn_plan::SplitPlan p = pedn_plan::plan_split_step(caps, dry, step_request(t + k, true, -1, s->plan.dead_streams));
+    zg64m |= (uint32_t)(p.zg64 != 0) << k;
+    zg32m |= (uint32_t)(p.zg32 != 0) << k;
+    lean_launches = p.lean_launches;
+    pedn_plan::commit_split_step(dry, p);
+  }
+  const size_t lds = dead_lds_bytes(s->plan.dead_block_waves);   // the block kernel's own share of the wave places
+  for (int c = 0; c < lean_launches; ++c) {
+    hipStream_t stream;
+    DevView vd = view_of(s, lean_launches == 1 ? -1 : c, &stream);
+    row_bases(vd, t);
+    const unsigned waves = (unsigned)s->n_dead_pos * (unsigned)(vd.subRS / 64);
+    if (waves > 0) hipLaunchKernelGGL(lean_block_kernel, dim3((waves + 3) / 4), dim3(256), lds, stream, vd, t, n, zg64m, zg32m, (const DeadRec*)s->d_dead_drec, s->n_dead_pos);
+  }
+  for (int k = 0; k < n; ++k) {
+    const pedn_plan::SplitPlan p = pedn_plan::plan_split_step(step_caps(s), s->marks, step_request(t + k, true, -1, s->plan.dead_streams));
+    launch_split_live(s, p, t + k);
+    pedn_plan::commit_split_step(s->marks, p);
+    mirror_marks(s);
+  }
 }
 
 // One chain's launches of a step, as the planner names them (pedn_plan::plan_step: the flush of a pending link update, the stand-alone
@@ -1426,9 +1465,16 @@ int pedn_run(pedn_sim* s, int32_t t0, int32_t t1) {
     if (split && (rc = launch_step(s, step_request(t++, lazy))) != PEDN_OK) return rc;
     const int idle = split && s->plan.dead_streams == 1 ? 1 : -1;
     if ((rc = fork_chains(s, split ? 3 : nch, idle)) != PEDN_OK) return rc;
-    for (; t < t1; ++t) {
-      if (split) launch_split_step(s, t);
-      else for (int c = 0; c < nch; ++c) launch_step(s, step_request(t, lazy, c, nch));
+    while (t < t1) {
+      if (split) {   // the steps that are left, in blocks of the lean stream (a block of one step: dead_link_kernel, as without blocks)
+        const int n = pedn_plan::dead_block_len(t, t1, s->plan.dead_block, s->v.W);
+        if (n > 1) launch_split_block(s, t, n);
+        else launch_split_step(s, t);
+        t += n;
+      } else {
+        for (int c = 0; c < nch; ++c) launch_step(s, step_request(t, lazy, c, nch));
+        ++t;
+      }
     }
     rc = join_chains(s, split ? 3 : nch, idle);    // the last step's link update stays pending on the joined stream (pending_links_first)
     if (rc != PEDN_OK) return rc;

@@ -1368,6 +1368,120 @@ __global__ __launch_bounds__(256, 8) void dead_link_kernel(DevView v, int t, con
 #undef DROW
 }
 
+// dead_link_kernel for a BLOCK of steps t0 .. t0 + n - 1 in one launch (launch_split_block in pedn_hip.hip; n <= PEDN_DEAD_BLOCK_MAX and
+// n <= W: pedn_plan::dead_block_len).  The same wave mapping, the same record, the same device functions and the same statements per step
+// in the same order; what a lane handed to itself through memory from one launch to the next stays in registers: the running sum and the
+// receiving flow of the step before (r_i of step t is receiving_flow[t - 1] = the r_prev of step t + 1).  Per block and wave: one kernel
+// boundary, one record burst, one load of rsum and of receiving_flow[t0 - 2], one store of rsum, one atomicOr of the flags of all steps.
+// The n loads of travel_time[t - 1 - W] are issued together in front of the loop: n <= W makes every one of them a row that an EARLIER
+// launch wrote, so the wave never reads back what it stored itself.
+// Rows: full-record mode only, so the row of step t0 + k is the row of t0 (DevView.rb, row_bases(t0)) plus k whole rows of the field;
+// travel_time[t - 1 - W] is RB_TT_P moved by k - W rows (RB_TT_W is a placeholder while the window has not filled).  zg64m / zg32m: the
+// zero-elision gates of step t0 + k in bit k.  The loop over the steps stays a loop (unrolled sixteen times it is 38 KB of code next to a
+// live kernel that shares the instruction cache); the preloaded values are a register array that the wave-uniform k indexes.
+#define PEDN_DEAD_BLOCK_MAX 16
+__global__ __launch_bounds__(256, 8) void lean_block_kernel(DevView v, int t0, int n, uint32_t zg64m, uint32_t zg32m, const DeadRec* __restrict__ rec,
+                                                            int n_rec) {
+  const unsigned rgroups = (unsigned)(v.subRS >> 6);
+  const unsigned w = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned idx = w / rgroups;
+  if (idx >= (unsigned)n_rec) return;   // wave-uniform
+  const DeadRec D = rec[idx];           // the whole record, in front of the branch: one burst
+  const int lane = (int)(threadIdx.x & 63);
+  const int RS = v.RS, L = v.L;
+  const int r0 = v.sub0 + (int)(w % rgroups) * 64, r = r0 + lane;
+  const int lin = D.lin, lout = D.lout;
+  const uint32_t oin = (uint32_t)lin * (uint32_t)RS + (uint32_t)r0, oout = (uint32_t)lout * (uint32_t)RS + (uint32_t)r0;
+  // This wave's columns in the rows of step t0: lane K of `col` holds the pointer of field RB_K (v.rb[K] + the incoming or the outgoing
+  // link's column), and every lane moves its own on by one row of its field per step.  A store reads its field's lane back into two
+  // scalars (BCOL).  Thirteen pointers in two vector registers instead of 26 scalar ones that live through the loop: with them, the
+  // record and the launch constants the loop has more scalars than a wave of 8 per SIMD gets, and the rest would be spilled into lanes
+  // one by one.  (Elements of a row: inflow .. cumulative_outflow hold the virtual links too, row_bases.)
+  constexpr uint32_t OUT_FIELDS = 1u << RB_GATE_P | 1u << RB_R_P | 1u << RB_R_Q | 1u << RB_CI_T | 1u << RB_IN_T | 1u << RB_CI_P | 1u << RB_IN_P;
+  constexpr uint32_t ALL_LINK_FIELDS = 0xffu;   // RB_IN_P .. RB_CO_T
+  constexpr uint32_t F32_FIELDS = ~0u << RB_N_Q;   // RB_N_Q .. RB_TT_W
+  static_assert(RB_CO_T == 7 && RB_N_Q == 13 && RB_COUNT <= 32, "the field masks of lean_block_kernel follow the RB_* order");
+  const size_t row = (size_t)L * (size_t)RS, row_a = (size_t)v.Lall * (size_t)RS;
+  const uint32_t kf = (uint32_t)lane < (uint32_t)RB_COUNT ? (uint32_t)lane : 0u;
+  const uint32_t esz = (F32_FIELDS >> kf) & 1u ? 4u : 8u;
+  const uint64_t col_step = (uint64_t)((ALL_LINK_FIELDS >> kf) & 1u ? row_a : row) * esz;
+  uint64_t col = (uint64_t)((OUT_FIELDS >> kf) & 1u ? oout : oin) * esz;
+  {
+    uintptr_t base = 0;
+#pragma unroll
+    for (int K = 0; K < RB_COUNT; ++K) base = lane == K ? (uintptr_t)v.rb[K] : base;
+    col += base;
+  }
+  // (the builtin takes and returns int: each half goes through uint32_t, or the low word's top bit would be extended over the high one)
+#define BLANE(X, K) (uintptr_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(X), K)
+#define BCOL(T, K) reinterpret_cast<T*>(BLANE(col >> 32, K) << 32 | BLANE(col, K))
+  const bool phys = lin < L;
+  // (the record fields that only per-lane arithmetic and stores read: kept in vector registers, which the kernel has to spare)
+  double d_send = D.send, d_rr0 = D.rr0, d_rr1 = D.rr1, d_gate = D.gate, d_length = D.length;
+  asm volatile("" : "+v"(d_send), "+v"(d_rr0), "+v"(d_rr1), "+v"(d_gate), "+v"(d_length));
+  uint32_t fl = 0;
+  float rs = 0.0f;
+  double r_prev = 0.0;
+  float old[PEDN_DEAD_BLOCK_MAX];
+  if (phys) {
+    const float* p_tt = BCOL(float, RB_TT_P);
+    rs = v.rsum[(size_t)lin * RS + r];
+    r_prev = stream_ld(&BCOL(double, RB_R_Q)[lane]);
+#pragma unroll
+    for (int k = 0; k < PEDN_DEAD_BLOCK_MAX; ++k)   // travel_time[t' - W] of step t' = t0 - 1 + k: W rows in front of the row that step writes
+      old[k] = k < n && t0 - 1 + k >= v.W ? stream_ld(&(p_tt + (ptrdiff_t)(k - v.W) * (ptrdiff_t)row)[lane]) : 0.0f;
+  }
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) {
+    const int tp = t0 + k - 1;
+    const bool zg64 = ((zg64m >> k) & 1u) != 0, zg32 = ((zg32m >> k) & 1u) != 0;
+    if (phys) {
+      const bool lu_win = tp >= v.W;
+      // Network.update_link_states(t') for the incoming link, as in node_step<LU>
+      const double nz = speed_noise_of(v, D.noise, lin, tp, r);
+      const float na = 0.0f, ka = D.ka;   // (float)(num_pedestrians[t' - 1] + (inflow[t'] - outflow[t'])) of +0.0 each, and na / area
+      if (!(zg32 && (__float_as_int(na) | __float_as_int(ka)) == 0)) {   // (the same in all 64 lanes: no vote)
+        stream_st(&BCOL(float, RB_N_P)[lane], na);
+        stream_st(&BCOL(float, RB_K_P)[lane], ka);
+      }
+      const SpeedOut so = speed_finish(v, SpeedBase{(D.bits & DEAD_IS64) != 0, D.v64, D.v32}, d_length, D.noise, D.tt0, tp, ka, rs, old[k], nz);
+      stream_st(&BCOL(float, RB_V_P)[lane], so.spd);
+      stream_st(&BCOL(float, RB_TT_P)[lane], so.tt);
+      if (!(zg32 && __all(__float_as_int(so.lf) == 0))) stream_st(&BCOL(float, RB_LF_P)[lane], so.lf);
+      if (lu_win) stream_st(&BCOL(float, RB_ATT_P)[lane], so.att);
+      rs = so.rs;   // the next step's running sum
+      if ((D.bits & DEAD_GATE_REC) != 0) stream_st(&BCOL(double, RB_GATE_P)[lane], d_gate);   // (full-record mode: the gate-record rule alone)
+      double s_i = 0.0;
+      if (tp >= D.fft) {
+        const int tau = __float2int_rn(so.att / (float)v.dt);  // link.py:260: send_flow's look-back, here for its flag alone
+        if (tau <= 0) fl |= PEDN_F_SAME_STEP;
+        s_i = d_send;
+        fl |= D.fl_send;
+      }
+      stream_st(&BCOL(double, RB_S_P)[lane], s_i);
+      const bool before_sw = tp + 1 - D.tau_sw < 0;
+      fl |= before_sw ? D.fl_rr0 : D.fl_rr1;
+      const double r_i = recv_minus_reverse(recv_smooth(before_sw ? d_rr0 : d_rr1, r_prev), s_i);
+      stream_st(&BCOL(double, RB_R_P)[lane], r_i);
+      r_prev = r_i;   // receiving_flow[t']: what the next step smooths against
+    }
+    // Node.update_links with qo = qi = +0.0 on cumulative counts of +0.0 (a virtual pair of such a node: its demand row is +0.0 too)
+    if (!zg64) {
+      stream_st(&BCOL(double, RB_CO_T)[lane], 0.0);
+      stream_st(&BCOL(double, RB_OUT_T)[lane], 0.0);
+      stream_st(&BCOL(double, RB_CI_T)[lane], 0.0);
+      stream_st(&BCOL(double, RB_IN_T)[lane], 0.0);
+    }
+    col += col_step;   // every field's next row
+  }
+  if (phys) {
+    v.rsum[(size_t)lin * RS + r] = rs;
+    if (fl) atomicOr(&v.flags[r], fl);
+  }
+#undef BCOL
+#undef BLANE
+}
+
 // The records of dead_link_kernel, one lane per slot: the slot's step on the inputs the proof fixes, as far as it is the same in every
 // lane -- the calls dead_link_kernel made for every lane and step before it had a record, with +0.0 where the proof puts it.  Launched by
 // dl_refresh behind the upload of the slots' SlotRec copies, never inside a step.  v: the engine's own view (shared gates, dt, W).

@@ -162,6 +162,15 @@ static inline SplitPlan plan_split_step(const StepCaps& c, const StepState& st, 
   return p;
 }
 
+// The block cutter of a split range (launch_split_block): how many of the steps [t, t1) that are left the lean stream takes in its next
+// launch.  K: EnginePlan.dead_block; W: the window of the running average (DevView.W).  Never more than W: step t' of a block reads
+// travel_time[t' - 1 - W], and with at most W steps per block the highest such row, (t + n - 1) - 1 - W, lies below the lowest row the
+// block writes, t - 1 -- every row a block reads W back was written by an EARLIER launch.  At least one step (W < 1: single steps, which
+// dead_link_kernel performs).
+constexpr int DEAD_BLOCK_MAX = 16;   // = PEDN_DEAD_BLOCK_MAX of lean_block_kernel: one bit per step in two 32-bit gate masks, one register per step
+constexpr int DEAD_BLOCK_DEFAULT = 4, DEAD_BLOCK_WAVES_DEFAULT = 2;   // (profiles/dead_block_settings.txt)
+static inline int dead_block_len(int t, int t1, int K, int W) { return std::max(1, std::min(std::min(K, W), std::min(DEAD_BLOCK_MAX, t1 - t))); }
+
 // ---- commits
 // what every committed step leaves behind: node launches of t on every replica [lu: they performed the link update of t - 1], the link
 // update of t pending or not, quiet words of t in packing `pack` or none
@@ -275,6 +284,8 @@ struct Knobs {
   int dead_links = -1;     // PEDN_DEAD_LINKS=0|1
   int dead_waves = -1;     // PEDN_DEAD_WAVES, clamped to 3..8
   int dead_streams = -1;   // PEDN_DEAD_STREAMS=1|2 (anything but 1 is 2)
+  int dead_block = -1;     // PEDN_DEAD_BLOCK, clamped to 1..DEAD_BLOCK_MAX
+  int dead_block_waves = -1;   // PEDN_DEAD_BLOCK_WAVES, clamped to 2..8
   int stream_probe = -1;   // PEDN_STREAM_PROBE=0|1
 };
 
@@ -290,6 +301,8 @@ static inline Knobs knobs_from_env() {
   if (const char* f = getenv("PEDN_RL_CHAINS")) k.rl_chains = atoi(f) == 2 ? 2 : 1;
   if (const char* f = getenv("PEDN_DEAD_WAVES")) k.dead_waves = std::max(3, std::min(atoi(f), 8));
   if (const char* f = getenv("PEDN_DEAD_STREAMS")) k.dead_streams = atoi(f) == 1 ? 1 : 2;
+  if (const char* f = getenv("PEDN_DEAD_BLOCK")) k.dead_block = std::max(1, std::min(atoi(f), DEAD_BLOCK_MAX));
+  if (const char* f = getenv("PEDN_DEAD_BLOCK_WAVES")) k.dead_block_waves = std::max(2, std::min(atoi(f), 8));
   return k;
 }
 
@@ -342,6 +355,11 @@ struct EnginePlan {
   // it does not use (dead_lds_bytes in pedn_hip.hip: the size leaves the rest of the CU's LDS to the live workgroups).
   int dead_waves = 5;
   int dead_streams = 1;    // 1 | 2: one lean launch per step for the whole batch, or one per half on the chain streams
+  // Blocks of steps (lean_block_kernel, launch_split_block in pedn_hip.hip): the lean stream steps up to dead_block steps of a split range
+  // per launch, the running sum and the previous receiving flow in registers (1: dead_link_kernel, one launch per step; at run time never
+  // more than W steps: dead_block_len).  dead_block_waves: the block kernel's OWN share of the wave places, as dead_waves (2..8).
+  int dead_block = DEAD_BLOCK_DEFAULT;
+  int dead_block_waves = DEAD_BLOCK_WAVES_DEFAULT;
   bool dead_capable = false;   // the dead-link plan can be taken at all: its buffers are allocated (pedn_sim::d_live_rec and what goes with it)
   // 32-bit words of [2][slot positions][RS / 64][own | inbox] for the full packing (0: no quiet words; melbourne x 1024 ~ 0.3 MB) and
   // for the live packing at its capacity (0: not dead_capable)
@@ -410,6 +428,14 @@ static inline EnginePlan choose(const PlanInputs& in, const Knobs& k) {
   if (k.dead_links >= 0) p.dead_links = k.dead_links != 0;
   if (k.dead_waves >= 0) p.dead_waves = k.dead_waves;
   if (k.dead_streams >= 0) p.dead_streams = k.dead_streams;
+  // Blocks of steps for the lean stream.  Up to 1024 replicas the live launches are the step and the lean stream has time to spare: short
+  // blocks at the smallest share of the wave places (melbourne x 1024: 15.8-16.0 -> 14.8-15.0 us per step in the driver's window, 16.0-16.4
+  // -> 15.6-15.8 in the default one; share 5: no gain).  Above, the lean stream is the longer one and a share of 2 starves it (x 4096: 41.4-
+  // 42.6 -> 45.3-46.2): the share of dead_waves and longer blocks (x 4096 31.9-32.6, x 2048 21.7-22.4 -> 20.9-21.3).
+  // profiles/dead_block_settings.txt
+  const bool lean_bound = in.RS > 1024;
+  p.dead_block = k.dead_block >= 0 ? k.dead_block : lean_bound ? 8 : DEAD_BLOCK_DEFAULT;
+  p.dead_block_waves = k.dead_block_waves >= 0 ? k.dead_block_waves : lean_bound ? 5 : DEAD_BLOCK_WAVES_DEFAULT;
   if (k.stream_probe >= 0) p.stream_probe = k.stream_probe != 0;
   const size_t groups = (size_t)(in.RS / 64);
   if (p.quiet) p.quiet_words = (size_t)2 * (size_t)in.n_rec * groups * 2;
