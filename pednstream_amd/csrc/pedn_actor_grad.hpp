@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pedn_critic.hpp"
+#include "pedn_adam.hpp"
 #include "pedn_mlp.hpp"
 #include "pedn_mlp_grad.hpp"
 
@@ -57,95 +57,23 @@ __device__ __forceinline__ ActorGradLate ag_late_args() {
   return p;
 }
 
-// One forward layer of a group of 4 waves (thread t of 256) for the tile, pedn_mlp.hpp's mlp_layer with a group's own staging rows: acc[r] =
-// b[o]; then mlp_mac over chunks of 32 inputs, lane o < rows.  Rows [0, n0) of the layer come from w0 / b0, the others from w1 / b1.  A
-// group that is not active takes the barriers only.  first: gather(c0, kmax) fills sXc for every group.
-template <class Gather>
-__device__ __forceinline__ void ag_layer(float (&acc)[PEDN_CRITIC_ROWS], bool active, const float* w0, const float* b0, const float* w1,
-                                         const float* b1, int n0, int rows, int K, bool first, float* sW, const float* sXc, const float* xin,
-                                         int xs, int t, Gather gather) {
-  const int lane = t & 63, w4 = t >> 6;
-  const float bias = active && lane < rows ? (lane < n0 ? b0[lane] : b1[lane - n0]) : 0.0f;
-#pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) acc[r] = bias;
-  for (int c0 = 0; c0 < K; c0 += PEDN_ACTOR_CHUNK) {
-    const int kmax = K - c0 < PEDN_ACTOR_CHUNK ? K - c0 : PEDN_ACTOR_CHUNK;
-    __syncthreads();   // the chunk before has been consumed (and what the caller wrote to LDS for this layer is there)
-    if (active)
-      for (int idx = t; idx < rows * PEDN_ACTOR_CHUNK; idx += 256) {
-        const int o = idx / PEDN_ACTOR_CHUNK, kk = idx % PEDN_ACTOR_CHUNK;
-        if (kk < kmax) sW[o * PEDN_GRAD_PAD + kk] = (o < n0 ? w0 + (unsigned)(o * K) : w1 + (unsigned)((o - n0) * K))[c0 + kk];
-      }
-    if (first) gather(c0, kmax);
-    __syncthreads();
-    if (active && lane < rows)
-      mlp_mac(acc, sW + lane * PEDN_GRAD_PAD, first ? sXc + w4 * PEDN_CRITIC_ROWS * PEDN_ACTOR_CHUNK : xin + c0, first ? PEDN_ACTOR_CHUNK : xs, kmax);
-  }
-}
-
-// The gradients of one actor layer's weight [64][K] and bias from the tile's output gradient d (rows of PEDN_CRITIC_DS) and its input x
-// (rows of xs words; first: the gathered chunk sXc), into gw and gb: wave w < 8 of the workgroup takes columns 4 * w .. + 3 of every
-// chunk, wave 8 the bias.  sG: staging rows.
-template <class Gather>
-__device__ __forceinline__ void ag_dw(const float* d, const float* x, int xs, int K, int nrows, float* gw, float* gb, float* sG, const float* sXc,
-                                      bool first, int tid, Gather gather) {
-  const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  __syncthreads();   // d is there
-  if (w == 8) {
-    float b = 0.0f;
-    for (int r = 0; r < nrows; ++r) b = b + d[r * PEDN_CRITIC_DS + lane];
-    gb[lane] = b;
-  }
-  for (int c0 = 0; c0 < K; c0 += PEDN_ACTOR_CHUNK) {
-    const int kmax = K - c0 < PEDN_ACTOR_CHUNK ? K - c0 : PEDN_ACTOR_CHUNK;
-    if (first) {
-      gather(c0, kmax);
-      __syncthreads();
-    }
-    if (w < 8) {
-      float g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      mlp_grad_dw(g, d + lane, PEDN_CRITIC_DS, (first ? sXc : x + c0) + 4 * w, first ? PEDN_ACTOR_CHUNK : xs, nrows);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sG[lane * PEDN_GRAD_PAD + 4 * w + j] = g[j];
-    }
-    __syncthreads();
-    mlp_grad_store(sG, gw, K, c0, kmax, tid, PEDN_AG_THREADS);
-    __syncthreads();   // sG and the gathered chunk are free
-  }
-}
-
-// acc[r] = sum over o ascending of d[r][o] * w[o][k] for lane k < 64 and rows 4 * wave .. + 3 of waves 0-7, from +0.0.  sT: staging rows.
-__device__ __forceinline__ void ag_dx(float (&acc)[4], const float* d, const float* w, int K, float* sT, int tid) {
-  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = 0.0f;
-  int n = PEDN_ACTOR_CHUNK;
-  asm volatile("" : "+s"(n));   // (no instruction: the count stays a run-time value, see mlp_grad_dx)
-  for (int o0 = 0; o0 < PEDN_ACTOR_HIDDEN; o0 += PEDN_ACTOR_CHUNK) {
-    __syncthreads();   // the staging rows are free
-    mlp_grad_stage_wt(sT, w, K, o0, tid, PEDN_AG_THREADS);
-    __syncthreads();
-    if (wv < 8) mlp_grad_dx(acc, sT + lane * PEDN_GRAD_PAD, d + 4 * wv * PEDN_CRITIC_DS + o0, PEDN_CRITIC_DS, n);
-  }
-}
-
 __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGradArgs a) {
   __shared__ float sW[3][PEDN_ACTOR_HIDDEN * PEDN_GRAD_PAD];
-  __shared__ __attribute__((aligned(16))) float sXc[PEDN_CRITIC_TILE * PEDN_ACTOR_CHUNK];
-  __shared__ __attribute__((aligned(16))) float sA[3][PEDN_CRITIC_TILE * PEDN_ACTOR_HIDDEN];   // h1 of the three networks
-  __shared__ __attribute__((aligned(16))) float sB[PEDN_CRITIC_TILE * PEDN_ACTOR_HIDDEN];      // the actor's h2
-  __shared__ __attribute__((aligned(16))) float sC[PEDN_CRITIC_TILE * PEDN_ACTOR_HIDDEN];      // the actor's h3 behind its ReLU
-  __shared__ __attribute__((aligned(16))) float sF[2][PEDN_CRITIC_TILE * PEDN_CRITIC_FEAT];    // the critics' fc input rows
-  __shared__ __attribute__((aligned(16))) float sD[3][PEDN_CRITIC_TILE * PEDN_CRITIC_DS];      // 0, 1: the critics' fc output; 2: the heads' gradient
-  __shared__ float sOut[PEDN_CRITIC_TILE * 2 * PEDN_ACTOR_MAX_ACT];                            // mu | pre-softplus of the heads
-  __shared__ float sAct[PEDN_CRITIC_TILE * PEDN_ACTOR_MAX_ACT];                                // new_action
-  __shared__ float sLogp[PEDN_CRITIC_TILE * PEDN_ACTOR_MAX_ACT];
-  __shared__ float sTail[3][PEDN_CRITIC_TILE * PEDN_ACTOR_MAX_ACT];                         // std, eps and t = tanh(u), for the backward's tail
-  __shared__ float sEnt[PEDN_CRITIC_TILE];
-  __shared__ float sQ[2][PEDN_CRITIC_TILE];
+  __shared__ __attribute__((aligned(16))) float sXc[PEDN_GRAD_TILE * PEDN_ACTOR_CHUNK];
+  __shared__ __attribute__((aligned(16))) float sA[3][PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];   // h1 of the three networks
+  __shared__ __attribute__((aligned(16))) float sB[PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];      // the actor's h2
+  __shared__ __attribute__((aligned(16))) float sC[PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];      // the actor's h3 behind its ReLU
+  __shared__ __attribute__((aligned(16))) float sF[2][PEDN_GRAD_TILE * PEDN_GRAD_FEAT];    // the critics' fc input rows
+  __shared__ __attribute__((aligned(16))) float sD[3][PEDN_GRAD_TILE * PEDN_GRAD_DS];      // 0, 1: the critics' fc output; 2: the heads' gradient
+  __shared__ float sOut[PEDN_GRAD_TILE * 2 * PEDN_ACTOR_MAX_ACT];                            // mu | pre-softplus of the heads
+  __shared__ float sAct[PEDN_GRAD_TILE * PEDN_ACTOR_MAX_ACT];                                // new_action
+  __shared__ float sLogp[PEDN_GRAD_TILE * PEDN_ACTOR_MAX_ACT];
+  __shared__ float sTail[3][PEDN_GRAD_TILE * PEDN_ACTOR_MAX_ACT];                         // std, eps and t = tanh(u), for the backward's tail
+  __shared__ float sEnt[PEDN_GRAD_TILE];
+  __shared__ float sQ[2][PEDN_GRAD_TILE];
   __shared__ float sWo[2][PEDN_ACTOR_HIDDEN];      // the critics' fc_out weights
   __shared__ double sV[2][PEDN_ACTOR_MAX_ACT];     // d q / d action of each critic
-  __shared__ float sL[2][PEDN_CRITIC_TILE];        // a row's -alpha * entropy - min_q, and its entropy - target_entropy
+  __shared__ float sL[2][PEDN_GRAD_TILE];        // a row's -alpha * entropy - min_q, and its entropy - target_entropy
   const int tid = (int)threadIdx.x, t = tid & 255, lane = tid & 63;
   const int g = __builtin_amdgcn_readfirstlane(tid >> 8), w4 = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
   const int H = PEDN_ACTOR_HIDDEN;
@@ -153,8 +81,8 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
   const int32_t* tb = a.table + (size_t)agent * PEDN_ACTOR_TABLE_COLS;
   const int obs0 = tb[0], obs_w = tb[1], act0 = tb[2], act_w = tb[3];
   const int K1 = a.S * obs_w, K3 = H + act_w + 1;
-  const int row0 = (int)blockIdx.x * PEDN_CRITIC_TILE;
-  const int nrows = a.B - row0 < PEDN_CRITIC_TILE ? a.B - row0 : PEDN_CRITIC_TILE;
+  const int row0 = (int)blockIdx.x * PEDN_GRAD_TILE;
+  const int nrows = a.B - row0 < PEDN_GRAD_TILE ? a.B - row0 : PEDN_GRAD_TILE;
   const bool is_actor = g == 2;
   const float* anet = a.actor + tb[4];
   const float* net = is_actor ? anet : a.online + a.ctable[2 * agent + g];
@@ -163,53 +91,43 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
   const int ah = at3 + H * H + H;                                    // the actor's heads, for every thread
   float* mW = sW[g];
   float* mA = sA[g];
-  const int myrow = w4 * PEDN_CRITIC_ROWS;
+  const int myrow = w4 * PEDN_GRAD_WAVE_ROWS;
   // the wave's first row once more, as a vector value, for the stores of its rows: from the scalar the compiler forms every row's LDS
   // address in SGPRs and holds them through the forward, which spilled
-  const int vrow = ((tid >> 6) & 3) * PEDN_CRITIC_ROWS;
+  const int vrow = ((tid >> 6) & 3) * PEDN_GRAD_WAVE_ROWS;
   const bool given = a.noise != nullptr;
-  float acc[PEDN_CRITIC_ROWS];
+  float acc[PEDN_GRAD_WAVE_ROWS];
 
-  // inputs [c0, c0 + kmax) of the tile's rows for all three networks: input f * S + s is s[row][s][obs0 + f]; zeros elsewhere
-  auto gather = [&](int c0, int kmax) {
-    for (int idx = tid; idx < PEDN_CRITIC_TILE * PEDN_ACTOR_CHUNK; idx += PEDN_AG_THREADS) {
-      const int r = idx / PEDN_ACTOR_CHUNK, kk = idx % PEDN_ACTOR_CHUNK;
-      float v = 0.0f;
-      if (kk < kmax && r < nrows) {
-        const unsigned k = (unsigned)(c0 + kk), f = k / (unsigned)a.S, s = k - f * (unsigned)a.S;
-        v = a.s[((size_t)(row0 + r) * a.S + s) * a.n_obs + obs0 + f];
-      }
-      sXc[idx] = v;
-    }
-  };
+  // inputs [c0, c0 + kmax) of the tile's rows for all three networks
+  auto gather = [&](int c0, int kmax) { sac_gather_chunk(sXc, a.s, a.S, a.n_obs, obs0, row0, nrows, c0, kmax, tid, PEDN_AG_THREADS); };
 
   // ---- forward: the encoders of the three networks side by side
-  ag_layer(acc, true, net, net + H * K1, net, net + H * K1, H, H, K1, true, mW, sXc, nullptr, 0, t, gather);
+  mlp_group_layer(acc, true, net, net + H * K1, net, net + H * K1, H, H, K1, true, mW, sXc, nullptr, 0, t, gather);
 #pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) mA[(vrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
-  ag_layer(acc, true, net + at2, net + at2 + H * H, net + at2, net + at2 + H * H, H, H, H, false, mW, sXc, mA + myrow * H, H, t, gather);
+  for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) mA[(vrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
+  mlp_group_layer(acc, true, net + at2, net + at2 + H * H, net + at2, net + at2 + H * H, H, H, H, false, mW, sXc, mA + myrow * H, H, t, gather);
   if (is_actor) {
 #pragma unroll
-    for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) sB[(vrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sB[(vrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
   } else {
 #pragma unroll
-    for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) sF[g][(vrow + r) * PEDN_CRITIC_FEAT + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sF[g][(vrow + r) * PEDN_GRAD_FEAT + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
   }
   // the actor's fc and heads (section 14's SAC kind); the critics' groups take the barriers
-  ag_layer(acc, is_actor, anet + at3, anet + at3 + H * H, anet + at3, anet + at3 + H * H, H, H, H, false, mW, sXc, sB + myrow * H, H, t, gather);
+  mlp_group_layer(acc, is_actor, anet + at3, anet + at3 + H * H, anet + at3, anet + at3 + H * H, H, H, H, false, mW, sXc, sB + myrow * H, H, t, gather);
   if (is_actor) {
 #pragma unroll
-    for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) sC[(vrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sC[(vrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
   }
   const float* wmu = anet + ah;
   const float* bmu = wmu + act_w * H;
   const float* wsd = bmu + act_w;
   const float* bsd = wsd + act_w * H;
-  ag_layer(acc, is_actor, wmu, bmu, wsd, bsd, act_w, 2 * act_w, H, false, mW, sXc, sC + myrow * H, H, t, gather);
+  mlp_group_layer(acc, is_actor, wmu, bmu, wsd, bsd, act_w, 2 * act_w, H, false, mW, sXc, sC + myrow * H, H, t, gather);
   if (is_actor && lane < 2 * act_w) {
     const int col = lane < act_w ? lane : PEDN_ACTOR_MAX_ACT + lane - act_w;
 #pragma unroll
-    for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) sOut[(vrow + r) * 2 * PEDN_ACTOR_MAX_ACT + col] = acc[r];
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sOut[(vrow + r) * 2 * PEDN_ACTOR_MAX_ACT + col] = acc[r];
   }
   __syncthreads();
 
@@ -221,7 +139,7 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
   float* mW2 = sW[g2];
   // ---- section 15's tail on a lane per (row, action) of the actor's group; what the backward's tail needs of it waits in LDS
   const int tr = t / act_w, tj = t - tr * act_w;
-  const bool pair = actor2 && tr < PEDN_CRITIC_TILE;
+  const bool pair = actor2 && tr < PEDN_GRAD_TILE;
   const bool live = tr < nrows;
   if (pair) {
     const float mu = sOut[tr * 2 * PEDN_ACTOR_MAX_ACT + tj], z = sOut[tr * 2 * PEDN_ACTOR_MAX_ACT + PEDN_ACTOR_MAX_ACT + tj];
@@ -256,16 +174,16 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
     }
   }
   if (!actor2) {
-    if (t < PEDN_CRITIC_TILE) {   // the newest frame's last column of the agent; zeros in rows past B and behind the row's end
+    if (t < PEDN_GRAD_TILE) {   // the newest frame's last column of the agent; zeros in rows past B and behind the row's end
       const size_t row = (size_t)(row0 + t);
-      sF[g2][t * PEDN_CRITIC_FEAT + H + act_w] = t < nrows ? a.s[(row * a.S + (a.S - 1)) * a.n_obs + obs0 + obs_w - 1] : 0.0f;
-      for (int j = K3; j < PEDN_CRITIC_FEAT; ++j) sF[g2][t * PEDN_CRITIC_FEAT + j] = 0.0f;
+      sF[g2][t * PEDN_GRAD_FEAT + H + act_w] = t < nrows ? a.s[(row * a.S + (a.S - 1)) * a.n_obs + obs0 + obs_w - 1] : 0.0f;
+      for (int j = K3; j < PEDN_GRAD_FEAT; ++j) sF[g2][t * PEDN_GRAD_FEAT + j] = 0.0f;
     }
     if (w4 == 3) sWo[g2][lane] = net[at4 + lane];
   }
   __syncthreads();   // new_action and logp are there
   if (actor2) {
-    if (t < PEDN_CRITIC_TILE) {
+    if (t < PEDN_GRAD_TILE) {
       float ent = 0.0f;
       for (int j = 0; j < act_w; ++j) ent = ent - sLogp[t * PEDN_ACTOR_MAX_ACT + j];
       sEnt[t] = ent;
@@ -274,30 +192,30 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
         la->out_agents[(size_t)(row0 + t) * la->n_agents + agent] = ent;
       }
     }
-  } else if (tr < PEDN_CRITIC_TILE)
-    sF[g2][tr * PEDN_CRITIC_FEAT + H + tj] = sAct[tr * PEDN_ACTOR_MAX_ACT + tj];
+  } else if (tr < PEDN_GRAD_TILE)
+    sF[g2][tr * PEDN_GRAD_FEAT + H + tj] = sAct[tr * PEDN_ACTOR_MAX_ACT + tj];
   // ---- the critics' fc and fc_out on (states, new_action): section 15's arithmetic, section 18's q
-  ag_layer(acc, !actor2, net + at3, net + at3 + H * K3, net + at3, net + at3 + H * K3, H, H, K3, false, mW2, sXc,
-           sF[actor2 ? 0 : g2] + myrow * PEDN_CRITIC_FEAT, PEDN_CRITIC_FEAT, t, gather);
+  mlp_group_layer(acc, !actor2, net + at3, net + at3 + H * K3, net + at3, net + at3 + H * K3, H, H, K3, false, mW2, sXc,
+           sF[actor2 ? 0 : g2] + myrow * PEDN_GRAD_FEAT, PEDN_GRAD_FEAT, t, gather);
   if (!actor2) {
 #pragma unroll
-    for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) sD[g2][(vrow + r) * PEDN_CRITIC_DS + lane] = acc[r];   // (no ReLU behind fc, as in the reference)
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sD[g2][(vrow + r) * PEDN_GRAD_DS + lane] = acc[r];   // (no ReLU behind fc, as in the reference)
   }
   __syncthreads();
   if (!actor2) {
-    if (lane < PEDN_CRITIC_ROWS) {   // fc_out on a lane per row, section 15's chain
+    if (lane < PEDN_GRAD_WAVE_ROWS) {   // fc_out on a lane per row, section 15's chain
       const int r = myrow + lane;
       float q = net[at4 + H];
-      for (int k = 0; k < H; ++k) q = q + sWo[g2][k] * sD[g2][r * PEDN_CRITIC_DS + k];
+      for (int k = 0; k < H; ++k) q = q + sWo[g2][k] * sD[g2][r * PEDN_GRAD_DS + k];
       sQ[g2][r] = q;
       if (r < nrows) {
         ActorGradLate la = ag_late_args();
         la->out_agents[((size_t)(1 + g2) * a.B + row0 + r) * la->n_agents + agent] = q;
       }
-    } else if (w4 == 1 && lane - PEDN_CRITIC_ROWS < act_w) {
+    } else if (w4 == 1 && lane - PEDN_GRAD_WAVE_ROWS < act_w) {
       // d q / d action_j = sum over o ascending of fc_out[o] * fc[o][64 + j], from +0.0, in double (64 terms that cancel: in float32 this
       // sum alone carried the gradient's error); fc's last chunk (columns 64 ..) is still staged
-      const int j = lane - PEDN_CRITIC_ROWS;
+      const int j = lane - PEDN_GRAD_WAVE_ROWS;
       double v = 0.0;
       for (int o = 0; o < H; ++o) v = v + (double)sWo[g2][o] * (double)mW2[o * PEDN_GRAD_PAD + j];
       sV[g2][j] = v;
@@ -309,7 +227,7 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
     ActorGradLate la = ag_late_args();
     const int B = la->B;
     const float alpha = (float)exp((double)la->log_alpha[agent]);
-    if (t < PEDN_CRITIC_TILE) {
+    if (t < PEDN_GRAD_TILE) {
       const float q1 = sQ[0][t], q2 = sQ[1][t];
       const float q = (q2 < q1 || q2 != q2) ? q2 : q1;   // torch.min: NaN wins
       sL[0][t] = -(alpha * sEnt[t]) - q;
@@ -338,8 +256,8 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
         gmu = (float)gu;
         gz = (float)(gsd * sp);
       }
-      mD[tr * PEDN_CRITIC_DS + tj] = gmu;
-      mD[tr * PEDN_CRITIC_DS + act_w + tj] = gz;
+      mD[tr * PEDN_GRAD_DS + tj] = gmu;
+      mD[tr * PEDN_GRAD_DS + act_w + tj] = gz;
       if (live) {
         const size_t plane = (size_t)B * la->n_actions;
         float* o = la->out_actions + (size_t)(row0 + tr) * la->n_actions + act0 + tj;
@@ -363,42 +281,32 @@ __global__ __launch_bounds__(PEDN_AG_THREADS) void sacactor_grad_kernel(ActorGra
   const float* hsd = hmu + act_w * H + act_w;
 
   // ---- backward through the actor, all waves.  The heads: a thread per weight, then h3's gradient behind the ReLU mask into sD[0]
-  for (int idx = tid; idx < 2 * act_w * H; idx += PEDN_AG_THREADS) {
-    const int o = idx >> 6, k = idx & 63;
-    float v = 0.0f;
-    for (int r = 0; r < nrows; ++r) v = v + mD[r * PEDN_CRITIC_DS + o] * sC[r * H + k];
-    gws[ah + (o < act_w ? 0 : act_w) + idx] = v;
-  }
-  if (tid < 2 * act_w) {
-    float v = 0.0f;
-    for (int r = 0; r < nrows; ++r) v = v + mD[r * PEDN_CRITIC_DS + tid];
-    gws[ah + (tid < act_w ? act_w * H + tid : 2 * act_w * H + tid)] = v;
-  }
+  mlp_grad_heads_tile<false>(mD, PEDN_GRAD_DS, sC, act_w, nrows, gws + ah, true, tid, PEDN_AG_THREADS);
   float* dD = sD[0];
-  for (int idx = tid; idx < PEDN_CRITIC_TILE * H; idx += PEDN_AG_THREADS) {
+  for (int idx = tid; idx < PEDN_GRAD_TILE * H; idx += PEDN_AG_THREADS) {
     const int r = idx >> 6, k = idx & 63;
     float v = 0.0f;
-    for (int o = 0; o < 2 * act_w; ++o) v = v + mD[r * PEDN_CRITIC_DS + o] * (o < act_w ? hmu[o * H + k] : hsd[(o - act_w) * H + k]);
-    dD[r * PEDN_CRITIC_DS + k] = sC[idx] > 0.0f ? v : 0.0f;
+    for (int o = 0; o < 2 * act_w; ++o) v = v + mD[r * PEDN_GRAD_DS + o] * (o < act_w ? hmu[o * H + k] : hsd[(o - act_w) * H + k]);
+    dD[r * PEDN_GRAD_DS + k] = sC[idx] > 0.0f ? v : 0.0f;
   }
   // fc, the mask, encoder.fc2, the mask, encoder.fc1
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   float dx[4];
-  ag_dw(dD, sB, H, H, nrows, gws + at3, gws + at3 + H * H, sW[0], sXc, false, tid, gather);
-  ag_dx(dx, dD, anet + at3, H, sW[1], tid);
+  mlp_grad_dw_tile<4, false>(dD, PEDN_GRAD_DS, sB, H, H, nrows, gws + at3, gws + at3 + H * H, sW[0], false, true, wv < 8, 8, tid, PEDN_AG_THREADS, gather);
+  mlp_grad_dx_tile(dx, wv < 8, dD + 4 * wv * PEDN_GRAD_DS, PEDN_GRAD_DS, anet + at3, H, sW[1], tid, PEDN_AG_THREADS);
   __syncthreads();   // every wave has read the output gradient that is overwritten now
   if (wv < 8) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dD[(4 * wv + r) * PEDN_CRITIC_DS + lane] = sB[(4 * wv + r) * H + lane] > 0.0f ? dx[r] : 0.0f;
+    for (int r = 0; r < 4; ++r) dD[(4 * wv + r) * PEDN_GRAD_DS + lane] = sB[(4 * wv + r) * H + lane] > 0.0f ? dx[r] : 0.0f;
   }
-  ag_dw(dD, sA[2], H, H, nrows, gws + at2, gws + at2 + H * H, sW[0], sXc, false, tid, gather);
-  ag_dx(dx, dD, anet + at2, H, sW[1], tid);
+  mlp_grad_dw_tile<4, false>(dD, PEDN_GRAD_DS, sA[2], H, H, nrows, gws + at2, gws + at2 + H * H, sW[0], false, true, wv < 8, 8, tid, PEDN_AG_THREADS, gather);
+  mlp_grad_dx_tile(dx, wv < 8, dD + 4 * wv * PEDN_GRAD_DS, PEDN_GRAD_DS, anet + at2, H, sW[1], tid, PEDN_AG_THREADS);
   __syncthreads();
   if (wv < 8) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dD[(4 * wv + r) * PEDN_CRITIC_DS + lane] = sA[2][(4 * wv + r) * H + lane] > 0.0f ? dx[r] : 0.0f;
+    for (int r = 0; r < 4; ++r) dD[(4 * wv + r) * PEDN_GRAD_DS + lane] = sA[2][(4 * wv + r) * H + lane] > 0.0f ? dx[r] : 0.0f;
   }
-  ag_dw(dD, sXc, PEDN_ACTOR_CHUNK, K1, nrows, gws, gws + H * K1, sW[0], sXc, true, tid, gather);
+  mlp_grad_dw_tile<4, false>(dD, PEDN_GRAD_DS, sXc, PEDN_ACTOR_CHUNK, K1, nrows, gws, gws + H * K1, sW[0], true, true, wv < 8, 8, tid, PEDN_AG_THREADS, gather);
   if (given) return;
   __syncthreads();   // the tail's lanes have read the draw counter
   if (tid == 0) {
@@ -416,28 +324,16 @@ struct ActorAdamArgs {
   float* log_alpha;            // [n_agents]
   float* alpha_mv;             // [2][n_agents]: exp_avg and exp_avg_sq of log_alpha
   float* scalars;              // [3][n_agents]: actor_loss, alpha_loss, alpha_grad
-  int64_t* state;              // 0 the step count, 1 the ticket (its low 32 bits), 2 and 3 the doubles beta1^t and beta2^t
+  int64_t* state;              // pedn_adam.hpp's step state
   int64_t n, pack4, ws_stride; // floats: the pack's length, where a workspace row's sums start, a workspace row's length
   int32_t tiles, n_agents, B, do_adam;
   double lr, alpha_lr, beta1, beta2;
-  float b2, omb1, omb2, eps;   // (float)beta2, (float)(1 - beta1), (float)(1 - beta2), (float)eps
+  AdamCoef coef;
 };
 
-// Section 18's Adam step of one element with exp_avg_sq's last product fused into its sum: v = fma((1 - beta2) * g, g, v * beta2), one rounding
-// fewer than critic_adam_one's.  torch's own step fuses it too, and with every product rounded one element of a recorded update lay 1.26 ulp
-// from the float64 step where the reference lay 0.26.  An explicit fmaf: the library is built with -ffp-contract=off.
-__device__ __forceinline__ float actor_adam_one(float g, float& m, float& v, float p, const ActorAdamArgs& a, float nstep, float s) {
-  m = m + a.omb1 * (g - m);
-  v = fmaf(a.omb2 * g, g, v * a.b2);
-  const float den = sqrtf(v) / s + a.eps;
-  return p + (nstep * m) / den;
-}
-
 __global__ __launch_bounds__(256) void sacactor_adam_kernel(ActorAdamArgs a) {
-  const double* pw = reinterpret_cast<const double*>(a.state + 2);
-  const int64_t steps = a.state[0];
-  const double b1t = pw[0] * a.beta1, b2t = pw[1] * a.beta2;   // the products behind this step
-  const float nstep = -(float)(a.lr / (1.0 - b1t)), nstep_alpha = -(float)(a.alpha_lr / (1.0 - b1t)), s = (float)sqrt(1.0 - b2t);
+  const AdamStep st = adam_step_begin(a.state, a.beta1, a.beta2);
+  const float nstep = adam_nstep(a.lr, st), nstep_alpha = adam_nstep(a.alpha_lr, st), s = st.s;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (int64_t i = gid; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
     float g = 0.0f;
@@ -445,7 +341,7 @@ __global__ __launch_bounds__(256) void sacactor_adam_kernel(ActorAdamArgs a) {
     a.grads[i] = g;
     if (a.do_adam) {
       float m = a.m[i], v = a.v[i];
-      const float p = actor_adam_one(g, m, v, a.p[i], a, nstep, s);
+      const float p = adam_one<true>(g, m, v, a.p[i], a.coef, nstep, s);
       a.m[i] = m; a.v[i] = v; a.p[i] = p;
     }
   }
@@ -462,22 +358,13 @@ __global__ __launch_bounds__(256) void sacactor_adam_kernel(ActorAdamArgs a) {
     a.scalars[2 * a.n_agents + gid] = ga;
     if (a.do_adam) {
       float m = a.alpha_mv[gid], v = a.alpha_mv[a.n_agents + gid];
-      const float p = actor_adam_one(ga, m, v, a.log_alpha[gid], a, nstep_alpha, s);
+      const float p = adam_one<true>(ga, m, v, a.log_alpha[gid], a.coef, nstep_alpha, s);
       a.alpha_mv[gid] = m; a.alpha_mv[a.n_agents + gid] = v; a.log_alpha[gid] = p;
     }
   }
   if (!a.do_adam) return;
   __syncthreads();   // every wave of the workgroup has read the step state
-  if (threadIdx.x == 0) {
-    unsigned* ticket = reinterpret_cast<unsigned*>(a.state + 1);
-    const unsigned mine = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (mine + 1u == gridDim.x) {   // the last workgroup: nobody reads the state any more
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.state, steps + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.state + 2, (int64_t)__double_as_longlong(b1t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.state + 3, (int64_t)__double_as_longlong(b2t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) adam_step_advance(a.state, st, gridDim.x);   // the last workgroup advances the state
 }
 
 // ---- host side: pedn_sac_actor_update of include/pedn.h; no state in the engine's handle
@@ -490,17 +377,14 @@ int pedn_sac_actor_update(const float* states, const float* noise, const int32_t
   if (!states || !table || !critic_table || !actor_params || !online_params || !log_alpha || !target_entropy || !grads || !exp_avg || !exp_avg_sq ||
       !alpha_moments || !workspace || !out_actions || !out_agents || !scalars || !adam_state || !draw_state)
     return fail(nullptr, PEDN_E_ARG, "null argument");
-  if (hidden_size != PEDN_ACTOR_HIDDEN) return fail(nullptr, PEDN_E_ARG, "the SAC actor kernels are built for hidden_size 64");
-  if (batch < 1 || stack_size < 1 || n_obs < 1 || n_actions < 1 || n_agents < 1 || n_agents > 65535)
-    return fail(nullptr, PEDN_E_ARG, "batch, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)");
-  if (pack_floats < 1) return fail(nullptr, PEDN_E_ARG, "the actors' pack is empty");
-  if (((uintptr_t)actor_params | (uintptr_t)online_params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)workspace) & 15)
-    return fail(nullptr, PEDN_E_ARG, "the packs and the workspace must be 16-byte aligned");
-  if (!(actor_lr >= 0.0 && actor_lr < INFINITY && alpha_lr >= 0.0 && alpha_lr < INFINITY))
-    return fail(nullptr, PEDN_E_ARG, "lr must be finite and not negative");
-  if (!(eps >= 0.0 && eps < INFINITY)) return fail(nullptr, PEDN_E_ARG, "eps must be finite and not negative");
-  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return fail(nullptr, PEDN_E_ARG, "the betas must be in [0, 1)");
-  const int tiles = (batch + PEDN_CRITIC_TILE - 1) / PEDN_CRITIC_TILE;
+  if (const char* why = update_refusal(
+          hidden_size, "the SAC actor kernels are built for hidden_size 64", batch >= 1 && stack_size >= 1 && n_obs >= 1 && n_actions >= 1, n_agents,
+          "batch, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)", nullptr, pack_floats >= 1,
+          "the actors' pack is empty",
+          (uintptr_t)actor_params | (uintptr_t)online_params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)workspace,
+          actor_lr, alpha_lr, beta1, beta2, eps))
+    return fail(nullptr, PEDN_E_ARG, why);
+  const int tiles = (batch + PEDN_GRAD_TILE - 1) / PEDN_GRAD_TILE;
   const int64_t pack4 = (pack_floats + 3) / 4 * 4;
   const int64_t ws_stride = pack4 + (2 * (int64_t)n_agents + 3) / 4 * 4;
   ActorGradArgs a{};
@@ -517,7 +401,7 @@ int pedn_sac_actor_update(const float* states, const float* noise, const int32_t
   b.scalars = scalars; b.state = adam_state; b.n = pack_floats; b.pack4 = pack4; b.ws_stride = ws_stride;
   b.tiles = tiles; b.n_agents = n_agents; b.B = batch; b.do_adam = do_adam ? 1 : 0;
   b.lr = actor_lr; b.alpha_lr = alpha_lr; b.beta1 = beta1; b.beta2 = beta2;
-  b.b2 = (float)beta2; b.omb1 = (float)(1.0 - beta1); b.omb2 = (float)(1.0 - beta2); b.eps = (float)eps;
+  b.coef = adam_coef(beta1, beta2, eps);
   int64_t blocks = (b.n + 255) / 256;
   const int64_t need = ((int64_t)n_agents + 255) / 256;   // the agents' scalars have a thread each
   blocks = blocks < need ? need : blocks < 2048 ? blocks : 2048;

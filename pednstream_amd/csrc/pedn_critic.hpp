@@ -18,13 +18,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pedn_adam.hpp"
 #include "pedn_mlp.hpp"
 #include "pedn_mlp_grad.hpp"
-
-#define PEDN_CRITIC_TILE 32       // rows per workgroup
-#define PEDN_CRITIC_ROWS 8        // rows per wave
-#define PEDN_CRITIC_FEAT 96       // words of a critic's fc input row: 64 + act_w + 1 <= 73, rounded up to whole chunks
-#define PEDN_CRITIC_DS 68         // words of a row of h3 and of the output gradients: 16-byte aligned rows, 8 rows on 8 banks
 
 struct CriticArgs {
   const float* s;              // [B][S][n_obs]
@@ -40,83 +36,14 @@ struct CriticArgs {
   float scale;                 // (float)(2.0 / B)
 };
 
-// One forward layer of a critic's 4 waves (thread t of 256) for the tile: acc[r] = b[o]; then mlp_mac over chunks of 32 inputs, lane o.
-// first: gather(c0, kmax) fills sXc (32 rows of 32, zeros behind kmax and in rows past B) for both critics; otherwise x is this wave's rows
-// xin of stride xs.  The barriers are the workgroup's: both critics call this with the same K.
-template <class Gather>
-__device__ __forceinline__ void critic_layer(float (&acc)[PEDN_CRITIC_ROWS], const float* w, const float* b, int K, bool first, float* sW,
-                                             const float* sXc, const float* xin, int xs, int t, Gather gather) {
-  const int lane = t & 63, w4 = t >> 6;
-  const float bias = b[lane];
-#pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) acc[r] = bias;
-  for (int c0 = 0; c0 < K; c0 += PEDN_ACTOR_CHUNK) {
-    const int kmax = K - c0 < PEDN_ACTOR_CHUNK ? K - c0 : PEDN_ACTOR_CHUNK;
-    __syncthreads();   // the chunk before has been consumed (and what the caller wrote to LDS for this layer is there)
-    for (int idx = t; idx < PEDN_ACTOR_HIDDEN * PEDN_ACTOR_CHUNK; idx += 256) {
-      const int o = idx / PEDN_ACTOR_CHUNK, kk = idx % PEDN_ACTOR_CHUNK;
-      if (kk < kmax) sW[o * PEDN_GRAD_PAD + kk] = w[(unsigned)(o * K + c0 + kk)];
-    }
-    if (first) gather(c0, kmax);
-    __syncthreads();
-    mlp_mac(acc, sW + lane * PEDN_GRAD_PAD, first ? sXc + w4 * PEDN_CRITIC_ROWS * PEDN_ACTOR_CHUNK : xin + c0, first ? PEDN_ACTOR_CHUNK : xs, kmax);
-  }
-}
-
-// The gradients of one layer's weight [64][K] and bias from the tile's output gradient d (rows of PEDN_CRITIC_DS) and its input x (rows of
-// xs words that cover whole chunks; first: the gathered chunk sXc), into gw and gb: wave w4 of the critic takes columns 8 * w4 .. + 7 of
-// every chunk.  sG: the critic's staging rows.
-template <class Gather>
-__device__ __forceinline__ void critic_dw(const float* d, const float* x, int xs, int K, int nrows, float* gw, float* gb, float* sG, bool first,
-                                          int t, Gather gather) {
-  const int lane = t & 63, w4 = t >> 6;
-  __syncthreads();   // d is there
-  if (w4 == 0) {
-    float b = 0.0f;
-    for (int r = 0; r < nrows; ++r) b = b + d[r * PEDN_CRITIC_DS + lane];
-    gb[lane] = b;
-  }
-  for (int c0 = 0; c0 < K; c0 += PEDN_ACTOR_CHUNK) {
-    const int kmax = K - c0 < PEDN_ACTOR_CHUNK ? K - c0 : PEDN_ACTOR_CHUNK;
-    if (first) {
-      gather(c0, kmax);
-      __syncthreads();
-    }
-    float g[PEDN_CRITIC_ROWS];
-#pragma unroll
-    for (int j = 0; j < PEDN_CRITIC_ROWS; ++j) g[j] = 0.0f;
-    mlp_grad_dw(g, d + lane, PEDN_CRITIC_DS, (first ? x : x + c0) + PEDN_CRITIC_ROWS * w4, xs, nrows);
-#pragma unroll
-    for (int j = 0; j < PEDN_CRITIC_ROWS; ++j) sG[lane * PEDN_GRAD_PAD + PEDN_CRITIC_ROWS * w4 + j] = g[j];
-    __syncthreads();
-    mlp_grad_store(sG, gw, K, c0, kmax, t, 256);
-    __syncthreads();   // sG and the gathered chunk are free
-  }
-}
-
-// acc[r] = sum over o ascending of d[r][o] * w[o][k] for lane k < 64 and the wave's 8 rows, from +0.0.  sT: the critic's staging rows.
-__device__ __forceinline__ void critic_dx(float (&acc)[PEDN_CRITIC_ROWS], const float* d, const float* w, int K, float* sT, int t) {
-  const int lane = t & 63, w4 = t >> 6;
-#pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) acc[r] = 0.0f;
-  int n = PEDN_ACTOR_CHUNK;
-  asm volatile("" : "+s"(n));   // (no instruction: the count stays a run-time value, see mlp_grad_dx)
-  for (int o0 = 0; o0 < PEDN_ACTOR_HIDDEN; o0 += PEDN_ACTOR_CHUNK) {
-    __syncthreads();   // the staging rows are free
-    mlp_grad_stage_wt(sT, w, K, o0, t, 256);
-    __syncthreads();
-    mlp_grad_dx(acc, sT + lane * PEDN_GRAD_PAD, d + w4 * PEDN_CRITIC_ROWS * PEDN_CRITIC_DS + o0, PEDN_CRITIC_DS, n);
-  }
-}
-
 __global__ __launch_bounds__(512) void critic_grad_kernel(CriticArgs a) {
   __shared__ float sW[2][PEDN_ACTOR_HIDDEN * PEDN_GRAD_PAD];
-  __shared__ __attribute__((aligned(16))) float sXc[PEDN_CRITIC_TILE * PEDN_ACTOR_CHUNK];
-  __shared__ __attribute__((aligned(16))) float sH1[2][PEDN_CRITIC_TILE * PEDN_ACTOR_HIDDEN];
-  __shared__ __attribute__((aligned(16))) float sFeat[2][PEDN_CRITIC_TILE * PEDN_CRITIC_FEAT];
-  __shared__ __attribute__((aligned(16))) float sD[2][PEDN_CRITIC_TILE * PEDN_CRITIC_DS];   // h3, then the output gradient of the layer at hand
-  __shared__ float sE[2][PEDN_CRITIC_TILE];    // q - td
-  __shared__ float sDq[2][PEDN_CRITIC_TILE];   // its gradient
+  __shared__ __attribute__((aligned(16))) float sXc[PEDN_GRAD_TILE * PEDN_ACTOR_CHUNK];
+  __shared__ __attribute__((aligned(16))) float sH1[2][PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];
+  __shared__ __attribute__((aligned(16))) float sFeat[2][PEDN_GRAD_TILE * PEDN_GRAD_FEAT];
+  __shared__ __attribute__((aligned(16))) float sD[2][PEDN_GRAD_TILE * PEDN_GRAD_DS];   // h3, then the output gradient of the layer at hand
+  __shared__ float sE[2][PEDN_GRAD_TILE];    // q - td
+  __shared__ float sDq[2][PEDN_GRAD_TILE];   // its gradient
   const int tid = (int)threadIdx.x, t = tid & 255, lane = tid & 63;
   const int c = __builtin_amdgcn_readfirstlane(tid >> 8), w4 = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
   const int H = PEDN_ACTOR_HIDDEN;
@@ -124,8 +51,8 @@ __global__ __launch_bounds__(512) void critic_grad_kernel(CriticArgs a) {
   const int32_t* tb = a.table + (size_t)agent * PEDN_ACTOR_TABLE_COLS;
   const int obs0 = tb[0], obs_w = tb[1], act0 = tb[2], act_w = tb[3];
   const int K1 = a.S * obs_w, K3 = H + act_w + 1;
-  const int row0 = (int)blockIdx.x * PEDN_CRITIC_TILE;
-  const int nrows = a.B - row0 < PEDN_CRITIC_TILE ? a.B - row0 : PEDN_CRITIC_TILE;
+  const int row0 = (int)blockIdx.x * PEDN_GRAD_TILE;
+  const int nrows = a.B - row0 < PEDN_GRAD_TILE ? a.B - row0 : PEDN_GRAD_TILE;
   const int32_t at = a.ctable[2 * agent + c];
   const float* net = a.online + at;
   float* gws = a.ws + (size_t)blockIdx.x * a.ws_stride + at;
@@ -134,45 +61,36 @@ __global__ __launch_bounds__(512) void critic_grad_kernel(CriticArgs a) {
   float* mH1 = sH1[c];
   float* mF = sFeat[c];
   float* mD = sD[c];
-  const int myrow = w4 * PEDN_CRITIC_ROWS;
-  float acc[PEDN_CRITIC_ROWS];
+  const int myrow = w4 * PEDN_GRAD_WAVE_ROWS;
+  float acc[PEDN_GRAD_WAVE_ROWS];
 
-  // inputs [c0, c0 + kmax) of the tile's rows for both critics: input f * S + s is s[row][s][obs0 + f]; zeros elsewhere
-  auto gather = [&](int c0, int kmax) {
-    for (int idx = tid; idx < PEDN_CRITIC_TILE * PEDN_ACTOR_CHUNK; idx += 512) {
-      const int r = idx / PEDN_ACTOR_CHUNK, kk = idx % PEDN_ACTOR_CHUNK;
-      float v = 0.0f;
-      if (kk < kmax && r < nrows) {
-        const unsigned k = (unsigned)(c0 + kk), f = k / (unsigned)a.S, s = k - f * (unsigned)a.S;
-        v = a.s[((size_t)(row0 + r) * a.S + s) * a.n_obs + obs0 + f];
-      }
-      sXc[idx] = v;
-    }
-  };
+  // inputs [c0, c0 + kmax) of the tile's rows for both critics
+  auto gather = [&](int c0, int kmax) { sac_gather_chunk(sXc, a.s, a.S, a.n_obs, obs0, row0, nrows, c0, kmax, tid, 512); };
 
   // ---- forward: section 15's critic on the sampled states and the stored actions
-  critic_layer(acc, net, net + H * K1, K1, true, mW, sXc, nullptr, 0, t, gather);
+  mlp_group_layer(acc, true, net, net + H * K1, net, net + H * K1, H, H, K1, true, mW, sXc, nullptr, 0, t, gather);
 #pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) mH1[(myrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
-  critic_layer(acc, net + at2, net + at2 + H * H, H, false, mW, sXc, mH1 + myrow * H, H, t, gather);
+  for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) mH1[(myrow + r) * H + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
+  mlp_group_layer(acc, true, net + at2, net + at2 + H * H, net + at2, net + at2 + H * H, H, H, H, false, mW, sXc, mH1 + myrow * H, H, t, gather);
 #pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) mF[(myrow + r) * PEDN_CRITIC_FEAT + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
-  if (t < PEDN_CRITIC_TILE) {   // the stored action and the newest frame's last column of the agent; zeros in rows past B
+  for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) mF[(myrow + r) * PEDN_GRAD_FEAT + lane] = acc[r] < 0.0f ? 0.0f : acc[r];
+  if (t < PEDN_GRAD_TILE) {   // the stored action and the newest frame's last column of the agent; zeros in rows past B
     const bool live = t < nrows;
     const size_t row = (size_t)(row0 + t);
-    for (int j = 0; j < act_w; ++j) mF[t * PEDN_CRITIC_FEAT + H + j] = live ? a.actions[row * a.n_actions + act0 + j] : 0.0f;
-    mF[t * PEDN_CRITIC_FEAT + H + act_w] = live ? a.s[(row * a.S + (a.S - 1)) * a.n_obs + obs0 + obs_w - 1] : 0.0f;
-    for (int j = K3; j < PEDN_CRITIC_FEAT; ++j) mF[t * PEDN_CRITIC_FEAT + j] = 0.0f;
+    for (int j = 0; j < act_w; ++j) mF[t * PEDN_GRAD_FEAT + H + j] = live ? a.actions[row * a.n_actions + act0 + j] : 0.0f;
+    mF[t * PEDN_GRAD_FEAT + H + act_w] = live ? a.s[(row * a.S + (a.S - 1)) * a.n_obs + obs0 + obs_w - 1] : 0.0f;
+    for (int j = K3; j < PEDN_GRAD_FEAT; ++j) mF[t * PEDN_GRAD_FEAT + j] = 0.0f;
   }
-  critic_layer(acc, net + at3, net + at3 + H * K3, K3, false, mW, sXc, mF + myrow * PEDN_CRITIC_FEAT, PEDN_CRITIC_FEAT, t, gather);
+  mlp_group_layer(acc, true, net + at3, net + at3 + H * K3, net + at3, net + at3 + H * K3, H, H, K3, false, mW, sXc, mF + myrow * PEDN_GRAD_FEAT,
+                  PEDN_GRAD_FEAT, t, gather);
 #pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) mD[(myrow + r) * PEDN_CRITIC_DS + lane] = acc[r];   // (no ReLU behind fc, as in the reference)
+  for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) mD[(myrow + r) * PEDN_GRAD_DS + lane] = acc[r];   // (no ReLU behind fc, as in the reference)
   const float* wo = net + at4;
   __syncthreads();
-  if (lane < PEDN_CRITIC_ROWS) {   // fc_out on a lane per row, section 15's chain
+  if (lane < PEDN_GRAD_WAVE_ROWS) {   // fc_out on a lane per row, section 15's chain
     const int r = myrow + lane;
     float q = wo[H];
-    for (int k = 0; k < H; ++k) q = q + wo[k] * mD[r * PEDN_CRITIC_DS + k];
+    for (int k = 0; k < H; ++k) q = q + wo[k] * mD[r * PEDN_GRAD_DS + k];
     float e = 0.0f;
     if (r < nrows) {
       const size_t row = (size_t)(row0 + r);
@@ -187,7 +105,7 @@ __global__ __launch_bounds__(512) void critic_grad_kernel(CriticArgs a) {
   // ---- backward.  fc_out: its weight (lane k of wave 1), its bias and the tile's sum of squares (wave 2); then h3's gradient in place
   if (w4 == 1) {
     float g = 0.0f;
-    for (int r = 0; r < nrows; ++r) g = g + sDq[c][r] * mD[r * PEDN_CRITIC_DS + lane];
+    for (int r = 0; r < nrows; ++r) g = g + sDq[c][r] * mD[r * PEDN_GRAD_DS + lane];
     gws[at4 + lane] = g;
   } else if (w4 == 2 && lane < 2) {
     float g = 0.0f;
@@ -203,21 +121,21 @@ __global__ __launch_bounds__(512) void critic_grad_kernel(CriticArgs a) {
   {
     const float wl = wo[lane];
 #pragma unroll
-    for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) mD[(myrow + r) * PEDN_CRITIC_DS + lane] = sDq[c][myrow + r] * wl;
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) mD[(myrow + r) * PEDN_GRAD_DS + lane] = sDq[c][myrow + r] * wl;
   }
   // fc: weight and bias; the 64 encoder columns of dfeat; the ReLU mask z > 0
-  critic_dw(mD, mF, PEDN_CRITIC_FEAT, K3, nrows, gws + at3, gws + at3 + H * K3, mW, false, t, gather);
-  critic_dx(acc, mD, net + at3, K3, mW, t);
+  mlp_grad_dw_tile<8, false>(mD, PEDN_GRAD_DS, mF, PEDN_GRAD_FEAT, K3, nrows, gws + at3, gws + at3 + H * K3, mW, false, true, true, 0, t, 256, gather);
+  mlp_grad_dx_tile(acc, true, mD + myrow * PEDN_GRAD_DS, PEDN_GRAD_DS, net + at3, K3, mW, t, 256);
   __syncthreads();   // every wave has read the output gradient that is overwritten now
 #pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) mD[(myrow + r) * PEDN_CRITIC_DS + lane] = mF[(myrow + r) * PEDN_CRITIC_FEAT + lane] > 0.0f ? acc[r] : 0.0f;
+  for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) mD[(myrow + r) * PEDN_GRAD_DS + lane] = mF[(myrow + r) * PEDN_GRAD_FEAT + lane] > 0.0f ? acc[r] : 0.0f;
   // encoder.fc2, then the mask, then encoder.fc1
-  critic_dw(mD, mH1, H, H, nrows, gws + at2, gws + at2 + H * H, mW, false, t, gather);
-  critic_dx(acc, mD, net + at2, H, mW, t);
+  mlp_grad_dw_tile<8, false>(mD, PEDN_GRAD_DS, mH1, H, H, nrows, gws + at2, gws + at2 + H * H, mW, false, true, true, 0, t, 256, gather);
+  mlp_grad_dx_tile(acc, true, mD + myrow * PEDN_GRAD_DS, PEDN_GRAD_DS, net + at2, H, mW, t, 256);
   __syncthreads();
 #pragma unroll
-  for (int r = 0; r < PEDN_CRITIC_ROWS; ++r) mD[(myrow + r) * PEDN_CRITIC_DS + lane] = mH1[(myrow + r) * H + lane] > 0.0f ? acc[r] : 0.0f;
-  critic_dw(mD, sXc, PEDN_ACTOR_CHUNK, K1, nrows, gws, gws + H * K1, mW, true, t, gather);
+  for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) mD[(myrow + r) * PEDN_GRAD_DS + lane] = mH1[(myrow + r) * H + lane] > 0.0f ? acc[r] : 0.0f;
+  mlp_grad_dw_tile<8, false>(mD, PEDN_GRAD_DS, sXc, PEDN_ACTOR_CHUNK, K1, nrows, gws, gws + H * K1, mW, true, true, true, 0, t, 256, gather);
 }
 
 struct CriticAdamArgs {
@@ -227,25 +145,16 @@ struct CriticAdamArgs {
   float4* v;                   // exp_avg_sq
   float4* p;                   // the online pack
   float* losses;               // [n_agents][2]
-  int64_t* state;              // 0 the step count, 1 the ticket (its low 32 bits), 2 and 3 the doubles beta1^t and beta2^t
+  int64_t* state;              // pedn_adam.hpp's step state
   int64_t n4, ws_stride4;      // the pack's and a workspace row's length in float4
   int32_t tiles, n_agents, B, do_adam;
   double lr, beta1, beta2;
-  float b2, omb1, omb2, eps;   // (float)beta2, (float)(1 - beta1), (float)(1 - beta2), (float)eps
+  AdamCoef coef;
 };
 
-__device__ __forceinline__ float critic_adam_one(float g, float& m, float& v, float p, const CriticAdamArgs& a, float nstep, float s) {
-  m = m + a.omb1 * (g - m);
-  v = v * a.b2 + (a.omb2 * g) * g;
-  const float den = sqrtf(v) / s + a.eps;
-  return p + (nstep * m) / den;
-}
-
 __global__ __launch_bounds__(256) void critic_adam_kernel(CriticAdamArgs a) {
-  const double* pw = reinterpret_cast<const double*>(a.state + 2);
-  const int64_t steps = a.state[0];
-  const double b1t = pw[0] * a.beta1, b2t = pw[1] * a.beta2;   // the products behind this step
-  const float nstep = -(float)(a.lr / (1.0 - b1t)), s = (float)sqrt(1.0 - b2t);
+  const AdamStep st = adam_step_begin(a.state, a.beta1, a.beta2);
+  const float nstep = adam_nstep(a.lr, st), s = st.s;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (int64_t i = gid; i < a.n4; i += (int64_t)gridDim.x * blockDim.x) {
     float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -256,10 +165,10 @@ __global__ __launch_bounds__(256) void critic_adam_kernel(CriticAdamArgs a) {
     a.grads[i] = g;
     if (a.do_adam) {
       float4 m = a.m[i], v = a.v[i], p = a.p[i];
-      p.x = critic_adam_one(g.x, m.x, v.x, p.x, a, nstep, s);
-      p.y = critic_adam_one(g.y, m.y, v.y, p.y, a, nstep, s);
-      p.z = critic_adam_one(g.z, m.z, v.z, p.z, a, nstep, s);
-      p.w = critic_adam_one(g.w, m.w, v.w, p.w, a, nstep, s);
+      p.x = adam_one<false>(g.x, m.x, v.x, p.x, a.coef, nstep, s);
+      p.y = adam_one<false>(g.y, m.y, v.y, p.y, a.coef, nstep, s);
+      p.z = adam_one<false>(g.z, m.z, v.z, p.z, a.coef, nstep, s);
+      p.w = adam_one<false>(g.w, m.w, v.w, p.w, a.coef, nstep, s);
       a.m[i] = m; a.v[i] = v; a.p[i] = p;
     }
   }
@@ -271,16 +180,7 @@ __global__ __launch_bounds__(256) void critic_adam_kernel(CriticAdamArgs a) {
   }
   if (!a.do_adam) return;
   __syncthreads();   // every wave of the workgroup has read the step state
-  if (threadIdx.x == 0) {
-    unsigned* ticket = reinterpret_cast<unsigned*>(a.state + 1);
-    const unsigned mine = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (mine + 1u == gridDim.x) {   // the last workgroup: nobody reads the state any more
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.state, steps + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.state + 2, (int64_t)__double_as_longlong(b1t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.state + 3, (int64_t)__double_as_longlong(b2t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (threadIdx.x == 0) adam_step_advance(a.state, st, gridDim.x);   // the last workgroup advances the state
 }
 
 // ---- host side: pedn_sac_critic_update of include/pedn.h; no state in the engine's handle
@@ -292,16 +192,13 @@ int pedn_sac_critic_update(const float* states, const float* actions, const floa
   if (!states || !actions || !td_target || !table || !critic_table || !online_params || !grads || !exp_avg || !exp_avg_sq || !workspace || !q ||
       !losses || !adam_state)
     return fail(nullptr, PEDN_E_ARG, "null argument");
-  if (hidden_size != PEDN_ACTOR_HIDDEN) return fail(nullptr, PEDN_E_ARG, "the critic kernels are built for hidden_size 64");
-  if (batch < 1 || stack_size < 1 || n_obs < 1 || n_actions < 1 || n_agents < 1 || n_agents > 65535)
-    return fail(nullptr, PEDN_E_ARG, "batch, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)");
-  if (pack_floats < 4 || pack_floats % 4) return fail(nullptr, PEDN_E_ARG, "the packs' length must be a positive multiple of 4 floats");
-  if (((uintptr_t)online_params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)workspace) & 15)
-    return fail(nullptr, PEDN_E_ARG, "the packs and the workspace must be 16-byte aligned");
-  if (!(lr >= 0.0 && lr < INFINITY)) return fail(nullptr, PEDN_E_ARG, "lr must be finite and not negative");
-  if (!(eps >= 0.0 && eps < INFINITY)) return fail(nullptr, PEDN_E_ARG, "eps must be finite and not negative");
-  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return fail(nullptr, PEDN_E_ARG, "the betas must be in [0, 1)");
-  const int tiles = (batch + PEDN_CRITIC_TILE - 1) / PEDN_CRITIC_TILE;
+  if (const char* why = update_refusal(
+          hidden_size, "the critic kernels are built for hidden_size 64", batch >= 1 && stack_size >= 1 && n_obs >= 1 && n_actions >= 1, n_agents,
+          "batch, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)", nullptr, pack_floats >= 4 && pack_floats % 4 == 0,
+          "the packs' length must be a positive multiple of 4 floats",
+          (uintptr_t)online_params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)workspace, lr, lr, beta1, beta2, eps))
+    return fail(nullptr, PEDN_E_ARG, why);
+  const int tiles = (batch + PEDN_GRAD_TILE - 1) / PEDN_GRAD_TILE;
   const int64_t ws_stride = pack_floats + (2 * (int64_t)n_agents + 3) / 4 * 4;
   CriticArgs a{};
   a.s = states; a.actions = actions; a.td = td_target; a.table = table; a.ctable = critic_table; a.online = online_params;
@@ -315,7 +212,7 @@ int pedn_sac_critic_update(const float* states, const float* actions, const floa
   b.v = reinterpret_cast<float4*>(exp_avg_sq); b.p = reinterpret_cast<float4*>(online_params); b.losses = losses; b.state = adam_state;
   b.n4 = pack_floats / 4; b.ws_stride4 = ws_stride / 4; b.tiles = tiles; b.n_agents = n_agents; b.B = batch; b.do_adam = do_adam ? 1 : 0;
   b.lr = lr; b.beta1 = beta1; b.beta2 = beta2;
-  b.b2 = (float)beta2; b.omb1 = (float)(1.0 - beta1); b.omb2 = (float)(1.0 - beta2); b.eps = (float)eps;
+  b.coef = adam_coef(beta1, beta2, eps);
   int64_t blocks = (b.n4 + 255) / 256;
   const int64_t need = (2 * (int64_t)n_agents + 255) / 256;   // the losses have a thread each
   blocks = blocks < need ? need : blocks < 2048 ? blocks : 2048;

@@ -26,14 +26,10 @@
 #include <stdint.h>
 
 #include "pedn_actor.hpp"
-#include "pedn_actor_grad.hpp"
-#include "pedn_critic.hpp"
+#include "pedn_adam.hpp"
 #include "pedn_mlp.hpp"
 #include "pedn_mlp_grad.hpp"
 
-#define PEDN_PG_TILE PEDN_CRITIC_TILE      // rows per tile: section 18's
-#define PEDN_PG_ROWS PEDN_CRITIC_ROWS      // rows per wave
-#define PEDN_PG_DS PEDN_CRITIC_DS          // words of a row of the output gradients
 #define PEDN_PG_BLOCKS 16                  // workgroups per (agent, network) of the reduce and Adam launches: part of the norm's order
 #define PEDN_PG_SUMS 8                     // floats per agent and slab: three DOUBLES, the sums of -min(surr1, surr2), of logp - old, of (v - td)^2; 2 unused
 #define PEDN_PG_SCALARS 7                  // actor_loss, critic_loss, approx_kl, actor_norm, value_norm, actor_coef, value_coef
@@ -60,58 +56,20 @@ struct PpoGradArgs {
   float vscale;            // (float)(2.0 / rows)
 };
 
-// The gradients of one layer's weight [64][K] and bias from the tile's output gradient d (rows of PEDN_PG_DS) and its input x (rows of xs
-// words; first: the gathered chunk sXc), added to the slab's gw and gb (fresh: stored): wave w of the four takes columns 8 * w .. + 7 of
-// every chunk, wave 0 the bias first.  Thread t reads and writes the same addresses of the slab in every tile.  sG: staging rows.
-template <class Gather>
-__device__ __forceinline__ void pg_dw(const float* d, const float* x, int xs, int K, int nrows, float* gw, float* gb, float* sG, const float* sXc,
-                                      bool first, bool fresh, int t, Gather gather) {
-  const int lane = t & 63, w4 = t >> 6;
-  __syncthreads();   // d is there
-  if (w4 == 0) {
-    float b = 0.0f;
-    for (int r = 0; r < nrows; ++r) b = b + d[r * PEDN_PG_DS + lane];
-    gb[lane] = fresh ? b : gb[lane] + b;
-  }
-  for (int c0 = 0; c0 < K; c0 += PEDN_ACTOR_CHUNK) {
-    const int kmax = K - c0 < PEDN_ACTOR_CHUNK ? K - c0 : PEDN_ACTOR_CHUNK;
-    if (first) {
-      gather(c0, kmax);
-      __syncthreads();
-    }
-    float g[PEDN_PG_ROWS];
-#pragma unroll
-    for (int j = 0; j < PEDN_PG_ROWS; ++j) g[j] = 0.0f;
-    mlp_grad_dw(g, d + lane, PEDN_PG_DS, (first ? sXc : x + c0) + PEDN_PG_ROWS * w4, first ? PEDN_ACTOR_CHUNK : xs, nrows);
-#pragma unroll
-    for (int j = 0; j < PEDN_PG_ROWS; ++j) sG[lane * PEDN_GRAD_PAD + PEDN_PG_ROWS * w4 + j] = g[j];
-    __syncthreads();
-    for (int idx = t; idx < PEDN_ACTOR_HIDDEN * PEDN_ACTOR_CHUNK; idx += 256) {
-      const int o = idx / PEDN_ACTOR_CHUNK, kk = idx % PEDN_ACTOR_CHUNK;
-      if (kk < kmax) {
-        float* p = gw + (unsigned)(o * K + c0 + kk);
-        const float v = sG[o * PEDN_GRAD_PAD + kk];
-        *p = fresh ? v : *p + v;
-      }
-    }
-    __syncthreads();   // sG and the gathered chunk are free
-  }
-}
-
 typedef const __attribute__((address_space(4))) PpoGradArgs* PpoGradLate;
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void ppograd_kernel(PpoGradArgs a) {
   __shared__ float sW[PEDN_ACTOR_HIDDEN * PEDN_GRAD_PAD];
-  __shared__ __attribute__((aligned(16))) float sXc[PEDN_PG_TILE * PEDN_ACTOR_CHUNK];
-  __shared__ __attribute__((aligned(16))) float sA[PEDN_PG_TILE * PEDN_ACTOR_HIDDEN];   // h1
-  __shared__ __attribute__((aligned(16))) float sB[PEDN_PG_TILE * PEDN_ACTOR_HIDDEN];   // h2
-  __shared__ __attribute__((aligned(16))) float sC[PEDN_PG_TILE * PEDN_ACTOR_HIDDEN];   // h3 behind its ReLU
-  __shared__ __attribute__((aligned(16))) float sX[PEDN_PG_TILE * PEDN_ACTOR_HIDDEN];   // the LayerNorm's normalised rows
-  __shared__ __attribute__((aligned(16))) float sD[PEDN_PG_TILE * PEDN_PG_DS];          // the output gradient of the layer at hand
-  __shared__ float sOut[PEDN_PG_TILE * 2 * PEDN_ACTOR_MAX_ACT];                         // mu | pre-softplus of the heads
-  __shared__ float sEl[2][PEDN_PG_TILE * PEDN_ACTOR_MAX_ACT];                           // -min(surr1, surr2) and logp - old; value: v - td
-  __shared__ float sSd[PEDN_PG_TILE], sDv[PEDN_PG_TILE];                                // the LayerNorm's sqrt(var + eps); the value's gradient
-  __shared__ int32_t sT[PEDN_PG_TILE], sE[PEDN_PG_TILE];
+  __shared__ __attribute__((aligned(16))) float sXc[PEDN_GRAD_TILE * PEDN_ACTOR_CHUNK];
+  __shared__ __attribute__((aligned(16))) float sA[PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];   // h1
+  __shared__ __attribute__((aligned(16))) float sB[PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];   // h2
+  __shared__ __attribute__((aligned(16))) float sC[PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];   // h3 behind its ReLU
+  __shared__ __attribute__((aligned(16))) float sX[PEDN_GRAD_TILE * PEDN_ACTOR_HIDDEN];   // the LayerNorm's normalised rows
+  __shared__ __attribute__((aligned(16))) float sD[PEDN_GRAD_TILE * PEDN_GRAD_DS];          // the output gradient of the layer at hand
+  __shared__ float sOut[PEDN_GRAD_TILE * 2 * PEDN_ACTOR_MAX_ACT];                         // mu | pre-softplus of the heads
+  __shared__ float sEl[2][PEDN_GRAD_TILE * PEDN_ACTOR_MAX_ACT];                           // -min(surr1, surr2) and logp - old; value: v - td
+  __shared__ float sSd[PEDN_GRAD_TILE], sDv[PEDN_GRAD_TILE];                                // the LayerNorm's sqrt(var + eps); the value's gradient
+  __shared__ int32_t sT[PEDN_GRAD_TILE], sE[PEDN_GRAD_TILE];
   const int tid0 = (int)threadIdx.x;
   const int H = PEDN_ACTOR_HIDDEN;
   const int agent = (int)blockIdx.y;
@@ -130,7 +88,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     int tid = tid0;
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int vrow = (tid >> 6) * PEDN_PG_ROWS;   // the wave's first row (a vector value: the stores of its rows index with it)
+    const int vrow = (tid >> 6) * PEDN_GRAD_WAVE_ROWS;   // the wave's first row (a vector value: the stores of its rows index with it)
     const int32_t* tb = la->table + (size_t)agent * PEDN_ACTOR_TABLE_COLS;
     const int act_w = tb[3];
     const int K1 = la->S * tb[1];
@@ -148,7 +106,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
       const int S = la->S, obs0 = la->table[(size_t)agent * PEDN_ACTOR_TABLE_COLS];
       const unsigned k = (unsigned)(c0 + kk), f = k / (unsigned)S, s = k - f * (unsigned)S;
 #pragma unroll
-      for (int i = 0; i < PEDN_PG_TILE * PEDN_ACTOR_CHUNK / 256; ++i) {
+      for (int i = 0; i < PEDN_GRAD_TILE * PEDN_ACTOR_CHUNK / 256; ++i) {
         const int r = (int)(threadIdx.x >> 5) + i * (256 / PEDN_ACTOR_CHUNK);
         const int t = sT[r];
         float x = 0.0f;
@@ -161,27 +119,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
       }
     };
     const bool fresh = tile == (int)blockIdx.x;
-    const int64_t row0 = (int64_t)tile * PEDN_PG_TILE;
-    const int nrows = la->rows - row0 < PEDN_PG_TILE ? (int)(la->rows - row0) : PEDN_PG_TILE;
+    const int64_t row0 = (int64_t)tile * PEDN_GRAD_TILE;
+    const int nrows = la->rows - row0 < PEDN_GRAD_TILE ? (int)(la->rows - row0) : PEDN_GRAD_TILE;
     __syncthreads();   // the tile before is done with the LDS
-    if (tid < PEDN_PG_TILE) {
+    if (tid < PEDN_GRAD_TILE) {
       const int64_t r = row0 + (int64_t)tid;
       const int64_t tr = r / (int64_t)la->N;
       sT[tid] = r < la->rows ? (int32_t)tr : -1;
       sE[tid] = (int32_t)(r - tr * (int64_t)la->N);
     }
     // ---- forward: section 16's, with h1, h2, h3 (and the LayerNorm's rows) kept
-    float acc[PEDN_PG_ROWS];
+    float acc[PEDN_GRAD_WAVE_ROWS];
     mlp_layer(acc, net, net + H * K1, net, net + H * K1, H, H, K1, true, sW, sXc, sA, gather);
     mlp_relu_store(sA + vrow * H + lane, acc);
     mlp_layer(acc, net + at2, net + at2 + H * H, net + at2, net + at2 + H * H, H, H, Hk, false, sW, sXc, sA, gather);
     mlp_relu_store(sB + vrow * H + lane, acc);
     mlp_layer(acc, net + at3, net + at3 + H * H, net + at3, net + at3 + H * H, H, H, Hk, false, sW, sXc, sB, gather);
     if (is_actor) {
-      float xh[PEDN_PG_ROWS], sd[PEDN_PG_ROWS];
+      float xh[PEDN_GRAD_WAVE_ROWS], sd[PEDN_GRAD_WAVE_ROWS];
       mlp_layer_norm_keep(acc, xh, sd, net[at4 + lane], net[at4 + H + lane]);
 #pragma unroll
-      for (int r = 0; r < PEDN_PG_ROWS; ++r) {
+      for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) {
         sX[(vrow + r) * H + lane] = xh[r];
         if (lane == 0) sSd[vrow + r] = sd[r];
       }
@@ -195,7 +153,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
       PpoGradLate lt = la;
       asm volatile("" : "+s"(lt));
       const int lr = lane / act_w, j = lane - lr * act_w;
-      if (lr < PEDN_PG_ROWS) {
+      if (lr < PEDN_GRAD_WAVE_ROWS) {
         const int tr = vrow + lr;
         float gmu = 0.0f, gz = 0.0f, el = 0.0f, ek = 0.0f;
         if (tr < nrows) {
@@ -235,26 +193,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
             o[0] = sd; o[plane] = gmu; o[2 * plane] = gz;
           }
         }
-        sD[tr * PEDN_PG_DS + j] = gmu;
-        sD[tr * PEDN_PG_DS + act_w + j] = gz;
+        sD[tr * PEDN_GRAD_DS + j] = gmu;
+        sD[tr * PEDN_GRAD_DS + act_w + j] = gz;
         sEl[0][tr * PEDN_ACTOR_MAX_ACT + j] = el;
         sEl[1][tr * PEDN_ACTOR_MAX_ACT + j] = ek;
       }
       __syncthreads();
       // ---- the heads: a thread per weight; the tile's two sums; h3's gradient behind the ReLU mask, a lane per neuron
-      for (int idx = tid; idx < 2 * act_w * H; idx += 256) {
-        const int o = idx >> 6, k = idx & 63;
-        float v = 0.0f;
-        for (int r = 0; r < nrows; ++r) v = v + sD[r * PEDN_PG_DS + o] * sC[r * H + k];
-        float* p = gws + ah + (o < act_w ? 0 : act_w) + idx;
-        *p = fresh ? v : *p + v;
-      }
-      if (tid < 2 * act_w) {
-        float v = 0.0f;
-        for (int r = 0; r < nrows; ++r) v = v + sD[r * PEDN_PG_DS + tid];
-        float* p = gws + ah + (tid < act_w ? act_w * H + tid : 2 * act_w * H + tid);
-        *p = fresh ? v : *p + v;
-      }
+      mlp_grad_heads_tile<true>(sD, PEDN_GRAD_DS, sC, act_w, nrows, gws + ah, fresh, tid, 256);
       if (tid == 64 || tid == 128) {   // one chain over the tile's (row, action) elements, rows ascending, actions ascending within
         const int which = tid >> 7;
         // IN DOUBLE: the elements cancel (the advantages are normalised to mean 0), and as a float32 chain this sum alone carried the
@@ -265,38 +211,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
         double* p = reinterpret_cast<double*>(la->ws + (size_t)blockIdx.x * (size_t)la->ws_stride + la->apack4 + la->vpack + (int64_t)PEDN_PG_SUMS * agent) + which;
         *p = fresh ? v : *p + v;
       }
-      float dy[PEDN_PG_ROWS];
+      float dy[PEDN_GRAD_WAVE_ROWS];
 #pragma unroll
-      for (int r = 0; r < PEDN_PG_ROWS; ++r) dy[r] = 0.0f;
+      for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) dy[r] = 0.0f;
       {
         const float* hmu = net + ah;
         const float* hsd = hmu + act_w * H + act_w;
         for (int o = 0; o < 2 * act_w; ++o) {
           const float w = o < act_w ? hmu[o * H + lane] : hsd[(o - act_w) * H + lane];
 #pragma unroll
-          for (int r = 0; r < PEDN_PG_ROWS; ++r) dy[r] = dy[r] + sD[(vrow + r) * PEDN_PG_DS + o] * w;
+          for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) dy[r] = dy[r] + sD[(vrow + r) * PEDN_GRAD_DS + o] * w;
         }
       }
 #pragma unroll
-      for (int r = 0; r < PEDN_PG_ROWS; ++r) dy[r] = sC[(vrow + r) * H + lane] > 0.0f ? dy[r] : 0.0f;
+      for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) dy[r] = sC[(vrow + r) * H + lane] > 0.0f ? dy[r] : 0.0f;
       __syncthreads();   // every thread has read the heads' gradient
 #pragma unroll
-      for (int r = 0; r < PEDN_PG_ROWS; ++r) sD[(vrow + r) * PEDN_PG_DS + lane] = dy[r];
+      for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sD[(vrow + r) * PEDN_GRAD_DS + lane] = dy[r];
       __syncthreads();
       // ---- the LayerNorm: its weight (wave 0) and bias (wave 1), rows ascending; then its input's gradient, the wave's own rows
       if (wave < 2) {
         float v = 0.0f;
         if (wave == 0)
-          for (int r = 0; r < nrows; ++r) v = v + sD[r * PEDN_PG_DS + lane] * sX[r * H + lane];
+          for (int r = 0; r < nrows; ++r) v = v + sD[r * PEDN_GRAD_DS + lane] * sX[r * H + lane];
         else
-          for (int r = 0; r < nrows; ++r) v = v + sD[r * PEDN_PG_DS + lane];
+          for (int r = 0; r < nrows; ++r) v = v + sD[r * PEDN_GRAD_DS + lane];
         float* p = gws + at4 + wave * H + lane;
         *p = fresh ? v : *p + v;
       }
       {
-        float xh[PEDN_PG_ROWS], sd[PEDN_PG_ROWS];
+        float xh[PEDN_GRAD_WAVE_ROWS], sd[PEDN_GRAD_WAVE_ROWS];
 #pragma unroll
-        for (int r = 0; r < PEDN_PG_ROWS; ++r) {
+        for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) {
           xh[r] = sX[(vrow + r) * H + lane];
           sd[r] = sSd[vrow + r];
         }
@@ -304,14 +250,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
       }
       __syncthreads();   // waves 0 and 1 have read the LayerNorm's output gradient
 #pragma unroll
-      for (int r = 0; r < PEDN_PG_ROWS; ++r) sD[(vrow + r) * PEDN_PG_DS + lane] = dy[r];
+      for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sD[(vrow + r) * PEDN_GRAD_DS + lane] = dy[r];
     } else {
       // ---- value_head on a lane per row (section 16's chain), e = v - td, dv = e * (float)(2 / R)
       const float* wo = net + at4;
       PpoGradLate lv = la;
       asm volatile("" : "+s"(lv));
       __syncthreads();   // h3 is there
-      if (lane < PEDN_PG_ROWS) {
+      if (lane < PEDN_GRAD_WAVE_ROWS) {
         const int r = vrow + lane;
         float v = wo[H];
         for (int k = 0; k < H; ++k) v = v + wo[k] * sC[r * H + k];
@@ -344,21 +290,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
       {
         const float wl = wo[lane];
 #pragma unroll
-        for (int r = 0; r < PEDN_PG_ROWS; ++r) sD[(vrow + r) * PEDN_PG_DS + lane] = sC[(vrow + r) * H + lane] > 0.0f ? sDv[vrow + r] * wl : 0.0f;
+        for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sD[(vrow + r) * PEDN_GRAD_DS + lane] = sC[(vrow + r) * H + lane] > 0.0f ? sDv[vrow + r] * wl : 0.0f;
       }
     }
     // ---- fc, the mask, encoder.fc2, the mask, encoder.fc1: section 18's pieces
-    pg_dw(sD, sB, H, Hk, nrows, gws + at3, gws + at3 + H * H, sW, sXc, false, fresh, tid, gather);
-    critic_dx(acc, sD, net + at3, H, sW, tid);
+    mlp_grad_dw_tile<8, true>(sD, PEDN_GRAD_DS, sB, H, Hk, nrows, gws + at3, gws + at3 + H * H, sW, false, fresh, true, 0, tid, 256, gather);
+    mlp_grad_dx_tile(acc, true, sD + vrow * PEDN_GRAD_DS, PEDN_GRAD_DS, net + at3, H, sW, tid, 256);
     __syncthreads();   // every wave has read the output gradient that is overwritten now
 #pragma unroll
-    for (int r = 0; r < PEDN_PG_ROWS; ++r) sD[(vrow + r) * PEDN_PG_DS + lane] = sB[(vrow + r) * H + lane] > 0.0f ? acc[r] : 0.0f;
-    pg_dw(sD, sA, H, Hk, nrows, gws + at2, gws + at2 + H * H, sW, sXc, false, fresh, tid, gather);
-    critic_dx(acc, sD, net + at2, H, sW, tid);
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sD[(vrow + r) * PEDN_GRAD_DS + lane] = sB[(vrow + r) * H + lane] > 0.0f ? acc[r] : 0.0f;
+    mlp_grad_dw_tile<8, true>(sD, PEDN_GRAD_DS, sA, H, Hk, nrows, gws + at2, gws + at2 + H * H, sW, false, fresh, true, 0, tid, 256, gather);
+    mlp_grad_dx_tile(acc, true, sD + vrow * PEDN_GRAD_DS, PEDN_GRAD_DS, net + at2, H, sW, tid, 256);
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < PEDN_PG_ROWS; ++r) sD[(vrow + r) * PEDN_PG_DS + lane] = sA[(vrow + r) * H + lane] > 0.0f ? acc[r] : 0.0f;
-    pg_dw(sD, sXc, PEDN_ACTOR_CHUNK, K1, nrows, gws, gws + H * K1, sW, sXc, true, fresh, tid, gather);
+    for (int r = 0; r < PEDN_GRAD_WAVE_ROWS; ++r) sD[(vrow + r) * PEDN_GRAD_DS + lane] = sA[(vrow + r) * H + lane] > 0.0f ? acc[r] : 0.0f;
+    mlp_grad_dw_tile<8, true>(sD, PEDN_GRAD_DS, sXc, PEDN_ACTOR_CHUNK, K1, nrows, gws, gws + H * K1, sW, true, fresh, true, 0, tid, 256, gather);
   }
 }
 
@@ -436,11 +382,11 @@ struct PpoAdamArgs {
   const double* parts;
   float *g_a, *g_v, *m_a, *m_v, *v_a, *v_v, *p_a, *p_v;   // per network: the clipped gradients, exp_avg, exp_avg_sq, the parameters
   float* scalars;
-  int64_t* state;          // [n_agents][4]: the step count, the ticket (its low 32 bits), the doubles beta1^t and beta2^t
+  int64_t* state;          // [n_agents][4]: pedn_adam.hpp's step state of every agent
   int32_t S, n_agents, do_adam;
   float max_norm;
   double lr_a, lr_v, beta1, beta2, kl_stop;   // kl_stop = 1.5 * kl_tolerance
-  float b2, omb1, omb2, eps;
+  AdamCoef coef;
 };
 
 __global__ __launch_bounds__(256) void ppograd_adam_kernel(PpoAdamArgs a) {
@@ -450,10 +396,8 @@ __global__ __launch_bounds__(256) void ppograd_adam_kernel(PpoAdamArgs a) {
   int off, len;
   pg_net_range(a.table, a.vtable, agent, is_actor, a.S, off, len);
   int64_t* st = a.state + 4 * (size_t)agent;
-  const int64_t steps = st[0];
-  const double* pw = reinterpret_cast<const double*>(st + 2);
-  const double b1t = pw[0] * a.beta1, b2t = pw[1] * a.beta2;   // the products behind this step
-  const float nstep = -(float)((is_actor ? a.lr_a : a.lr_v) / (1.0 - b1t)), s = (float)sqrt(1.0 - b2t);
+  const AdamStep step = adam_step_begin(st, a.beta1, a.beta2);
+  const float nstep = adam_nstep(is_actor ? a.lr_a : a.lr_v, step), s = step.s;
   // clip_grad_norm_: total_norm over the network's tensors, coef = min(max_norm / (total_norm + 1e-6), 1), g = g * coef
   const double* parts = a.parts + ((size_t)agent * 2 + (is_actor ? 1 : 0)) * PEDN_PG_BLOCKS;
   double total = 0.0;
@@ -466,14 +410,12 @@ __global__ __launch_bounds__(256) void ppograd_adam_kernel(PpoAdamArgs a) {
   float* mm = (is_actor ? a.m_a : a.m_v) + off;
   float* vv = (is_actor ? a.v_a : a.v_v) + off;
   float* pp = (is_actor ? a.p_a : a.p_v) + off;
-  ActorAdamArgs one{};   // section 19's step, written once: actor_adam_one reads these four
-  one.b2 = a.b2; one.omb1 = a.omb1; one.omb2 = a.omb2; one.eps = a.eps;
   for (int i = (int)blockIdx.x * 256 + tid; i < len; i += (int)gridDim.x * 256) {
     const float g = raw[i] * coef;
     gr[i] = g;
     if (a.do_adam) {
       float m = mm[i], v = vv[i];
-      const float p = actor_adam_one(g, m, v, pp[i], one, nstep, s);
+      const float p = adam_one<true>(g, m, v, pp[i], a.coef, nstep, s);
       mm[i] = m; vv[i] = v; pp[i] = p;
     }
   }
@@ -483,18 +425,10 @@ __global__ __launch_bounds__(256) void ppograd_adam_kernel(PpoAdamArgs a) {
   }
   if (!a.do_adam) return;
   __syncthreads();   // every wave of the workgroup has read the flag and the step state
-  if (tid == 0) {
-    unsigned* ticket = reinterpret_cast<unsigned*>(st + 1);
-    const unsigned mine = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (mine + 1u == 2u * gridDim.x) {   // the last workgroup of the agent's two networks: nobody reads its state any more
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(st, steps + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(st + 2, (int64_t)__double_as_longlong(b1t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(st + 3, (int64_t)__double_as_longlong(b2t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // the reference's early stop: behind the step of an epoch whose approx_kl > 1.5 * kl_tolerance (this epoch's reduce launch wrote it)
-      if ((double)a.scalars[2 * a.n_agents + agent] > a.kl_stop) __hip_atomic_store(a.flags + agent, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  // the last workgroup of the agent's two networks advances its state and takes the reference's early stop: behind the step of an epoch
+  // whose approx_kl > 1.5 * kl_tolerance (this epoch's reduce launch wrote it)
+  if (tid == 0 && adam_step_advance(st, step, 2u * gridDim.x) && (double)a.scalars[2 * a.n_agents + agent] > a.kl_stop)
+    __hip_atomic_store(a.flags + agent, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // stop_flags[0 .. n) = 0: a launch like the others, so that a captured update is one chain of kernel nodes
@@ -525,26 +459,24 @@ int pedn_ppo_epoch_update(const float* obs, const void* actions, const float* ol
       !actor_grads || !value_grads || !actor_raw_grads || !value_raw_grads || !actor_exp_avg || !value_exp_avg || !actor_exp_avg_sq ||
       !value_exp_avg_sq || !workspace || !norm_parts || !log_probs || !values || !scalars || !adam_state || !stop_flags)
     return fail(nullptr, PEDN_E_ARG, "null argument");
-  if (hidden_size != PEDN_ACTOR_HIDDEN) return fail(nullptr, PEDN_E_ARG, "the PPO update kernels are built for hidden_size 64");
-  if (T < 1 || N < 1 || stack_size < 1 || n_obs < 1 || n_actions < 1 || n_agents < 1 || n_agents > 65535)
-    return fail(nullptr, PEDN_E_ARG, "T, N, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)");
-  if (actions_f64 < 0 || actions_f64 > 1) return fail(nullptr, PEDN_E_ARG, "the actions' dtype flag is 0 (float32) or 1 (float64)");
-  if (groups < 1 || groups > 65535) return fail(nullptr, PEDN_E_ARG, "groups must be in 1 .. 65535");
-  if (actor_pack_floats < 1 || value_pack_floats < 4 || value_pack_floats % 4)
-    return fail(nullptr, PEDN_E_ARG, "the actors' pack is empty or the value pack's length is no positive multiple of 4 floats");
-  if (((uintptr_t)actor_params | (uintptr_t)value_params | (uintptr_t)actor_grads | (uintptr_t)value_grads | (uintptr_t)actor_raw_grads |
-       (uintptr_t)value_raw_grads | (uintptr_t)actor_exp_avg | (uintptr_t)value_exp_avg | (uintptr_t)actor_exp_avg_sq |
-       (uintptr_t)value_exp_avg_sq | (uintptr_t)workspace) & 15)
-    return fail(nullptr, PEDN_E_ARG, "the packs and the workspace must be 16-byte aligned");
-  if (!(actor_lr >= 0.0 && actor_lr < INFINITY && critic_lr >= 0.0 && critic_lr < INFINITY))
-    return fail(nullptr, PEDN_E_ARG, "lr must be finite and not negative");
-  if (!(eps >= 0.0 && eps < INFINITY)) return fail(nullptr, PEDN_E_ARG, "eps must be finite and not negative");
-  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return fail(nullptr, PEDN_E_ARG, "the betas must be in [0, 1)");
+  if (const char* why = update_refusal(
+          hidden_size, "the PPO update kernels are built for hidden_size 64", T >= 1 && N >= 1 && stack_size >= 1 && n_obs >= 1 && n_actions >= 1,
+          n_agents, "T, N, stack_size, n_obs, n_actions and n_agents must be positive (at most 65535 agents)",
+          actions_f64 < 0 || actions_f64 > 1 ? "the actions' dtype flag is 0 (float32) or 1 (float64)"
+          : groups < 1 || groups > 65535  ? "groups must be in 1 .. 65535"
+                                          : nullptr,
+          actor_pack_floats >= 1 && value_pack_floats >= 4 && value_pack_floats % 4 == 0,
+          "the actors' pack is empty or the value pack's length is no positive multiple of 4 floats",
+          (uintptr_t)actor_params | (uintptr_t)value_params | (uintptr_t)actor_grads | (uintptr_t)value_grads | (uintptr_t)actor_raw_grads |
+              (uintptr_t)value_raw_grads | (uintptr_t)actor_exp_avg | (uintptr_t)value_exp_avg | (uintptr_t)actor_exp_avg_sq |
+              (uintptr_t)value_exp_avg_sq | (uintptr_t)workspace,
+          actor_lr, critic_lr, beta1, beta2, eps))
+    return fail(nullptr, PEDN_E_ARG, why);
   if (!(clip_eps > 0.0 && clip_eps < INFINITY)) return fail(nullptr, PEDN_E_ARG, "clip_eps must be finite and positive");
   if (!(max_grad_norm > 0.0 && max_grad_norm < INFINITY)) return fail(nullptr, PEDN_E_ARG, "max_grad_norm must be finite and positive");
   if (kl_tolerance != kl_tolerance) return fail(nullptr, PEDN_E_ARG, "kl_tolerance must not be NaN");
   const int64_t rows = (int64_t)T * (int64_t)N;
-  const int64_t tiles = (rows + PEDN_PG_TILE - 1) / PEDN_PG_TILE;
+  const int64_t tiles = (rows + PEDN_GRAD_TILE - 1) / PEDN_GRAD_TILE;
   if (tiles > 0x7fffffffLL) return fail(nullptr, PEDN_E_ARG, "T * N is beyond 2^31 - 1 tiles of 32 rows");
   const int G = (int)(tiles < (int64_t)groups ? tiles : (int64_t)groups);
   const int64_t apack4 = (actor_pack_floats + 3) / 4 * 4;
@@ -570,7 +502,7 @@ int pedn_ppo_epoch_update(const float* obs, const void* actions, const float* ol
   c.p_a = actor_params; c.p_v = value_params; c.scalars = scalars; c.state = adam_state;
   c.S = stack_size; c.n_agents = n_agents; c.do_adam = do_adam ? 1 : 0; c.max_norm = (float)max_grad_norm;
   c.lr_a = actor_lr; c.lr_v = critic_lr; c.beta1 = beta1; c.beta2 = beta2; c.kl_stop = 1.5 * kl_tolerance;
-  c.b2 = (float)beta2; c.omb1 = (float)(1.0 - beta1); c.omb2 = (float)(1.0 - beta2); c.eps = (float)eps;
+  c.coef = adam_coef(beta1, beta2, eps);
   hipLaunchKernelGGL(ppograd_adam_kernel, dim3(PEDN_PG_BLOCKS, (unsigned)n_agents, 2u), dim3(256), 0, (hipStream_t)stream, c);
   HIP_TRY(nullptr, hipGetLastError());
   return PEDN_OK;

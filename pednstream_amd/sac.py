@@ -40,7 +40,7 @@ AGENT_OUTPUTS = ("entropy", "q1", "q2", "td_target")
 ACTOR_ACTION_OUTPUTS = ("mu", "std", "eps", "logp", "new_actions", "z", "t", "d_mu", "d_z")      # z: the pre-softplus value; t = tanh(mu + std * eps); d_*: the loss' gradients
 ACTOR_AGENT_OUTPUTS = ("entropy", "q1", "q2")
 TILE = 8                        # rows per workgroup of sac_target_kernel (PEDN_SAC_TILE)
-CRITIC_TILE = 32                # rows per workgroup of critic_grad_kernel (PEDN_CRITIC_TILE): part of section 18's order of sums
+CRITIC_TILE = 32                # rows per workgroup of critic_grad_kernel (PEDN_GRAD_TILE): part of section 18's order of sums
 ADAM_STATE_INIT = (0, 0, 0x3FF0000000000000, 0x3FF0000000000000)      # the step count, the ticket, the doubles beta1^0 and beta2^0
 
 
