@@ -766,6 +766,32 @@ int pedn_draw_demand(pedn_sim* sim, int32_t node, uint64_t seed, const int32_t* 
  * with chunks of `seed` doubles visited in a scrambled order (n and seed powers of two). */
 int pedn_device_math(int32_t device, int32_t op, int32_t n, const double* a, const double* b, uint64_t seed, double* out);
 
+/* ---- one epoch of PPO's clipped-loss update of the recurrent agents (rl/agents/PPO_org.py:579-629 with use_stacked_obs=False) -------------
+ * Handle-free, on plain device pointers; the arithmetic contract is DESIGN section 21 (tests/lstm_update_model.py restates it in numpy).
+ *   obs, actions, table, value_table, actor_params, value_params, min_std, max_std   as for pedn_lstm_ppo_evaluate; both packs are stepped
+ *                in place.  Env e is one sequence obs[0 .. T - 1][e] from a zero state; done flags inside it do not reset the state
+ *   old_log_probs, advantages, td_target, *_grads, *_raw_grads, *_exp_avg, *_exp_avg_sq, workspace, norm_parts, log_probs, values, scalars,
+ *   adam_state, stop_flags, groups and the hyper-parameters   as for pedn_ppo_epoch_update, with the recurrent networks' packs
+ *   activations  f32 [2][n_agents][T * N][384], 16-byte aligned: per network (0 the value networks, 1 the actors), agent and row r = t * N + e
+ *                the forward's h', c' and activated gates i, f, g, o (64 each); the backward overwrites the gates with the pre-activation
+ *                gradients a_i, a_f, a_g, a_o.  Need not be zeroed
+ *   tail         f32 [4][T][N][n_actions]: std, the actor loss' gradients by mu and by the pre-softplus value, and -min(surr1, surr2)
+ * Five launches on `stream`: every env's sequence forward through time, then backward (each a workgroup per 32 envs, agent and network),
+ * the weight gradients over tiles of 32 rows into the groups' slabs, their sum with the losses and the norms' parts, then clip_grad_norm_
+ * and, if do_adam is not 0, one torch.optim.Adam step of each network.  hidden_size must be 64 and num_layers 1.  No allocation, no
+ * synchronisation, constant arguments: safe under stream capture. */
+int pedn_lstm_ppo_epoch_update(const float* obs, const void* actions, const float* old_log_probs, const float* advantages, const float* td_target,
+                               const int32_t* table, const int32_t* value_table, float* actor_params, float* value_params, float* actor_grads,
+                               float* value_grads, float* actor_raw_grads, float* value_raw_grads, float* actor_exp_avg, float* value_exp_avg,
+                               float* actor_exp_avg_sq, float* value_exp_avg_sq, float* workspace, float* activations, float* tail,
+                               double* norm_parts, float* log_probs, float* values, float* scalars, int64_t* adam_state, int32_t* stop_flags,
+                               int64_t actor_pack_floats, int64_t value_pack_floats, int32_t T, int32_t N, int32_t n_obs, int32_t n_actions,
+                               int32_t n_agents, int32_t hidden_size, int32_t num_layers, int32_t actions_f64, int32_t groups, double min_std,
+                               double max_std, double actor_lr, double critic_lr, double clip_eps, double max_grad_norm, double kl_tolerance,
+                               double beta1, double beta2, double eps, int32_t do_adam, void* stream);
+/* stop_flags[0 .. n_agents) = 0, one small launch on `stream`: capturable. */
+int pedn_lstm_ppo_begin_update(int32_t* stop_flags, int32_t n_agents, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
 #include "pedn_ppo.hpp"
 #include "pedn_ppo_grad.hpp"
 #include "pedn_lstm.hpp"
+#include "pedn_lstm_grad.hpp"
 #include "pedn_metrics.hpp"
 
 // The first launch on a stream and the first cross-stream wait cost the runtime ~0.2 ms (queue creation, signal set-up): pay

@@ -94,9 +94,11 @@ __device__ __forceinline__ void lstm_gates(float (&acc)[PEDN_LSTM_GATES][PEDN_AC
 }
 
 // c' = f * c + i * g, h' = o * tanh(c') of this lane's unit in the wave's rows.  c is updated in place, h' goes to hs (the state row in
-// LDS, only the row's own wave touches it) and relu(h') to hr (what the heads read).
-__device__ __forceinline__ void lstm_cell(const float (&acc)[PEDN_LSTM_GATES][PEDN_ACTOR_WAVE_ENVS], float (&c)[PEDN_ACTOR_WAVE_ENVS],
-                                          float* hs, float* hr) {
+// LDS, only the row's own wave touches it) and relu(h') to hr (what the heads read).  keep(r, i, f, g, o, c', h') is handed row r's
+// activated gates and new state: the update's forward stores them (pedn_lstm_grad.hpp).
+template <class Keep>
+__device__ __forceinline__ void lstm_cell_keep(const float (&acc)[PEDN_LSTM_GATES][PEDN_ACTOR_WAVE_ENVS], float (&c)[PEDN_ACTOR_WAVE_ENVS],
+                                               float* hs, float* hr, Keep keep) {
 #pragma unroll
   for (int r = 0; r < PEDN_ACTOR_WAVE_ENVS; ++r) {
     const float i = lstm_sigmoid(acc[0][r]), f = lstm_sigmoid(acc[1][r]), g = lstm_tanh(acc[2][r]), o = lstm_sigmoid(acc[3][r]);
@@ -105,7 +107,13 @@ __device__ __forceinline__ void lstm_cell(const float (&acc)[PEDN_LSTM_GATES][PE
     const float h = o * lstm_tanh(c[r]);
     hs[r * PEDN_ACTOR_HIDDEN] = h;
     hr[r * PEDN_ACTOR_HIDDEN] = h < 0.0f ? 0.0f : h;
+    keep(r, i, f, g, o, c[r], h);
   }
+}
+
+__device__ __forceinline__ void lstm_cell(const float (&acc)[PEDN_LSTM_GATES][PEDN_ACTOR_WAVE_ENVS], float (&c)[PEDN_ACTOR_WAVE_ENVS],
+                                          float* hs, float* hr) {
+  lstm_cell_keep(acc, c, hs, hr, [](int, float, float, float, float, float, float) {});
 }
 
 struct LstmActorArgs {

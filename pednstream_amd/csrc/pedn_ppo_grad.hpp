@@ -29,10 +29,7 @@
 #include "pedn_adam.hpp"
 #include "pedn_mlp.hpp"
 #include "pedn_mlp_grad.hpp"
-
-#define PEDN_PG_BLOCKS 16                  // workgroups per (agent, network) of the reduce and Adam launches: part of the norm's order
-#define PEDN_PG_SUMS 8                     // floats per agent and slab: three DOUBLES, the sums of -min(surr1, surr2), of logp - old, of (v - td)^2; 2 unused
-#define PEDN_PG_SCALARS 7                  // actor_loss, critic_loss, approx_kl, actor_norm, value_norm, actor_coef, value_coef
+#include "pedn_ppo_loss.hpp"   // the loss' tail and the reduce and Adam launches' bodies, shared with pedn_lstm_grad.hpp
 
 struct PpoGradArgs {
   const float* obs;        // [T + 1][N][n_obs]
@@ -160,33 +157,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
           const int64_t row = row0 + tr;
           const float mu = so[lr * 2 * PEDN_ACTOR_MAX_ACT + j], z = so[lr * 2 * PEDN_ACTOR_MAX_ACT + PEDN_ACTOR_MAX_ACT + j];
           const size_t at = (size_t)row * (size_t)lt->n_actions + (size_t)(lt->table[(size_t)agent * PEDN_ACTOR_TABLE_COLS + 2] + j);
-          const float sp = mlp_softplus(z);
-          const float sd = actor_clip(sp, lt->min_std, lt->max_std);
           const float act = lt->act_f64 ? (float)static_cast<const double*>(lt->actions)[at] : static_cast<const float*>(lt->actions)[at];
-          const float lp = (float)normal_log_prob(act, mu, sd);
           const float old = lt->old_logp[at], A = lt->adv[(size_t)row * (size_t)lt->n_agents + (size_t)agent];
-          lt->logp[at] = lp;
-          const float dl = lp - old;
-          const float lrc = dl < -20.0f ? -20.0f : (dl > 20.0f ? 20.0f : dl);
-          const float ratio = (float)exp((double)lrc);
-          const float rc = ratio < lt->clip_lo ? lt->clip_lo : (ratio > lt->clip_hi ? lt->clip_hi : ratio);
-          const float s1 = ratio * A, s2 = rc * A;
-          el = -((s2 < s1 || s2 != s2) ? s2 : s1);   // torch.min: NaN wins
-          ek = dl;
-          // torch.minimum's backward: the smaller one takes the gradient, equal ones half each (inside the range the two halves add up);
-          // clamp passes inside and on its bounds
-          const double w1 = s1 > s2 ? 0.0 : (s1 == s2 ? 0.5 : 1.0), w2 = s1 < s2 ? 0.0 : (s1 == s2 ? 0.5 : 1.0);
-          const double G = -1.0 / ((double)lt->rows * (double)act_w);
-          const double pr = (ratio >= lt->clip_lo && ratio <= lt->clip_hi) ? 1.0 : 0.0;
-          const double pl = (dl >= -20.0f && dl <= 20.0f) ? 1.0 : 0.0;
-          const double dlp = (G * (double)A * (w1 + w2 * pr)) * (double)ratio * pl;
-          const double dm = (double)act - (double)mu, S = (double)sd;
-          gmu = (float)(dlp * dm / (S * S));
-          __builtin_amdgcn_sched_barrier(0);   // (one double-precision quotient chain at a time, section 19's remedy: interleaved, their temporaries cost registers)
-          const double gsd = dlp * (dm * dm / (S * S * S) - 1.0 / S);
-          const double ps = (sp >= lt->min_std && sp <= lt->max_std) ? 1.0 : 0.0;
-          const double sg = z > 20.0f ? 1.0 : 1.0 / (1.0 + exp(-(double)z));
-          gz = (float)(gsd * ps * sg);
+          const PpoTailElem te = ppo_loss_tail(mu, z, act, old, A, lt->min_std, lt->max_std, lt->clip_lo, lt->clip_hi,
+                                               -1.0 / ((double)lt->rows * (double)act_w));
+          lt->logp[at] = te.lp;
+          gmu = te.gmu; gz = te.gz; el = te.el; ek = te.ek;
+          const float sd = te.sd;
           if (lt->tail) {
             const size_t plane = (size_t)lt->rows * (size_t)lt->n_actions;
             float* o = lt->tail + at;
@@ -316,119 +293,21 @@ __device__ __forceinline__ void pg_net_range(const int32_t* table, const int32_t
   len = is_actor ? trunk + 2 * H + 2 * (tb[3] * H + tb[3]) : trunk + H + 1;
 }
 
-struct PpoReduceArgs {
-  const float* ws;
-  const int32_t* table;
-  const int32_t* vtable;
-  const int32_t* flags;
-  float* raw_a;            // the unclipped gradient packs
-  float* raw_v;
-  double* parts;           // [n_agents][2][PEDN_PG_BLOCKS]: the workgroups' parts of sum g^2
-  float* scalars;          // [PEDN_PG_SCALARS][n_agents]
-  int64_t rows, apack4, vpack, ws_stride;
-  int32_t G, S, n_agents;
-};
-
 __global__ __launch_bounds__(256) void ppograd_reduce_kernel(PpoReduceArgs a) {
   __shared__ double sRed[256];
-  const int tid = (int)threadIdx.x, agent = (int)blockIdx.y;
+  const int agent = (int)blockIdx.y;
   if (a.flags[agent] != 0) return;
-  const bool is_actor = blockIdx.z != 0;
   int off, len;
-  pg_net_range(a.table, a.vtable, agent, is_actor, a.S, off, len);
-  const float* src = a.ws + (is_actor ? (int64_t)off : a.apack4 + (int64_t)off);
-  float* raw = (is_actor ? a.raw_a : a.raw_v) + off;
-  double sq = 0.0;
-  for (int i = (int)blockIdx.x * 256 + tid; i < len; i += PEDN_PG_BLOCKS * 256) {
-    float g = 0.0f;
-    for (int s = 0; s < a.G; ++s) g = g + src[(int64_t)s * a.ws_stride + i];   // slabs ascending
-    raw[i] = g;
-    sq = sq + (double)g * (double)g;
-  }
-  sRed[tid] = sq;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) sRed[tid] = sRed[tid] + sRed[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) a.parts[((size_t)agent * 2 + (is_actor ? 1 : 0)) * PEDN_PG_BLOCKS + blockIdx.x] = sRed[0];
-  if (blockIdx.x == 0 && tid == 0) {
-    // the three sums are doubles: slabs ascending from +0.0, the mean in double, rounded once
-    const float* sums = a.ws + a.apack4 + a.vpack + (int64_t)PEDN_PG_SUMS * agent;
-    if (is_actor) {
-      double l = 0.0, k = 0.0;
-      for (int s = 0; s < a.G; ++s) {
-        const double* d = reinterpret_cast<const double*>(sums + (int64_t)s * a.ws_stride);
-        l = l + d[0];
-        k = k + d[1];
-      }
-      const double cnt = (double)a.rows * (double)a.table[(size_t)agent * PEDN_ACTOR_TABLE_COLS + 3];
-      a.scalars[agent] = (float)(l / cnt);
-      a.scalars[2 * a.n_agents + agent] = (float)(k / cnt);
-    } else {
-      double q = 0.0;
-      for (int s = 0; s < a.G; ++s) q = q + reinterpret_cast<const double*>(sums + (int64_t)s * a.ws_stride)[2];
-      a.scalars[a.n_agents + agent] = (float)(q / (double)a.rows);
-    }
-  }
+  pg_net_range(a.table, a.vtable, agent, blockIdx.z != 0, a.S, off, len);
+  pg_reduce_body(a, off, len, sRed);
 }
 
-struct PpoAdamArgs {
-  const int32_t* table;
-  const int32_t* vtable;
-  int32_t* flags;
-  const float* raw_a;
-  const float* raw_v;
-  const double* parts;
-  float *g_a, *g_v, *m_a, *m_v, *v_a, *v_v, *p_a, *p_v;   // per network: the clipped gradients, exp_avg, exp_avg_sq, the parameters
-  float* scalars;
-  int64_t* state;          // [n_agents][4]: pedn_adam.hpp's step state of every agent
-  int32_t S, n_agents, do_adam;
-  float max_norm;
-  double lr_a, lr_v, beta1, beta2, kl_stop;   // kl_stop = 1.5 * kl_tolerance
-  AdamCoef coef;
-};
-
 __global__ __launch_bounds__(256) void ppograd_adam_kernel(PpoAdamArgs a) {
-  const int tid = (int)threadIdx.x, agent = (int)blockIdx.y;
+  const int agent = (int)blockIdx.y;
   if (a.flags[agent] != 0) return;
-  const bool is_actor = blockIdx.z != 0;
   int off, len;
-  pg_net_range(a.table, a.vtable, agent, is_actor, a.S, off, len);
-  int64_t* st = a.state + 4 * (size_t)agent;
-  const AdamStep step = adam_step_begin(st, a.beta1, a.beta2);
-  const float nstep = adam_nstep(is_actor ? a.lr_a : a.lr_v, step), s = step.s;
-  // clip_grad_norm_: total_norm over the network's tensors, coef = min(max_norm / (total_norm + 1e-6), 1), g = g * coef
-  const double* parts = a.parts + ((size_t)agent * 2 + (is_actor ? 1 : 0)) * PEDN_PG_BLOCKS;
-  double total = 0.0;
-  for (int b = 0; b < PEDN_PG_BLOCKS; ++b) total = total + parts[b];
-  const float norm = (float)sqrt(total);
-  float coef = a.max_norm / (norm + 1e-6f);
-  coef = coef > 1.0f ? 1.0f : coef;   // (NaN stays, as torch's clamp leaves it)
-  const float* raw = (is_actor ? a.raw_a : a.raw_v) + off;
-  float* gr = (is_actor ? a.g_a : a.g_v) + off;
-  float* mm = (is_actor ? a.m_a : a.m_v) + off;
-  float* vv = (is_actor ? a.v_a : a.v_v) + off;
-  float* pp = (is_actor ? a.p_a : a.p_v) + off;
-  for (int i = (int)blockIdx.x * 256 + tid; i < len; i += (int)gridDim.x * 256) {
-    const float g = raw[i] * coef;
-    gr[i] = g;
-    if (a.do_adam) {
-      float m = mm[i], v = vv[i];
-      const float p = adam_one<true>(g, m, v, pp[i], a.coef, nstep, s);
-      mm[i] = m; vv[i] = v; pp[i] = p;
-    }
-  }
-  if (blockIdx.x == 0 && tid == 0) {
-    a.scalars[(3 + (is_actor ? 0 : 1)) * a.n_agents + agent] = norm;
-    a.scalars[(5 + (is_actor ? 0 : 1)) * a.n_agents + agent] = coef;
-  }
-  if (!a.do_adam) return;
-  __syncthreads();   // every wave of the workgroup has read the flag and the step state
-  // the last workgroup of the agent's two networks advances its state and takes the reference's early stop: behind the step of an epoch
-  // whose approx_kl > 1.5 * kl_tolerance (this epoch's reduce launch wrote it)
-  if (tid == 0 && adam_step_advance(st, step, 2u * gridDim.x) && (double)a.scalars[2 * a.n_agents + agent] > a.kl_stop)
-    __hip_atomic_store(a.flags + agent, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  pg_net_range(a.table, a.vtable, agent, blockIdx.z != 0, a.S, off, len);
+  pg_adam_body(a, off, len);
 }
 
 // stop_flags[0 .. n) = 0: a launch like the others, so that a captured update is one chain of kernel nodes

@@ -219,6 +219,8 @@ def _load():
         "pedn_lstm_ppo_evaluate": (C.c_int, [C.c_void_p] * 11 + [C.c_int32] * 8 + [C.c_double] * 2 + [C.c_void_p]),
         "pedn_ppo_epoch_update": (C.c_int, [C.c_void_p] * 25 + [C.c_int64] * 2 + [C.c_int32] * 9 + [C.c_double] * 10 + [C.c_int32, C.c_void_p]),
         "pedn_ppo_begin_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+        "pedn_lstm_ppo_epoch_update": (C.c_int, [C.c_void_p] * 26 + [C.c_int64] * 2 + [C.c_int32] * 9 + [C.c_double] * 10 + [C.c_int32, C.c_void_p]),
+        "pedn_lstm_ppo_begin_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     }
     # the version first: a stale or alternate library (PEDN_HIP_LIB) must fail with this message, not with an AttributeError on a symbol
     lib.pedn_abi_version.restype, lib.pedn_abi_version.argtypes = C.c_int, []
@@ -257,6 +259,7 @@ EXPORTS = ["pedn_abi_version", "pedn_last_error", "pedn_create", "pedn_destroy",
            "pedn_replay_configure", "pedn_replay_free", "pedn_replay_begin", "pedn_replay_push", "pedn_replay_sample", "pedn_replay_size",
            "pedn_replay_device_ptr", "pedn_actor_forward", "pedn_sac_td_target", "pedn_sac_soft_update", "pedn_ppo_evaluate",
            "pedn_gae_next", "pedn_lstm_actor_forward", "pedn_lstm_reset", "pedn_lstm_ppo_evaluate", "pedn_sac_critic_update", "pedn_sac_actor_update",
+           "pedn_lstm_ppo_epoch_update", "pedn_lstm_ppo_begin_update",      # (the header's last two; the list is a set of names)
            "pedn_ppo_epoch_update", "pedn_ppo_begin_update"]
 
 

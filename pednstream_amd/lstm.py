@@ -15,9 +15,13 @@ tests/lstm_model.py restates it in numpy.
     store.finish()
     res = ppo.evaluate_store(store)                                 # values, next_values, old_log_probs
     adv, td_target = ppo.compute_gae(store, res["values"], res["next_values"], 0.99, 0.95)
-    ...                                                             # the normalisation line and the epochs in torch, on the bound modules
+    adv = (adv - adv.mean()) / (adv.std() + 1e-8)                   # the reference's normalisation line stays the caller's
+    ppo.update_store(store, res["old_log_probs"], adv, td_target, epochs=10)   # the clipped-loss epochs, in place in both packs
 
-``LstmActors`` is the constructor on plain numbers (no env).  Backward passes and the optimisers stay in torch.
+``LstmActors`` is the constructor on plain numbers (no env).  The epochs run on the device too (``epoch_update``, ``update_store``: both
+forwards over every env's whole sequence, back-propagation through time, ``clip_grad_norm_``, both Adam steps and the KL early stop of
+every agent in five launches per epoch, pednstream_amd/csrc/pedn_lstm_grad.hpp, DESIGN section 21, tests/lstm_update_model.py); torch
+modules bound to the packs see the steps and can still run the epochs themselves.
 """
 import ctypes as C
 
@@ -26,6 +30,10 @@ import numpy as np
 from . import engine as _engine
 from . import packs
 from .policy import HIDDEN, MAX_ACT_W, MODES          # (the agent table and the modes are the stacked actors')
+from .ppo import TILE, EpochUpdates
+
+ROW_FLOATS = 6 * HIDDEN         # of the epochs' activations per (network, agent, row): h', c' and the gates i, f, g, o (PEDN_LG_ROW)
+TAIL_PLANES = 4                 # std, d_mu, d_z, -min(surr1, surr2) per (row, action) (PEDN_LG_TAIL)
 
 GATE_ROWS = 4 * HIDDEN          # i, f, g, o
 
@@ -273,9 +281,11 @@ class LstmActors:
         return int(self._device()["state"][0].item())
 
 
-class LstmPpoTargets:
-    """``actors``: a ``LstmActors``; the agent table, ``min_std`` / ``max_std`` and the device are its.  The actors' pack is read in place;
-    the value networks live in a pack of their own."""
+class LstmPpoTargets(EpochUpdates):
+    """``actors``: a ``LstmActors``; the agent table, ``min_std`` / ``max_std`` and the device are its.  The actors' pack is read in place
+    (and stepped in place by the epochs); the value networks live in a pack of their own."""
+
+    _BEGIN = "pedn_lstm_ppo_begin_update"
 
     def __init__(self, actors):
         if not isinstance(actors, LstmActors):
@@ -288,6 +298,9 @@ class LstmPpoTargets:
         self._loaded = set()
         self._dev = None                # the device tensors, allocated once (a captured graph owns their addresses)
         self._out = {}                  # (T, N) -> dict of output tensors
+        self._udev = None               # the epochs' gradient packs, Adam state and flags
+        self._uout = {}                 # (T, N, groups) -> the epochs' workspace and outputs
+        self._ulast = None
 
     # ------------------------------------------------------------------------------------------------ parameters
     def _index(self, agent_id):
@@ -334,10 +347,7 @@ class LstmPpoTargets:
         T, N = int(obs.shape[0]) - 1, int(obs.shape[1])
         packs.check_tensor("obs", obs, self.device, (T + 1, N, self.n_obs))
         packs.check_tensor("actions", actions, self.device, (T, N, self.n_actions), (torch.float32, torch.float64))
-        self.actors._missing()
-        missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self._loaded]
-        if missing:
-            raise ValueError(f"no value networks were loaded for {missing}: load_state_dict() or bind() first")
+        self._check_loaded()
         d = self._device()
         out = self._out.setdefault((T, N), {})
         dev = torch.device("cuda", self.device)
@@ -395,6 +405,81 @@ class LstmPpoTargets:
         packs.check_tensor("next_values", next_values, self.device, shape)
         dones = v["done"].unsqueeze(-1).expand(*shape)
         return gae(v["rewards"], values, dones, gamma, lmbda, next_values=next_values)
+
+    # ------------------------------------------------------------------------------------------------ the clipped-loss epochs
+    def _check_loaded(self):
+        self.actors._missing()
+        missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self._loaded]
+        if missing:
+            raise ValueError(f"no value networks were loaded for {missing}: load_state_dict() or bind() first")
+
+    def update_workspace_bytes(self, T, N, groups=None):
+        """Bytes the epochs allocate for a rollout of ``T`` rows of ``N`` envs, once per (T, N, groups), with R = T * N:
+        ``4 * (2 * n_agents * R * 384 + 4 * R * n_actions + min(ceil(R / 32), groups) * slab)``, slab = the actors' pack (rounded up to 4
+        floats) + the value pack + 8 * n_agents floats.  The first term holds, per network, agent and row, the forward's h', c' and four
+        gates, which back-propagation through time needs and overwrites with the gates' gradients: it grows with the rollout, about 2.2 GB
+        per network and agent at 700 x 2048 rows -- it fits the card but is not small."""
+        groups = self._groups(groups)
+        if isinstance(T, bool) or isinstance(N, bool) or not isinstance(T, (int, np.integer)) or not isinstance(N, (int, np.integer)) or T < 1 or N < 1:
+            raise ValueError("T and N must be positive integers")
+        rows = int(T) * int(N)
+        slab = -(-self.actors.pack_size // 4) * 4 + self.pack_size + 8 * self.n_agents
+        return 4 * (2 * self.n_agents * rows * ROW_FLOATS + TAIL_PLANES * rows * self.n_actions + min(-(-rows // TILE), groups) * slab)
+
+    def _epoch_launch(self, obs, actions, old_log_probs, advantages, td_target, args, groups, do_adam, want_tail=False):
+        import torch
+
+        actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, b1, b2, eps = args
+        groups = self._groups(groups)
+        T, N = self._check_epoch_inputs(obs, actions, old_log_probs, advantages, td_target)
+        d, ud, ad = self._device(), self._update_device(), self.actors._device()
+        out = self._uout.get((T, N, groups))
+        if out is None:
+            dev = torch.device("cuda", self.device)
+            rows = T * N
+            slab = -(-self.actors.pack_size // 4) * 4 + self.pack_size + 8 * self.n_agents
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+            out = self._uout[(T, N, groups)] = {"ws": z(min(-(-rows // TILE), groups), slab), "act": z(2, self.n_agents, rows, ROW_FLOATS),
+                                                "tail4": z(TAIL_PLANES, T, N, self.n_actions), "log_probs": z(T, N, self.n_actions),
+                                                "values": z(T, N, self.n_agents)}
+            assert 4 * sum(out[k].numel() for k in ("ws", "act", "tail4")) == self.update_workspace_bytes(T, N, groups)
+        self._ulast = dict(out, tail=out["tail4"][:3] if want_tail else None)
+        if ad["pack"].data_ptr() % 16:
+            raise ValueError("the actors' pack is not 16-byte aligned")
+        p = lambda t: C.c_void_p(t.data_ptr())
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        lib = _engine.lib()
+        ua, uv = ud["actor"], ud["value"]
+        with torch.cuda.device(self.device):
+            rc = lib.pedn_lstm_ppo_epoch_update(p(obs), p(actions), p(old_log_probs), p(advantages), p(td_target), p(ad["table"]), p(d["vtable"]),
+                                                p(ad["pack"]), p(d["pack"]), p(ua["grads"]), p(uv["grads"]), p(ua["raw"]), p(uv["raw"]),
+                                                p(ua["exp_avg"]), p(uv["exp_avg"]), p(ua["exp_avg_sq"]), p(uv["exp_avg_sq"]), p(out["ws"]),
+                                                p(out["act"]), p(out["tail4"]), p(ud["parts"]), p(out["log_probs"]), p(out["values"]),
+                                                p(ud["scalars"]), p(ud["adam"]), p(ud["flags"]), self.actors.pack_size, self.pack_size, T, N,
+                                                self.n_obs, self.n_actions, self.n_agents, HIDDEN, 1, int(actions.dtype == torch.float64), groups,
+                                                self.actors.min_std, self.actors.max_std, actor_lr, critic_lr, clip_eps, max_grad_norm,
+                                                kl_tolerance, b1, b2, eps, 1 if do_adam else 0, C.c_void_p(int(stream)) if stream else None)
+        if rc != 0:
+            raise _launch_failed("pedn_lstm_ppo_epoch_update", rc)
+
+    def update_store(self, store, old_log_probs, advantages, td_target, epochs=10, actor_lr=3e-4, critic_lr=6e-4, clip_eps=0.2, max_grad_norm=0.5,
+                     kl_tolerance=0.01, betas=(0.9, 0.999), eps=1e-8, groups=None):
+        """Behind ``store.finish()``, ``evaluate_store(store)``, ``compute_gae(...)`` and the caller's normalisation line: ``begin_update()``
+        and ``epochs`` times ``epoch_update`` on the store's ``obs`` and ``actions``; every env's rows are one sequence from a zero state.
+        On the current torch stream, which ``evaluate_store`` and ``compute_gae`` used too; no allocation after the first call of a shape
+        (``update_workspace_bytes``), no synchronisation: capturable as one graph."""
+        args = self._update_arguments(actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, betas, eps)
+        if isinstance(epochs, bool) or not isinstance(epochs, (int, np.integer)) or int(epochs) < 0:
+            raise ValueError(f"epochs must be an integer and not negative, got {epochs!r}")
+        groups = self._groups(groups)
+        self._check_store(store)
+        if not store.store_obs:
+            raise ValueError("the store keeps no observations (rollout_store(store_obs=True))")
+        v = store.views()
+        self._check_epoch_inputs(v["obs"], v["actions"], old_log_probs, advantages, td_target)      # before begin_update()'s launch, and with epochs = 0
+        self.begin_update()
+        for _ in range(int(epochs)):
+            self._epoch_launch(v["obs"], v["actions"], old_log_probs, advantages, td_target, args, groups, True)
 
 
 def for_env(env, delta_actions=True, max_delta=2.5, min_std=1e-3, max_std=10.0, seed=0, hidden_size=HIDDEN, num_layers=1):

@@ -69,9 +69,163 @@ def make_value_module(obs_w, stack_size):
     return Value()
 
 
-class PpoTargets:
+class EpochUpdates:
+    """What the clipped-loss epochs of ``PpoTargets`` and of ``lstm.LstmPpoTargets`` share: the arguments' checks, the gradient packs, Adam
+    state and flags on the device, the epoch calls and their outputs.  A subclass has ``actors`` (with ``pack_size`` and ``offsets``), its
+    own ``pack_size`` / ``offsets``, ``_epoch_launch``, ``_check_loaded`` and the name of its ``_BEGIN`` export."""
+
+    @staticmethod
+    def _groups(groups):
+        if groups is None:
+            return DEFAULT_GROUPS
+        if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or not 1 <= int(groups) <= 65535:
+            raise ValueError(f"groups must be an integer in 1 .. 65535, got {groups!r}")
+        return int(groups)
+
+    @staticmethod
+    def _update_arguments(actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, betas, eps):
+        try:
+            actor_lr, critic_lr, eps, (b1, b2) = float(actor_lr), float(critic_lr), float(eps), (float(b) for b in betas)
+            clip_eps, max_grad_norm, kl_tolerance = float(clip_eps), float(max_grad_norm), float(kl_tolerance)
+        except (TypeError, ValueError):
+            raise ValueError("the learning rates, eps, clip_eps, max_grad_norm and kl_tolerance must be numbers and betas a pair of numbers") from None
+        for name, lr in (("actor_lr", actor_lr), ("critic_lr", critic_lr)):
+            if not (math.isfinite(lr) and lr >= 0.0):
+                raise ValueError(f"{name} must be finite and not negative, got {lr}")
+        if not (math.isfinite(eps) and eps >= 0.0):
+            raise ValueError(f"eps must be finite and not negative, got {eps}")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must be in [0, 1), got {(b1, b2)}")
+        if not (math.isfinite(clip_eps) and clip_eps > 0.0):
+            raise ValueError(f"clip_eps must be finite and positive, got {clip_eps}")
+        if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+            raise ValueError(f"max_grad_norm must be finite and positive, got {max_grad_norm}")
+        if math.isnan(kl_tolerance):
+            raise ValueError("kl_tolerance must not be NaN")
+        return actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, b1, b2, eps
+
+    def _update_device(self):
+        if self._udev is None:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            za = lambda: torch.zeros(-(-max(1, self.actors.pack_size) // 4) * 4, dtype=torch.float32, device=dev)
+            zv = lambda: torch.zeros(self.pack_size, dtype=torch.float32, device=dev)
+            self._udev = {"actor": {k: za() for k in ("grads", "raw", "exp_avg", "exp_avg_sq")},
+                          "value": {k: zv() for k in ("grads", "raw", "exp_avg", "exp_avg_sq")},
+                          "parts": torch.zeros(self.n_agents, 2, 16, dtype=torch.float64, device=dev),
+                          "scalars": torch.zeros(len(SCALARS), self.n_agents, dtype=torch.float32, device=dev),
+                          "adam": torch.tensor([ADAM_STATE_INIT] * self.n_agents, dtype=torch.int64, device=dev),
+                          "flags": torch.zeros(self.n_agents, dtype=torch.int32, device=dev)}
+        return self._udev
+
+    def _check_epoch_inputs(self, obs, actions, old_log_probs, advantages, td_target):
+        """(T, N) of an epoch's tensors, or ValueError: everything a launch reads, checked before any launch."""
+        import torch
+
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[0] < 2 or obs.shape[1] < 1:
+            raise ValueError("obs must be a torch tensor of shape [T + 1, N, n_obs] with T >= 1")
+        T, N = int(obs.shape[0]) - 1, int(obs.shape[1])
+        packs.check_tensor("obs", obs, self.device, (T + 1, N, self.n_obs))
+        packs.check_tensor("actions", actions, self.device, (T, N, self.n_actions), (torch.float32, torch.float64))
+        packs.check_tensor("old_log_probs", old_log_probs, self.device, (T, N, self.n_actions))
+        packs.check_tensor("advantages", advantages, self.device, (T, N, self.n_agents))
+        packs.check_tensor("td_target", td_target, self.device, (T, N, self.n_agents))
+        self._check_loaded()
+        return T, N
+
+    def epoch_update(self, obs, actions, old_log_probs, advantages, td_target, actor_lr=3e-4, critic_lr=6e-4, clip_eps=0.2, max_grad_norm=0.5,
+                     kl_tolerance=0.01, betas=(0.9, 0.999), eps=1e-8, groups=None, want_tail=False):
+        """ONE epoch of the reference's clipped-loss loop for every agent, in place in the actors' pack and the value pack: both
+        forwards on every row of ``obs`` [T + 1, N, n_obs] / ``actions`` [T, N, n_actions] (``evaluate``'s inputs), the clipped surrogate
+        against ``old_log_probs`` [T, N, n_actions] and ``advantages`` [T, N, n_agents], the MSE value loss against ``td_target`` [T, N,
+        n_agents], both backward passes, ``clip_grad_norm_(max_grad_norm)`` of each network, one Adam step of each (``actor_lr``,
+        ``critic_lr``) and the KL early stop: behind the step of an epoch whose ``approx_kl > 1.5 * kl_tolerance`` the agent's flag is set,
+        and further epochs leave the agent untouched until ``begin_update()``.  ``groups``: how many slabs of the workspace share the
+        tiles of 32 rows (part of the order of the sums; ``None``: ``DEFAULT_GROUPS``).  ``want_tail``: also write ``std``, ``d_mu`` and ``d_z``
+        [T, N, n_actions] (the loss' gradients by mu and by the pre-softplus value; large for a whole rollout).  Three launches (the
+        recurrent agents: five, over each env's whole sequence) on the current torch stream; no allocation after the first call of a (T, N,
+        groups), no synchronisation: capturable."""
+        args = self._update_arguments(actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, betas, eps)
+        self._epoch_launch(obs, actions, old_log_probs, advantages, td_target, args, groups, True, want_tail)
+
+    def epoch_gradients(self, obs, actions, old_log_probs, advantages, td_target, clip_eps=0.2, max_grad_norm=0.5, groups=None, want_tail=False):
+        """The launches of ``epoch_update`` with both Adam steps and the stop switched off: writes ``epoch_outputs``; no parameter, optimiser
+        state, step count or flag changes (an agent whose flag is set is skipped all the same)."""
+        args = self._update_arguments(0.0, 0.0, clip_eps, max_grad_norm, math.inf, (0.0, 0.0), 0.0)
+        self._epoch_launch(obs, actions, old_log_probs, advantages, td_target, args, groups, False, want_tail)
+
+    def begin_update(self):
+        """Clear every agent's stop flag with a device-side write on the current torch stream (capturable): the start of an update's epochs."""
+        import torch
+
+        ud = self._update_device()
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        lib = _engine.lib()
+        with torch.cuda.device(self.device):
+            rc = getattr(lib, self._BEGIN)(C.c_void_p(ud["flags"].data_ptr()), self.n_agents, C.c_void_p(int(stream)) if stream else None)
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)(f"{self._BEGIN} failed ({rc}): {lib.pedn_last_error(None).decode()}")
+
+    class _EpochOutputs:
+        def __init__(self, owner, out):
+            sc = owner._udev["scalars"]
+            self.log_probs, self.values = out["log_probs"], out["values"]
+            self.std, self.d_mu, self.d_z = out["tail"] if out["tail"] is not None else (None, None, None)
+            for i, k in enumerate(SCALARS):
+                setattr(self, k, sc[i])
+            self.stop_flags, self._owner = owner._udev["flags"], owner
+
+        def grads(self, agent_id, which, clipped=True):
+            """{key: float32 CUDA tensor} in ``nn.Linear`` shapes, the keys of ``parameters()``: views of the gradient pack the caller
+            reads, the clipped one (``clipped=False``: what ``clip_grad_norm_`` was given)."""
+            o = self._owner
+            i, name = o._index(agent_id), o._which(which)
+            return packs.views(o._udev[name]["grads" if clipped else "raw"], (o.actors.offsets if name == "actor" else o.offsets)[i])
+
+    @staticmethod
+    def _which(which):
+        if which not in ("actor", "value"):
+            raise ValueError(f"which must be 'actor' or 'value', got {which!r}")
+        return which
+
+    @property
+    def epoch_outputs(self):
+        """What the last ``epoch_update`` / ``epoch_gradients`` wrote, float32: ``log_probs`` [T, N, n_actions], ``values`` [T, N,
+        n_agents]; per agent ``actor_loss``, ``critic_loss``, ``approx_kl``, ``actor_norm``, ``value_norm``, ``actor_coef``,
+        ``value_coef``; ``stop_flags`` int32 [n_agents]; ``grads(agent_id, "actor" | "value")``; and, when the call asked for them (``want_tail``), ``std``,
+        ``d_mu``, ``d_z`` [T, N, n_actions] (``None`` otherwise)."""
+        if self._ulast is None:
+            raise ValueError("epoch_update() has not run")
+        return self._EpochOutputs(self, self._ulast)
+
+    def adam_state(self, agent_id, which):
+        """({key: exp_avg}, {key: exp_avg_sq}) of an agent's actor or value network: views of the optimiser's packs."""
+        i, name = self._index(agent_id), self._which(which)
+        ud, off = self._update_device()[name], (self.actors.offsets if name == "actor" else self.offsets)[i]
+        return packs.views(ud["exp_avg"], off), packs.views(ud["exp_avg_sq"], off)
+
+    def adam_steps(self):
+        """[n_agents] how many Adam steps each agent's two networks have made (the device counters; waits for the device): agents stop
+        independently."""
+        return [int(v) for v in self._update_device()["adam"][:, 0].tolist()]
+
+    def reset_adam(self):
+        """Zero both networks' exp_avg and exp_avg_sq and every agent's step count."""
+        import torch
+
+        ud = self._update_device()
+        for name in ("actor", "value"):
+            ud[name]["exp_avg"].zero_()
+            ud[name]["exp_avg_sq"].zero_()
+        ud["adam"].copy_(torch.tensor([ADAM_STATE_INIT] * self.n_agents, dtype=torch.int64))
+
+
+class PpoTargets(EpochUpdates):
     """``actors``: a ``StackedActors`` of kind "ppo"; the agent table, ``min_std`` / ``max_std``, the device and the stack size are its.
     The actors' pack is read in place; the value networks live in a pack of their own."""
+
+    _BEGIN = "pedn_ppo_begin_update"
 
     def __init__(self, actors):
         if not isinstance(actors, StackedActors):
@@ -212,51 +366,6 @@ class PpoTargets:
             raise ValueError("the number of rows must be positive")
         return min(-(-int(rows) // TILE), groups), -(-self.actors.pack_size // 4) * 4 + self.pack_size + 8 * self.n_agents
 
-    @staticmethod
-    def _groups(groups):
-        if groups is None:
-            return DEFAULT_GROUPS
-        if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or not 1 <= int(groups) <= 65535:
-            raise ValueError(f"groups must be an integer in 1 .. 65535, got {groups!r}")
-        return int(groups)
-
-    @staticmethod
-    def _update_arguments(actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, betas, eps):
-        try:
-            actor_lr, critic_lr, eps, (b1, b2) = float(actor_lr), float(critic_lr), float(eps), (float(b) for b in betas)
-            clip_eps, max_grad_norm, kl_tolerance = float(clip_eps), float(max_grad_norm), float(kl_tolerance)
-        except (TypeError, ValueError):
-            raise ValueError("the learning rates, eps, clip_eps, max_grad_norm and kl_tolerance must be numbers and betas a pair of numbers") from None
-        for name, lr in (("actor_lr", actor_lr), ("critic_lr", critic_lr)):
-            if not (math.isfinite(lr) and lr >= 0.0):
-                raise ValueError(f"{name} must be finite and not negative, got {lr}")
-        if not (math.isfinite(eps) and eps >= 0.0):
-            raise ValueError(f"eps must be finite and not negative, got {eps}")
-        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
-            raise ValueError(f"betas must be in [0, 1), got {(b1, b2)}")
-        if not (math.isfinite(clip_eps) and clip_eps > 0.0):
-            raise ValueError(f"clip_eps must be finite and positive, got {clip_eps}")
-        if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
-            raise ValueError(f"max_grad_norm must be finite and positive, got {max_grad_norm}")
-        if math.isnan(kl_tolerance):
-            raise ValueError("kl_tolerance must not be NaN")
-        return actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, b1, b2, eps
-
-    def _update_device(self):
-        if self._udev is None:
-            import torch
-
-            dev = torch.device("cuda", self.device)
-            za = lambda: torch.zeros(-(-max(1, self.actors.pack_size) // 4) * 4, dtype=torch.float32, device=dev)
-            zv = lambda: torch.zeros(self.pack_size, dtype=torch.float32, device=dev)
-            self._udev = {"actor": {k: za() for k in ("grads", "raw", "exp_avg", "exp_avg_sq")},
-                          "value": {k: zv() for k in ("grads", "raw", "exp_avg", "exp_avg_sq")},
-                          "parts": torch.zeros(self.n_agents, 2, 16, dtype=torch.float64, device=dev),
-                          "scalars": torch.zeros(len(SCALARS), self.n_agents, dtype=torch.float32, device=dev),
-                          "adam": torch.tensor([ADAM_STATE_INIT] * self.n_agents, dtype=torch.int64, device=dev),
-                          "flags": torch.zeros(self.n_agents, dtype=torch.int32, device=dev)}
-        return self._udev
-
     def _epoch_launch(self, obs, actions, old_log_probs, advantages, td_target, args, groups, do_adam, want_tail=False):
         import torch
 
@@ -291,21 +400,6 @@ class PpoTargets:
         if rc != 0:
             raise (ValueError if rc == -1 else RuntimeError)(f"pedn_ppo_epoch_update failed ({rc}): {lib.pedn_last_error(None).decode()}")
 
-    def _check_epoch_inputs(self, obs, actions, old_log_probs, advantages, td_target):
-        """(T, N) of an epoch's tensors, or ValueError: everything a launch reads, checked before any launch."""
-        import torch
-
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[0] < 2 or obs.shape[1] < 1:
-            raise ValueError("obs must be a torch tensor of shape [T + 1, N, n_obs] with T >= 1")
-        T, N = int(obs.shape[0]) - 1, int(obs.shape[1])
-        packs.check_tensor("obs", obs, self.device, (T + 1, N, self.n_obs))
-        packs.check_tensor("actions", actions, self.device, (T, N, self.n_actions), (torch.float32, torch.float64))
-        packs.check_tensor("old_log_probs", old_log_probs, self.device, (T, N, self.n_actions))
-        packs.check_tensor("advantages", advantages, self.device, (T, N, self.n_agents))
-        packs.check_tensor("td_target", td_target, self.device, (T, N, self.n_agents))
-        self._check_loaded()
-        return T, N
-
     def _check_loaded(self):
         missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self.actors._loaded]
         if missing:
@@ -313,38 +407,6 @@ class PpoTargets:
         missing = [self.agent_ids[i] for i in range(self.n_agents) if i not in self._loaded]
         if missing:
             raise ValueError(f"no value networks were loaded for {missing}: load_state_dict() or bind() first")
-
-    def epoch_update(self, obs, actions, old_log_probs, advantages, td_target, actor_lr=3e-4, critic_lr=6e-4, clip_eps=0.2, max_grad_norm=0.5,
-                     kl_tolerance=0.01, betas=(0.9, 0.999), eps=1e-8, groups=None, want_tail=False):
-        """ONE epoch of the reference's clipped-loss loop for every agent, in place in the ``StackedActors`` pack and the value pack: both
-        forwards on every row of ``obs`` [T + 1, N, n_obs] / ``actions`` [T, N, n_actions] (``evaluate``'s inputs), the clipped surrogate
-        against ``old_log_probs`` [T, N, n_actions] and ``advantages`` [T, N, n_agents], the MSE value loss against ``td_target`` [T, N,
-        n_agents], both backward passes, ``clip_grad_norm_(max_grad_norm)`` of each network, one Adam step of each (``actor_lr``,
-        ``critic_lr``) and the KL early stop: behind the step of an epoch whose ``approx_kl > 1.5 * kl_tolerance`` the agent's flag is set,
-        and further epochs leave the agent untouched until ``begin_update()``.  ``groups``: how many slabs of the workspace share the
-        tiles of 32 rows (part of the order of the sums; ``None``: ``DEFAULT_GROUPS``).  ``want_tail``: also write ``std``, ``d_mu`` and ``d_z``
-        [T, N, n_actions] (the loss' gradients by mu and by the pre-softplus value; large for a whole rollout).  Three launches on the
-        current torch stream; no allocation after the first call of a (T, N, groups), no synchronisation: capturable."""
-        args = self._update_arguments(actor_lr, critic_lr, clip_eps, max_grad_norm, kl_tolerance, betas, eps)
-        self._epoch_launch(obs, actions, old_log_probs, advantages, td_target, args, groups, True, want_tail)
-
-    def epoch_gradients(self, obs, actions, old_log_probs, advantages, td_target, clip_eps=0.2, max_grad_norm=0.5, groups=None, want_tail=False):
-        """The launches of ``epoch_update`` with both Adam steps and the stop switched off: writes ``epoch_outputs``; no parameter, optimiser
-        state, step count or flag changes (an agent whose flag is set is skipped all the same)."""
-        args = self._update_arguments(0.0, 0.0, clip_eps, max_grad_norm, math.inf, (0.0, 0.0), 0.0)
-        self._epoch_launch(obs, actions, old_log_probs, advantages, td_target, args, groups, False, want_tail)
-
-    def begin_update(self):
-        """Clear every agent's stop flag with a device-side write on the current torch stream (capturable): the start of an update's epochs."""
-        import torch
-
-        ud = self._update_device()
-        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
-        lib = _engine.lib()
-        with torch.cuda.device(self.device):
-            rc = lib.pedn_ppo_begin_update(C.c_void_p(ud["flags"].data_ptr()), self.n_agents, C.c_void_p(int(stream)) if stream else None)
-        if rc != 0:
-            raise (ValueError if rc == -1 else RuntimeError)(f"pedn_ppo_begin_update failed ({rc}): {lib.pedn_last_error(None).decode()}")
 
     def update_store(self, store, old_log_probs, advantages, td_target, epochs=10, actor_lr=3e-4, critic_lr=6e-4, clip_eps=0.2, max_grad_norm=0.5,
                      kl_tolerance=0.01, betas=(0.9, 0.999), eps=1e-8, groups=None):
@@ -380,60 +442,6 @@ class PpoTargets:
         self.begin_update()
         for _ in range(int(epochs)):
             self._epoch_launch(v["obs"], v["actions"], old_log_probs, advantages, td_target, args, groups, True)
-
-    class _EpochOutputs:
-        def __init__(self, owner, out):
-            sc = owner._udev["scalars"]
-            self.log_probs, self.values = out["log_probs"], out["values"]
-            self.std, self.d_mu, self.d_z = out["tail"] if out["tail"] is not None else (None, None, None)
-            for i, k in enumerate(SCALARS):
-                setattr(self, k, sc[i])
-            self.stop_flags, self._owner = owner._udev["flags"], owner
-
-        def grads(self, agent_id, which, clipped=True):
-            """{key: float32 CUDA tensor} in ``nn.Linear`` shapes, the keys of ``parameters()``: views of the gradient pack the caller
-            reads, the clipped one (``clipped=False``: what ``clip_grad_norm_`` was given)."""
-            o = self._owner
-            i, name = o._index(agent_id), o._which(which)
-            return packs.views(o._udev[name]["grads" if clipped else "raw"], (o.actors.offsets if name == "actor" else o.offsets)[i])
-
-    @staticmethod
-    def _which(which):
-        if which not in ("actor", "value"):
-            raise ValueError(f"which must be 'actor' or 'value', got {which!r}")
-        return which
-
-    @property
-    def epoch_outputs(self):
-        """What the last ``epoch_update`` / ``epoch_gradients`` wrote, float32: ``log_probs`` [T, N, n_actions], ``values`` [T, N,
-        n_agents]; per agent ``actor_loss``, ``critic_loss``, ``approx_kl``, ``actor_norm``, ``value_norm``, ``actor_coef``,
-        ``value_coef``; ``stop_flags`` int32 [n_agents]; ``grads(agent_id, "actor" | "value")``; and, when the call asked for them (``want_tail``), ``std``,
-        ``d_mu``, ``d_z`` [T, N, n_actions] (``None`` otherwise)."""
-        if self._ulast is None:
-            raise ValueError("epoch_update() has not run")
-        return self._EpochOutputs(self, self._ulast)
-
-    def adam_state(self, agent_id, which):
-        """({key: exp_avg}, {key: exp_avg_sq}) of an agent's actor or value network: views of the optimiser's packs."""
-        i, name = self._index(agent_id), self._which(which)
-        ud, off = self._update_device()[name], (self.actors.offsets if name == "actor" else self.offsets)[i]
-        return packs.views(ud["exp_avg"], off), packs.views(ud["exp_avg_sq"], off)
-
-    def adam_steps(self):
-        """[n_agents] how many Adam steps each agent's two networks have made (the device counters; waits for the device): agents stop
-        independently."""
-        return [int(v) for v in self._update_device()["adam"][:, 0].tolist()]
-
-    def reset_adam(self):
-        """Zero both networks' exp_avg and exp_avg_sq and every agent's step count."""
-        import torch
-
-        ud = self._update_device()
-        for name in ("actor", "value"):
-            ud[name]["exp_avg"].zero_()
-            ud[name]["exp_avg_sq"].zero_()
-        ud["adam"].copy_(torch.tensor([ADAM_STATE_INIT] * self.n_agents, dtype=torch.int64))
-
 
 def for_env(env, actors):
     """``PpoTargets`` over the stacked actors of a ``VecPedNetEnv``."""
